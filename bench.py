@@ -14,7 +14,11 @@ all_gather of the poses (RCCL), which is inside the timed region.
 one the metric is quoted on (32 pairs at N=5000: 32 / N per GPU = strong scaling; --pairs-per-gpu fixes the
 per-GPU batch instead).  n1000_b1, kitti_n5000_b16 and lomatch_n10000_b8 are configs[1], [3], [4].
 
-Rank 0 prints ONE JSON line.  Besides the contract fields it carries
+Rank 0 prints ONE JSON line.  A plain run does only what that line's headline needs: set-up, the W warm-up steps and the
+untimed --settle-seconds load, the K timed steps, and the line (metric, value, unit, higher_is_better, dtype, ms_per_step and
+the configuration).  --dump-outputs DIR writes what the last timed step returned (rank 0's final_trans and final_labels, plus
+the gathered poses with N > 1) as DIR/<name>.npy in float32; the inputs are seeded, so two builds can be compared output for
+output.  With --full the line also carries every leg and figure below (each needs runs of its own):
   roofline        -- the dominant kernel (sc_attention_split_kernel, MFMA-bound: every fp32 product as three f16
                      MFMAs, fp32 accumulate): algorithmic flops per launch / average launch duration measured with
                      hipEvents on the launch stream over the timed region (pdsc_profile_* in include/pointdsc_hip.h);
@@ -335,12 +339,42 @@ def extra_leg(config, over, what, args, dev, lib, census_mod, use_tail):
     return out
 
 
+DUMP_CAP_BYTES = 64 * 10**6      # --dump-outputs: at most 64 MB in all
+
+
+def dump_outputs(path, res, gathered_trans=None):
+    """--dump-outputs: what the last timed step returned, as <path>/<name>.npy in float32 -- final_trans [B, 4, 4] and final_labels
+    [B, N] of this rank's shard, and with N > 1 ranks the gathered poses of all ranks.  An array larger than its share of the cap
+    is stored as a fixed, seeded sample of its rows (the row indices next to it as <name>_rows.npy)."""
+    import numpy as np
+    arrays = {k: res[k] for k in ("final_trans", "final_labels")}
+    if gathered_trans is not None:
+        arrays["gathered_final_trans"] = gathered_trans
+    out = Path(path)
+    out.mkdir(parents=True, exist_ok=True)
+    share = DUMP_CAP_BYTES // (2 * len(arrays))       # (room for the row indices of a sampled array)
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        row_bytes = max(a[0].nbytes if a.shape[0] else 1, 1)
+        if a.nbytes > share:
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], size=max(1, share // row_bytes), replace=False))
+            a = a[rows]
+            np.save(out / f"{name}_rows.npy", rows.astype(np.float64))
+        np.save(out / f"{name}.npy", np.ascontiguousarray(a, dtype=np.float32))
+    log(f"outputs of the last timed step written to {out}: {', '.join(sorted(arrays))}")
+
+
 def parse():
     from pointdsc_amd import workloads
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every other leg of the line: parity check, sustained leg and power, single-stream "
+                         "leg with the roofline events, extra legs, CPU baseline (off: the headline figure only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float32, at most 64 MB in all)")
     ap.add_argument("--config", choices=sorted(workloads.WORKLOADS), default=workloads.DEFAULT,
                     help="BASELINE.json configuration (default: configs[2], the one the metric is quoted on)")
     ap.add_argument("--global-batch", type=int, default=0, help="override the configuration's pairs per step over ALL GPUs")
@@ -359,9 +393,9 @@ def parse():
     ap.add_argument("--range-guard", choices=["sync", "lazy", "off"], default=None,
                     help="--latency: the module's fp16 range guard for the plain calls (default: the module's own, 'sync': the call waits for the "
                          "forward and reads the range words the last launch left in pinned host memory; 'lazy': the call returns at once)")
-    ap.add_argument("--no-check", action="store_true", help="skip the parity check of this run's outputs")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--sustain-seconds", type=float, default=2.0, help="extra measured leg after the timed region (0 = off)")
+    ap.add_argument("--no-check", action="store_true", help="--full: skip the parity check of this run's outputs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline leg")
+    ap.add_argument("--sustain-seconds", type=float, default=2.0, help="--full: extra measured leg after the timed region (0 = off)")
     ap.add_argument("--in-flight", type=int, default=0,
                     help="forwards in flight: consecutive steps alternate between this many HIP streams (pointdsc_amd/pipeline.py); "
                          "1 = every step on the current stream; 0 = 2, or 6 captured hipGraphs (zero-copy replays) when a step is one small problem (<= 4096 "
@@ -386,9 +420,9 @@ def parse():
     ap.add_argument("--force-port", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--check-pairs", type=int, default=2, help=argparse.SUPPRESS)
     ap.add_argument("--extra", choices=["auto", "on", "off"], default="auto",
-                    help="after the headline, short legs (<= 3 s each) of the lines the headline does not show, each with its own parity "
+                    help="--full: after the headline, short legs (<= 3 s each) of the lines the headline does not show, each with its own parity "
                          "check, printed under `extra`: the trained-like checkpoint of the same configuration and the headline workload with the "
-                         "bit-exact fp32 spatial-consistency matrix (auto: on for the default invocation -- one GPU, default config, no --latency)")
+                         "bit-exact fp32 spatial-consistency matrix (auto: on for the default --full invocation -- one GPU, default config, no --latency)")
     ap.add_argument("--extra-seconds", type=float, default=1.5, help="timed length of each extra leg")
     ap.add_argument("--first-pair", type=int, default=0,
                     help="start the workload's pair list at this pair (default 0 = the configuration as BASELINE.json quotes it); e.g. "
@@ -414,6 +448,7 @@ def fp32_att(args):
 
 def main():
     args = parse()
+    full = args.full
     if args.cpu_baseline_worker:
         cpu_baseline_worker(args.config, args.cpu_pairs, args.cpu_threads or (os.cpu_count() or 1), args.check_pairs, args.force_port)
         return
@@ -561,8 +596,8 @@ def main():
 
     # With several forwards in flight the kernels of two streams share the chip, so a kernel's event-to-event time is no longer
     # its own duration: the roofline events are then recorded during the single-stream K steps that follow the timed region
-    # (same run, same data); with --in-flight 1 they are recorded during the timed region itself.
-    if depth["d"] == 1:
+    # (same run, same data); with --in-flight 1 they are recorded during the timed region itself.  (--full only)
+    if full and depth["d"] == 1:
         events_on()
     fence()
     t0 = time.perf_counter()
@@ -578,18 +613,21 @@ def main():
     # sharded over 8 GPUs must print the same fingerprint as the one-GPU run of the same pairs (tests/test_sharding_gloo.py)
     import hashlib
     poses_sha = hashlib.sha256(out["final_trans"].detach().cpu().contiguous().numpy().tobytes()).hexdigest()[:16] if isinstance(out, dict) else None
-    # ... and the discrete decisions of that forward (seeds, votes, chosen hypothesis, refinement trace, neighbour sets), read from
-    # its workspace before the next leg overwrites it: what tools/parity_census.py:explain needs should a pair leave the contract
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, timed_res, out["final_trans"] if world > 1 else None)
+    # ... and (--full) the discrete decisions of that forward (seeds, votes, chosen hypothesis, refinement trace, neighbour sets), read
+    # from its workspace before the next leg overwrites it: what tools/parity_census.py:explain needs should a pair leave the contract
     timed_dec, census_mod = None, None
-    try:
-        import importlib.util
-        _spec = importlib.util.spec_from_file_location("parity_census", ROOT / "tools" / "parity_census.py")
-        census_mod = importlib.util.module_from_spec(_spec)
-        _spec.loader.exec_module(census_mod)
-        if not (runners[in_flight].graphs and runners[in_flight]._captured):
-            timed_dec = census_mod.decisions(model, B, N)
-    except Exception as e:  # noqa: BLE001
-        log(f"decisions of the timed forward not available: {e!r}")
+    if full:
+        try:
+            import importlib.util
+            _spec = importlib.util.spec_from_file_location("parity_census", ROOT / "tools" / "parity_census.py")
+            census_mod = importlib.util.module_from_spec(_spec)
+            _spec.loader.exec_module(census_mod)
+            if not (runners[in_flight].graphs and runners[in_flight]._captured):
+                timed_dec = census_mod.decisions(model, B, N)
+        except Exception as e:  # noqa: BLE001
+            log(f"decisions of the timed forward not available: {e!r}")
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev if args.backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -601,14 +639,14 @@ def main():
         _lib.check(lib.pdsc_profile_read(kind, C.byref(ms), C.byref(n)), "pdsc_profile_read")
         return ms.value, n.value
 
-    if depth["d"] == 1:
+    if full and depth["d"] == 1:
         (att_ms, att_n), (cmp_ms, cmp_n), (lay_ms, lay_n) = read(0), read(1), read(2)
         _lib.check(lib.pdsc_profile_enable(0), "pdsc_profile_enable(0)")
 
     # ---- sustained leg: the same step for >= sustain_seconds (same step count on every rank) ----
     sustained = None
     power = None
-    if args.sustain_seconds > 0:
+    if full and args.sustain_seconds > 0:
         n_sus = max(args.steps, min(2000, int(math.ceil(args.sustain_seconds / max(elapsed / args.steps, 1e-6)))))
         fence()
         sampler = None
@@ -638,7 +676,7 @@ def main():
 
     # ---- the same K steps with every forward on ONE stream (no forwards in flight): reported next to `value` ----
     single = None
-    if depth["d"] > 1:
+    if full and depth["d"] > 1:
         depth["d"] = 1
         for _ in range(3):
             step()
@@ -660,7 +698,7 @@ def main():
         depth["d"] = in_flight
 
     rccl_probe = None
-    if solo_pg:
+    if full and solo_pg:
         # one all_gather of the pose payload through RCCL with world size 1 (gather_results itself short-circuits at world 1)
         payload = last["res"]["final_trans"].reshape(-1, 16).contiguous()
         flat = torch.empty_like(payload)
@@ -672,56 +710,12 @@ def main():
             dist.destroy_process_group()
         return
 
-    # fused layer launch (tail of layer i + head of layer i+1).  With layer_gemm = "h3" on the wavefront-resident kernel (the
-    # shipped default wherever pdsc_layer_prefers_block is 0) it is reported against HBM (`lay_bytes` below); the matrix-pipe
-    # figure (600 fp32 MFMAs x 64 + 288 f16 MFMAs x 32 cycles per 32-point tile) is only reported for layer_gemm = "f32" /
-    # the workgroup-per-tile kernel.  2 flop/MAC x (128*64 + 64*64 + 64*128 + 128*128 + 128*384) MACs per point
-    lay_flops = 2.0 * 86016 * N * B
-    lay_avg = lay_ms / max(lay_n, 1) * 1e-3
-    lay_pipe_cycles = (600 * 64 + 288 * 32) * math.ceil(N / 32) * B / 1024.0      # per SIMD (256 CUs x 4)
-    lay_ghz = lay_pipe_cycles / lay_avg / 1e9 if lay_n else None
-    # with the H3 GEMMs (model.layer_gemm = "h3", wavefront-resident kernel) the launch needs 16 k matrix-pipe cycles per tile
-    # and is bound by HBM: per point it reads the key-split partials (ns x (512 + 8) B) and the residual row (512 B) and
-    # writes featB (512 B), the Q rows (512 B) and its share of the K/V tile image (32 KiB / 32)
+    # what `dtype` names: the H3 GEMMs of the layer launch and the unorm16 spatial-consistency matrix
     lay_h3 = (not fp32_att(args)) and model.layer_gemm == "h3"      # (since r03 the H3 arithmetic has its own kernels at every size)
-    # (leaf form: one partial per LEAF)
-    lay_ns = int(lib.pdsc_attention_split_default_split(B, N))
-    if lay_h3 and model.att_leaves != "per_launch":
-        lay_ns = attention_plan(lib, B, N, model.att_leaves)["leaves"]
-    # r06: `bytes_per_launch` is the MINIMAL traffic of the fused launch, fixed by the algorithm and independent
-    # of how the attention split its keys: per point ONE message row in (512 B) + the residual row in (512 B), featB (512 B), the Q
-    # rows (fp16 hi|lo, 512 B) and the point's share of the K/V tile image (32 KiB / 32 = 1024 B) out = 3072 B.  What this
-    # implementation moves on top (one 520-byte partial per LEAF instead of one merged message) is reported as `moved_bytes`.
-    lay_bytes = 3072.0 * N * B
-    lay_moved = (520.0 * lay_ns + 512 + 512 + 512 + 32768 / 32.0) * N * B
-    lay_gbs = lay_bytes / lay_avg / 1e9 if lay_n else None
-    att_flops = 4.0 * 128 * float(N) * float(N) * B           # 2 GEMMs x 2 flop/MAC x C x N^2 per pair, per launch
-    att_avg = att_ms / max(att_n, 1) * 1e-3
-    att_tflops = att_flops / att_avg / 1e12 if att_n else None
-    # compat write + keypoint reads; the matrix is stored as unorm16 (2 B per entry) unless
-    # model.compat_format = "f32" 
     c16 = (not fp32_att(args)) and model.compat_format == "u16"
-    cmp_bytes = ((2.0 if c16 else 4.0) * N * N + 24.0 * N) * B
-    cmp_avg = cmp_ms / max(cmp_n, 1) * 1e-3
-    cmp_gbs = cmp_bytes / cmp_avg / 1e9 if cmp_n else None
     fp32 = args.attention_precision == "fp32"
-    att_peak = PEAK_FP32_MFMA_TFLOPS if fp32 else PEAK_F16_MFMA_TFLOPS
 
     value = total_pairs * args.steps / elapsed
-    roof = {"kernel": "sc_attention_kernel" if fp32 else "sc_attention_split_kernel", "bound": "mfma",
-            "achieved": None if att_tflops is None else round(att_tflops, 2), "peak": att_peak, "unit": "TFLOP/s",
-            "frac": None if att_tflops is None else round(att_tflops / att_peak, 4),
-            "traffic": None, "launches": att_n, "launches_per_forward": n_layers, "avg_launch_ms": round(att_avg * 1e3, 4),
-            "flops_per_launch": att_flops,
-            "timing": "hipEvents on the launch stream around one launch per forward (the %d launches of a forward do identical work), "
-                      "recorded during %s" % (n_layers, "the timed region" if depth["d"] == 1 else
-                                              "the single-stream K steps right after the timed region (with forwards in flight the "
-                                              "kernels of two streams overlap and an event pair no longer times one kernel)")}
-    if not fp32:
-        # `achieved` counts ALGORITHMIC flops (4 C N^2 per pair per launch) against the dense BF16/FP16 MFMA peak (one row of the guide); the kernel
-        # executes 3 f16 MFMAs per algorithmic product (hi*hi, hi*lo, lo*hi): its matrix-pipe share is 3 x frac.
-        roof["executed_tflops"] = None if att_tflops is None else round(3 * att_tflops, 2)
-        roof["executed_frac"] = None if att_tflops is None else round(3 * att_tflops / att_peak, 4)
     line = {
         "metric": "point-cloud pairs/sec @ N=%d corr" % N,
         "value": round(value, 3), "unit": "pairs/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -749,32 +743,80 @@ def main():
                                   % (world, ("no collective (single process)" if not (world > 1 or solo_pg) else
                                              "one all_gather of poses (%s)" % ("RCCL" if args.backend == "nccl" else "gloo rehearsal, ranks share the GPU")), depth["d"],
                                      ", each replayed as a captured hipGraph" if (runners[in_flight].graphs and runners[in_flight]._captured) else "")},
-        "roofline": roof,
-        # H3 kernel: algorithmic HBM bytes per launch / its duration against 8 TB/s; otherwise matrix-pipe issue cycles the
-        # launch needs per SIMD / its duration, against a pipe that is busy every cycle at the maximum clock
-        "roofline_layer": ({"kernel": "layer_h3_coop_kernel" if lib.pdsc_layer_h3_uses_coop(B, N) else "layer_h3_kernel", "bound": "hbm",
-                            "achieved": None if lay_gbs is None else round(lay_gbs, 1), "peak": PEAK_HBM_GBS, "unit": "GB/s",
-                            "frac": None if lay_gbs is None else round(lay_gbs / PEAK_HBM_GBS, 4),
-                            "traffic": None, "launches": lay_n, "avg_launch_ms": round(lay_avg * 1e3, 4),
-                            "bytes_per_launch": lay_bytes, "bytes_per_point": 3072, "moved_bytes": lay_moved,
-                            "moved_bytes_per_point": 520 * lay_ns + 2560, "partials_read_per_point": lay_ns,
-                            "moved_frac": None if not lay_n else round(lay_moved / lay_avg / 1e9 / PEAK_HBM_GBS, 4),
-                            "flops_per_launch": lay_flops} if lay_h3 else
-                           {"kernel": "layer_wave_kernel" if not lib.pdsc_layer_prefers_block(B, N) else "layer_fused_kernel",
-                            "bound": "mfma", "achieved": None if lay_ghz is None else round(lay_ghz, 4), "peak": MAX_CLOCK_GHZ,
-                            "unit": "G matrix-pipe cycles/s per SIMD",
-                            "frac": None if lay_ghz is None else round(lay_ghz / MAX_CLOCK_GHZ, 4),
-                            "traffic": None, "launches": lay_n, "avg_launch_ms": round(lay_avg * 1e3, 4),
-                            "flops_per_launch": lay_flops}),
-        "roofline_compat": {"kernel": "compat_sym_u16_kernel" if c16 else "compat_sym_kernel", "bound": "hbm",
-                            "achieved": None if cmp_gbs is None else round(cmp_gbs, 1), "peak": PEAK_HBM_GBS,
-                            "unit": "GB/s", "frac": None if cmp_gbs is None else round(cmp_gbs / PEAK_HBM_GBS, 4),
-                            "traffic": None, "launches": cmp_n, "avg_launch_ms": round(cmp_avg * 1e3, 4),
-                            "bytes_per_launch": cmp_bytes},
     }
-    if sustained is not None:
-        line["sustained"] = sustained
-    line["power"] = power
+    if full:
+        # fused layer launch (tail of layer i + head of layer i+1).  With layer_gemm = "h3" on the wavefront-resident kernel (the
+        # shipped default wherever pdsc_layer_prefers_block is 0) it is reported against HBM (`lay_bytes` below); the matrix-pipe
+        # figure (600 fp32 MFMAs x 64 + 288 f16 MFMAs x 32 cycles per 32-point tile) is only reported for layer_gemm = "f32" /
+        # the workgroup-per-tile kernel.  2 flop/MAC x (128*64 + 64*64 + 64*128 + 128*128 + 128*384) MACs per point
+        lay_flops = 2.0 * 86016 * N * B
+        lay_avg = lay_ms / max(lay_n, 1) * 1e-3
+        lay_pipe_cycles = (600 * 64 + 288 * 32) * math.ceil(N / 32) * B / 1024.0      # per SIMD (256 CUs x 4)
+        lay_ghz = lay_pipe_cycles / lay_avg / 1e9 if lay_n else None
+        # with the H3 GEMMs (model.layer_gemm = "h3", wavefront-resident kernel) the launch needs 16 k matrix-pipe cycles per tile
+        # and is bound by HBM: per point it reads the key-split partials (ns x (512 + 8) B) and the residual row (512 B) and
+        # writes featB (512 B), the Q rows (512 B) and its share of the K/V tile image (32 KiB / 32)
+        # (leaf form: one partial per LEAF)
+        lay_ns = int(lib.pdsc_attention_split_default_split(B, N))
+        if lay_h3 and model.att_leaves != "per_launch":
+            lay_ns = attention_plan(lib, B, N, model.att_leaves)["leaves"]
+        # r06: `bytes_per_launch` is the MINIMAL traffic of the fused launch, fixed by the algorithm and independent
+        # of how the attention split its keys: per point ONE message row in (512 B) + the residual row in (512 B), featB (512 B), the Q
+        # rows (fp16 hi|lo, 512 B) and the point's share of the K/V tile image (32 KiB / 32 = 1024 B) out = 3072 B.  What this
+        # implementation moves on top (one 520-byte partial per LEAF instead of one merged message) is reported as `moved_bytes`.
+        lay_bytes = 3072.0 * N * B
+        lay_moved = (520.0 * lay_ns + 512 + 512 + 512 + 32768 / 32.0) * N * B
+        lay_gbs = lay_bytes / lay_avg / 1e9 if lay_n else None
+        att_flops = 4.0 * 128 * float(N) * float(N) * B           # 2 GEMMs x 2 flop/MAC x C x N^2 per pair, per launch
+        att_avg = att_ms / max(att_n, 1) * 1e-3
+        att_tflops = att_flops / att_avg / 1e12 if att_n else None
+        # compat write + keypoint reads; the matrix is stored as unorm16 (2 B per entry) unless
+        # model.compat_format = "f32" 
+        cmp_bytes = ((2.0 if c16 else 4.0) * N * N + 24.0 * N) * B
+        cmp_avg = cmp_ms / max(cmp_n, 1) * 1e-3
+        cmp_gbs = cmp_bytes / cmp_avg / 1e9 if cmp_n else None
+        att_peak = PEAK_FP32_MFMA_TFLOPS if fp32 else PEAK_F16_MFMA_TFLOPS
+        roof = {"kernel": "sc_attention_kernel" if fp32 else "sc_attention_split_kernel", "bound": "mfma",
+                "achieved": None if att_tflops is None else round(att_tflops, 2), "peak": att_peak, "unit": "TFLOP/s",
+                "frac": None if att_tflops is None else round(att_tflops / att_peak, 4),
+                "traffic": None, "launches": att_n, "launches_per_forward": n_layers, "avg_launch_ms": round(att_avg * 1e3, 4),
+                "flops_per_launch": att_flops,
+                "timing": "hipEvents on the launch stream around one launch per forward (the %d launches of a forward do identical work), "
+                          "recorded during %s" % (n_layers, "the timed region" if depth["d"] == 1 else
+                                                  "the single-stream K steps right after the timed region (with forwards in flight the "
+                                                  "kernels of two streams overlap and an event pair no longer times one kernel)")}
+        if not fp32:
+            # `achieved` counts ALGORITHMIC flops (4 C N^2 per pair per launch) against the dense BF16/FP16 MFMA peak (one row of the guide); the kernel
+            # executes 3 f16 MFMAs per algorithmic product (hi*hi, hi*lo, lo*hi): its matrix-pipe share is 3 x frac.
+            roof["executed_tflops"] = None if att_tflops is None else round(3 * att_tflops, 2)
+            roof["executed_frac"] = None if att_tflops is None else round(3 * att_tflops / att_peak, 4)
+        line.update({
+            "roofline": roof,
+            # H3 kernel: algorithmic HBM bytes per launch / its duration against 8 TB/s; otherwise matrix-pipe issue cycles the
+            # launch needs per SIMD / its duration, against a pipe that is busy every cycle at the maximum clock
+            "roofline_layer": ({"kernel": "layer_h3_coop_kernel" if lib.pdsc_layer_h3_uses_coop(B, N) else "layer_h3_kernel", "bound": "hbm",
+                                "achieved": None if lay_gbs is None else round(lay_gbs, 1), "peak": PEAK_HBM_GBS, "unit": "GB/s",
+                                "frac": None if lay_gbs is None else round(lay_gbs / PEAK_HBM_GBS, 4),
+                                "traffic": None, "launches": lay_n, "avg_launch_ms": round(lay_avg * 1e3, 4),
+                                "bytes_per_launch": lay_bytes, "bytes_per_point": 3072, "moved_bytes": lay_moved,
+                                "moved_bytes_per_point": 520 * lay_ns + 2560, "partials_read_per_point": lay_ns,
+                                "moved_frac": None if not lay_n else round(lay_moved / lay_avg / 1e9 / PEAK_HBM_GBS, 4),
+                                "flops_per_launch": lay_flops} if lay_h3 else
+                               {"kernel": "layer_wave_kernel" if not lib.pdsc_layer_prefers_block(B, N) else "layer_fused_kernel",
+                                "bound": "mfma", "achieved": None if lay_ghz is None else round(lay_ghz, 4), "peak": MAX_CLOCK_GHZ,
+                                "unit": "G matrix-pipe cycles/s per SIMD",
+                                "frac": None if lay_ghz is None else round(lay_ghz / MAX_CLOCK_GHZ, 4),
+                                "traffic": None, "launches": lay_n, "avg_launch_ms": round(lay_avg * 1e3, 4),
+                                "flops_per_launch": lay_flops}),
+            "roofline_compat": {"kernel": "compat_sym_u16_kernel" if c16 else "compat_sym_kernel", "bound": "hbm",
+                                "achieved": None if cmp_gbs is None else round(cmp_gbs, 1), "peak": PEAK_HBM_GBS,
+                                "unit": "GB/s", "frac": None if cmp_gbs is None else round(cmp_gbs / PEAK_HBM_GBS, 4),
+                                "traffic": None, "launches": cmp_n, "avg_launch_ms": round(cmp_avg * 1e3, 4),
+                                "bytes_per_launch": cmp_bytes},
+        })
+        if sustained is not None:
+            line["sustained"] = sustained
+        line["power"] = power
     line["in_flight"] = depth["d"]
     if rccl_probe is not None:
         line["rccl_world1_probe"] = rccl_probe
@@ -783,27 +825,28 @@ def main():
     line["zero_copy_graphs"] = bool(runners[in_flight].zero_copy and line["hip_graphs"])
     if single is not None:
         line["single_stream"] = single
-    # PMC-derived HBM bytes per launch (tools/traffic_from_pmc.py writes profiles/traffic.json with the digest of the library sources it
-    # was collected on): used only when that digest is THIS library's -- a figure from another build is not this run's traffic (r05's
-    # line carried r04's number this way)
-    traffic_file = ROOT / "profiles" / "traffic.json"
-    line["traffic_source"] = None
-    if traffic_file.exists():
-        try:
-            from pointdsc_amd import build as _build
-            tj = json.loads(traffic_file.read_text())
-            key = f"{args.config}_B{B}" + ("_u16" if c16 else "")
-            digest = _build.source_digest()
-            if tj.get("_library_source_sha256") != digest:
-                line["traffic_source"] = "profiles/traffic.json ignored: collected on library sources %s, this run's are %s" % (
-                    str(tj.get("_library_source_sha256"))[:12], digest[:12])
-            elif key in tj:
-                line["roofline"]["traffic"] = tj[key].get(line["roofline"]["kernel"])
-                line["roofline_compat"]["traffic"] = tj[key].get(line["roofline_compat"]["kernel"])
-                line["roofline_layer"]["traffic"] = tj[key].get(line["roofline_layer"]["kernel"])
-                line["traffic_source"] = "profiles/traffic.json (%s; library sources %s = this build)" % (tj.get("_collected", "rocprofv3 --pmc"), digest[:12])
-        except Exception as e:  # noqa: BLE001
-            line["traffic_source"] = "profiles/traffic.json unreadable: %r" % (e,)
+    if full:
+        # PMC-derived HBM bytes per launch (tools/traffic_from_pmc.py writes profiles/traffic.json with the digest of the library sources it
+        # was collected on): used only when that digest is THIS library's -- a figure from another build is not this run's traffic (r05's
+        # line carried r04's number this way)
+        traffic_file = ROOT / "profiles" / "traffic.json"
+        line["traffic_source"] = None
+        if traffic_file.exists():
+            try:
+                from pointdsc_amd import build as _build
+                tj = json.loads(traffic_file.read_text())
+                key = f"{args.config}_B{B}" + ("_u16" if c16 else "")
+                digest = _build.source_digest()
+                if tj.get("_library_source_sha256") != digest:
+                    line["traffic_source"] = "profiles/traffic.json ignored: collected on library sources %s, this run's are %s" % (
+                        str(tj.get("_library_source_sha256"))[:12], digest[:12])
+                elif key in tj:
+                    line["roofline"]["traffic"] = tj[key].get(line["roofline"]["kernel"])
+                    line["roofline_compat"]["traffic"] = tj[key].get(line["roofline_compat"]["kernel"])
+                    line["roofline_layer"]["traffic"] = tj[key].get(line["roofline_layer"]["kernel"])
+                    line["traffic_source"] = "profiles/traffic.json (%s; library sources %s = this build)" % (tj.get("_collected", "rocprofv3 --pmc"), digest[:12])
+            except Exception as e:  # noqa: BLE001
+                line["traffic_source"] = "profiles/traffic.json unreadable: %r" % (e,)
 
     # ---- parity of this run's outputs, part 1: EVERY pair of rank 0's shard against the unmodified reference's outputs on
     #      the same pairs (tests/golden/census_<config>.npz: its fp32 and its fp64 run, oracle/make_census_goldens.py).  The
@@ -811,7 +854,7 @@ def main():
     #      output; a pair outside it passes only with a recorded discrete cause (same rule as test_parity_census).
     res = timed_res
     check = None
-    if not args.no_check:
+    if full and not args.no_check:
         check = {"result_judged": "last forward of the timed region (%d forward(s) in flight)" % depth["d"]}
         if single is not None:
             # the single-stream leg ran the same pairs on one stream afterwards: the schedule must not change a bit of the result
@@ -820,8 +863,8 @@ def main():
         check.update(reference_check(args.config, args.first_pair, B, N, res, timed_dec if rank == 0 else None, census_mod, w, kw, batch))
 
     # ---- extra legs: the lines a default invocation would otherwise never show ----
-    want_extra = args.extra == "on" or (args.extra == "auto" and world == 1 and args.config == workloads.DEFAULT and not args.latency
-                                        and not fp32 and not args.global_batch and not args.pairs_per_gpu and not args.first_pair)
+    want_extra = full and (args.extra == "on" or (args.extra == "auto" and world == 1 and args.config == workloads.DEFAULT and not args.latency
+                                                  and not fp32 and not args.global_batch and not args.pairs_per_gpu and not args.first_pair))
     if want_extra and world == 1:
         line["extra"] = {}
         legs = []
@@ -844,7 +887,7 @@ def main():
     # ---- CPU baseline: the reference's CPU path on this host's cores, bounded sample (rank 0, N=1 only), in a child
     #      process with a wall-clock cap so the bench always finishes; the same child runs the exact oracle on the
     #      first pairs for part 2 of the check ----
-    if world == 1 and not args.no_cpu_baseline:
+    if full and world == 1 and not args.no_cpu_baseline:
         import subprocess
         # 32 intra-op threads is the fastest setting measured on the 256-core GPU box (16: 0.42, 32: 0.59, 64: 0.33,
         # 128: 0.19 pairs/s; 256 threads did not finish 3 pairs in 240 s), so that is what the baseline gets

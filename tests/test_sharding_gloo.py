@@ -153,7 +153,7 @@ def test_eight_rank_bench_rehearsal_on_one_gpu(config, expect_per_rank):
     root = Path(__file__).resolve().parents[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), str(root / "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1", "--backend", "gloo",
-           "--config", config, "--no-cpu-baseline", "--sustain-seconds", "0", "--settle-seconds", "0"]
+           "--config", config, "--full", "--no-cpu-baseline", "--sustain-seconds", "0", "--settle-seconds", "0"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=str(root))
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -206,7 +206,7 @@ def test_one_rank_bench_through_rccl():
     root = Path(__file__).resolve().parents[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), str(root / "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--backend", "nccl",
-           "--config", "n5000_b32", "--pairs-per-gpu", "4", "--no-cpu-baseline", "--sustain-seconds", "0", "--settle-seconds", "0"]
+           "--config", "n5000_b32", "--pairs-per-gpu", "4", "--full", "--no-cpu-baseline", "--sustain-seconds", "0", "--settle-seconds", "0"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=str(root))
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -226,7 +226,7 @@ def test_bench_check_judges_a_census_pair_outside_the_contract_by_its_recorded_c
     from pathlib import Path
     root = Path(__file__).resolve().parents[1]
     cmd = [sys.executable, str(root / "bench.py"), "--config", "kitti_n5000_b16", "--global-batch", "2", "--first-pair", "60", "--steps", "4",
-           "--warmup", "1", "--no-cpu-baseline", "--sustain-seconds", "0", "--settle-seconds", "0"]
+           "--warmup", "1", "--full", "--no-cpu-baseline", "--sustain-seconds", "0", "--settle-seconds", "0"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=str(root))
     assert r.returncode == 0, r.stderr[-3000:]
     chk = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])["check"]
@@ -247,7 +247,8 @@ def test_plain_bench_invocation_with_eight_gpus_launches_itself():
     from pathlib import Path
     root = Path(__file__).resolve().parents[1]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
-    common = ["--steps", "2", "--warmup", "1", "--config", "n5000_b32", "--no-cpu-baseline", "--sustain-seconds", "0", "--settle-seconds", "0"]
+    common = ["--steps", "2", "--warmup", "1", "--config", "n5000_b32", "--full", "--no-cpu-baseline", "--sustain-seconds", "0",
+              "--settle-seconds", "0"]
     r = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "8", "--backend", "gloo"] + common,
                        capture_output=True, text=True, timeout=900, cwd=str(root), env=env)
     assert r.returncode == 0, r.stderr[-3000:]

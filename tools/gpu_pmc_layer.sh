@@ -22,7 +22,7 @@ for pass in \
   # (TCP_* / TA_* / TD_* passes hang rocprofv3 on this image until the timeout -- 5 GPU-minutes each; left out)
   i=$((i+1))
   rm -rf /tmp/pmcl_$i
-  timeout 300 rocprofv3 --pmc $pass --kernel-trace -d /tmp/pmcl_$i -o p -- python "$ROOT/bench.py" --steps 2 --warmup 1 --no-cpu-baseline --no-check --sustain-seconds 0 > "$OUT/${TAG}_pass$i.log" 2>&1
+  timeout 300 rocprofv3 --pmc $pass --kernel-trace -d /tmp/pmcl_$i -o p -- python "$ROOT/bench.py" --full --steps 2 --warmup 1 --no-cpu-baseline --no-check --sustain-seconds 0 > "$OUT/${TAG}_pass$i.log" 2>&1
   echo "## pass $i: $pass (exit $?)" >> "$SUMMARY"
   DB=$(find /tmp/pmcl_$i -name '*.db' | head -1)
   if [ -n "$DB" ]; then python "$ROOT/tools/rocpd_pmc_stats.py" "$DB" layer_ >> "$SUMMARY" 2>&1; else tail -n 5 "$OUT/${TAG}_pass$i.log" >> "$SUMMARY"; fi

@@ -31,20 +31,20 @@ if [ -z "$QUICK" ]; then
 fi
 for c in $CONFIGS kitti_n12000_b4 multiway_n20000_b1 trained_n5000_b32 trained_n1000_b1 trained_kitti_n5000_b16 trained_lomatch_n10000_b8; do      # (r04: the reference's real evaluation sizes; r05: trained-like weights)
   [ -f "$ROOT/tests/golden/bench_$c.npz" ] || continue
-  timeout 400 python bench.py --config $c > "$OUT/${TAG}_bench_$c.log" 2>&1; tail -1 "$OUT/${TAG}_bench_$c.log" > "$OUT/${TAG}_bench_line_$c.json"
+  timeout 400 python bench.py --full --config $c > "$OUT/${TAG}_bench_$c.log" 2>&1; tail -1 "$OUT/${TAG}_bench_$c.log" > "$OUT/${TAG}_bench_line_$c.json"
 done
 # r05: the same headline configuration with the per-launch key split (the fastest form: a pair's bits then depend on its batch), and the
 # number an unchanged caller sees: one pair per call, result read back (bench.py --latency)
-timeout 300 python bench.py --config n5000_b32 --att-leaves per_launch --no-cpu-baseline 2>/dev/null | tail -1 > "$OUT/${TAG}_bench_line_n5000_b32_per_launch_leaves.json"
+timeout 300 python bench.py --full --config n5000_b32 --att-leaves per_launch --no-cpu-baseline 2>/dev/null | tail -1 > "$OUT/${TAG}_bench_line_n5000_b32_per_launch_leaves.json"
 for s in n5000_b32:1 n1000_b1:1 trained_n1000_b1:1 lomatch_n10000_b8:1; do
   c=${s%%:*}
-  timeout 300 python bench.py --config $c --global-batch 1 --latency --no-cpu-baseline --steps 200 --warmup 20 --sustain-seconds 1 2>/dev/null | tail -1 > "$OUT/${TAG}_bench_line_${c}_latency_1pair.json"
+  timeout 300 python bench.py --full --config $c --global-batch 1 --latency --no-cpu-baseline --steps 200 --warmup 20 --sustain-seconds 1 2>/dev/null | tail -1 > "$OUT/${TAG}_bench_line_${c}_latency_1pair.json"
 done
 SHARES="n5000_b32:16 n5000_b32:8 n5000_b32:4 kitti_n5000_b16:8 kitti_n5000_b16:4 kitti_n5000_b16:2 lomatch_n10000_b8:4 lomatch_n10000_b8:2 lomatch_n10000_b8:1"
 if [ -z "$QUICK" ]; then
   for s in $SHARES; do
     c=${s%%:*}; B=${s##*:}
-    timeout 300 python bench.py --config $c --global-batch $B --no-cpu-baseline 2>/dev/null | tail -1 > "$OUT/${TAG}_bench_line_${c}_${B}pairs.json"
+    timeout 300 python bench.py --full --config $c --global-batch $B --no-cpu-baseline 2>/dev/null | tail -1 > "$OUT/${TAG}_bench_line_${c}_${B}pairs.json"
   done
   timeout 1200 python tools/parity_census.py --batches 0,1,2,4,8,16,32 > "$OUT/${TAG}_parity_census.txt" 2>&1
   timeout 600 python tools/parity_census.py --batches 0 --att-leaves per_launch > "$OUT/${TAG}_parity_census_per_launch_leaves.txt" 2>&1
@@ -57,7 +57,7 @@ cd /tmp
 for s in n5000_b32:32 n1000_b1:1 kitti_n5000_b16:16 lomatch_n10000_b8:8 n5000_b32:4 kitti_n5000_b16:2 lomatch_n10000_b8:1; do
   c=${s%%:*}; B=${s##*:}
   rm -rf /tmp/prof_$c
-  timeout 300 rocprofv3 --kernel-trace --stats -d /tmp/prof_$c -o k -- python "$ROOT/bench.py" --config $c --global-batch $B --in-flight 1 --steps 6 --warmup 1 --settle-seconds 0 --no-cpu-baseline --no-check --sustain-seconds 0 --extra off > "$OUT/${TAG}_rocprof_${c}_$B.log" 2>&1
+  timeout 300 rocprofv3 --kernel-trace --stats -d /tmp/prof_$c -o k -- python "$ROOT/bench.py" --full --config $c --global-batch $B --in-flight 1 --steps 6 --warmup 1 --settle-seconds 0 --no-cpu-baseline --no-check --sustain-seconds 0 --extra off > "$OUT/${TAG}_rocprof_${c}_$B.log" 2>&1
   DB=$(find /tmp/prof_$c -name '*.db' | head -1)
   [ -n "$DB" ] && python "$ROOT/tools/rocpd_kernel_stats.py" "$DB" > "$OUT/${TAG}_kernel_stats_${c}_${B}pairs.txt" 2>&1
   rm -rf /tmp/prof_$c

@@ -28,7 +28,7 @@ export TMPDIR=/tmp
 cd "$ROOT"
 line() { # file, bench args...
   local f=$1; shift
-  timeout 400 python bench.py "$@" > "$OUT/$f.log" 2>&1
+  timeout 400 python bench.py --full "$@" > "$OUT/$f.log" 2>&1
   tail -1 "$OUT/$f.log" > "$OUT/$f.json"
 }
 summ() {

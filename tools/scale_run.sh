@@ -16,10 +16,10 @@ export HSA_ENABLE_IPC_MODE_LEGACY=0
 for cfg in n5000_b32 kitti_n5000_b16 lomatch_n10000_b8; do
   for N in 1 2 4 8; do
     if [ "$N" = 1 ]; then
-      python bench.py --gpus 1 --steps $STEPS --warmup $WARMUP --config $cfg --no-cpu-baseline 2> "$OUT/scale_${cfg}_n$N.err" | tail -1 > "$OUT/scale_${cfg}_n$N.json"
+      python bench.py --full --gpus 1 --steps $STEPS --warmup $WARMUP --config $cfg --no-cpu-baseline 2> "$OUT/scale_${cfg}_n$N.err" | tail -1 > "$OUT/scale_${cfg}_n$N.json"
     else
       python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port $((29500 + N)) \
-        bench.py --gpus $N --steps $STEPS --warmup $WARMUP --config $cfg --backend $BACKEND --no-cpu-baseline 2> "$OUT/scale_${cfg}_n$N.err" | tail -1 > "$OUT/scale_${cfg}_n$N.json"
+        bench.py --full --gpus $N --steps $STEPS --warmup $WARMUP --config $cfg --backend $BACKEND --no-cpu-baseline 2> "$OUT/scale_${cfg}_n$N.err" | tail -1 > "$OUT/scale_${cfg}_n$N.json"
     fi
     python - "$OUT/scale_${cfg}_n$N.json" <<'PY'
 import json, sys
