@@ -12,7 +12,7 @@
  *     pdsc_forward_validation; the weight packers pdsc_wpack_floats / _offset, pdsc_wsplit_bytes / _offset / _build; the workspace
  *     queries pdsc_workspace_bytes / _offset; pdsc_encoder_range_probe; pdsc_version / pdsc_last_error; and, for the callers either
  *     side of the path (SURVEY.md section 8 f-2 .. f-4), pdsc_match_* / pdsc_select_correspondences / pdsc_build_corr_pos,
- *     pdsc_sm_baseline*, pdsc_cal_confidence, pdsc_eval_stats.
+ *     pdsc_sm_baseline*, pdsc_cal_confidence, pdsc_eval_stats, pdsc_icp_*.
  *   STAGE LEVEL -- one entry point per reference stage (sections a-1 .. a-11 below), the plan / size queries that go with them,
  *     pdsc_selftest_* and the diagnostic hooks.  The forward does not go through them (it calls the same launchers directly); they
  *     exist so that every stage can be parity-checked on its own (tests/test_gpu_parity.py), for the tools, and for a maintainer
@@ -598,6 +598,27 @@ int pdsc_cal_confidence(const float* M, long long ld, const float* leading_eig, 
  * trans, gt_trans [bs][16]; pred_labels, gt_labels [bs][N]; stats [bs][9]. */
 int pdsc_eval_stats(const float* trans, const float* gt_trans, const float* pred_labels, const float* gt_labels,
                     float re_thre, float te_thre, float* stats, int bs, int N, void* stream);
+
+/* ---- ICP post-step of the evaluation (the open3d hand-off of SURVEY.md section 8 f-4) ----------
+ * replaces evaluation/benchmark_utils.py:40-56 icp_refine (called by evaluation/test_3DMatch.py:79-80, test_KITTI.py:79-80,
+ * multiway/test_multi.py:53-54): open3d 0.9 registration_icp with TransformationEstimationPointToPoint, per pair:
+ *   fp64 throughout; T = init; P = src transformed by init (skipped when init passes Eigen's isIdentity()); evaluate(P);
+ *   up to max_iteration times { U = umeyama(P[corr], tgt[corr]) (identity for an empty set); T = U T; P = U P; evaluate(P);
+ *   stop when |d fitness| < relative_fitness and |d rmse| < relative_rmse };
+ *   evaluate: each source point's nearest target with fp64 d2 < float(max_distance^2) (FLANN's radius test; equal distances:
+ *   the lowest target index), fitness = |corr| / Ns_b, inlier_rmse = sqrt(sum d2 / |corr|) (both 0 for an empty set).
+ * src [bs][Ns][3], tgt [bs][Nt][3] (fp32, widened exactly), init_trans [bs][16]; Ns_per_pair / Nt_per_pair [bs] int32
+ * (DEVICE; NULL = every pair has Ns / Nt points; rows beyond a pair's count are padding and never read).
+ * Outputs [bs]: out_trans_f32 [bs][16], out_trans_f64 [bs][16] (optional), fitness, inlier_rmse (double), num_corr (final
+ * |corr|), iterations (loop iterations run).  max_distance <= 0 returns init with zeros (as open3d does); a non-finite init or
+ * point returns a NaN pose, NaN fitness / rmse, iterations 0.  The convergence test runs on the device: pairs stop independently.
+ * workspace: pdsc_icp_workspace_bytes(bs, Ns, Nt).  A pair's result does not depend on the batch it runs in.
+ * Defaults of the reference (open3d 0.9 ICPConvergenceCriteria): max_distance 0.10, relative_* 1e-6, max_iteration 30. */
+size_t pdsc_icp_workspace_bytes(int bs, int Ns, int Nt);
+int pdsc_icp_refine(const float* src, const float* tgt, const float* init_trans, const int* Ns_per_pair, const int* Nt_per_pair,
+                    double max_distance, double relative_fitness, double relative_rmse, int max_iteration, float* out_trans_f32,
+                    double* out_trans_f64, double* fitness, double* inlier_rmse, int* num_corr, int* iterations, void* workspace,
+                    size_t workspace_bytes, int bs, int Ns, int Nt, void* stream);
 
 /* ---- range probe for layer_gemm = PDSC_LAYER_GEMM_H3 ----------------------------------------------------------------
  * The H3 arithmetic carries every operand of the fc_message / PointCN GEMMs as fp16 hi + lo, so every activation of the

@@ -6,9 +6,11 @@ Only what the path needs lives here:
   _lib.py      ctypes binding of include/pointdsc_hip.h (fails loudly when the library is missing)
   model.py     ``PointDSC`` nn.Module: reference constructor, state_dict layout and forward contract
   ops.py       stage-level tensor wrappers (``rigid_transform_3d``, ``knn`` ...) over the C-ABI
+  icp.py       the evaluation's optional ICP post-step (``icp_refine``, ``registration_icp``) on the device
   sharding.py  one-process-per-GPU sharding of pair batches + the single RCCL pose gather
   synthetic.py seeded synthetic correspondence sets / weights (tests + bench)
 """
+from .icp import icp_refine, registration_icp  # noqa: F401
 from .model import PointDSC  # noqa: F401
 
-__all__ = ["PointDSC"]
+__all__ = ["PointDSC", "icp_refine", "registration_icp"]

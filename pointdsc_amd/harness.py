@@ -7,7 +7,8 @@ Replicates, without open3d / easydict (absent here):
     ``eval_3DMatch`` (:141-176: recall, mean RE / TE over the successful pairs, mean P / R / F1, mean times);
   * ``demo_registration.py:37-44,101-117``  cloud -> voxel down-sampling -> descriptors -> nearest-neighbour matching
     -> ``corr_pos`` -> ``model(data)``.
-The arithmetic on the path runs in libpointdsc_hip.so (correspondence construction f-2, forward a-*, stats row f-4);
+The arithmetic on the path runs in libpointdsc_hip.so (correspondence construction f-2, forward a-*, stats row f-4, the
+optional ICP post-step f-5);
 this module is host plumbing: PLY reading (binary little-endian float xyz), open3d-style voxel
 down-sampling in numpy, the pair loop, timers (``utils/timer.py`` semantics: wall clock, here with a device
 synchronisation so that model time is the GPU's).
@@ -29,6 +30,7 @@ import torch
 
 from . import ops
 from .correspondences import build_correspondences
+from .icp import icp_refine
 
 STATS_NAMES = ("success", "RE_deg", "TE_cm", "input_inliers", "input_inlier_ratio", "output_true_positives",
                "precision", "recall", "f1", "model_time_s", "data_time_s", "scene_ind")
@@ -135,12 +137,16 @@ def gt_labels_from_trans(src_keypts: torch.Tensor, tgt_keypts: torch.Tensor, gt_
 
 
 def eval_scene(model, pairs: Iterable[Dict[str, np.ndarray]], scene_ind: int = 0, re_thre: float = 15.0, te_thre: float = 30.0,
-               inlier_threshold: float = 0.10, use_mutual: bool = False, device: str = "cuda:0", batch_size: int = 1) -> np.ndarray:
+               inlier_threshold: float = 0.10, use_mutual: bool = False, device: str = "cuda:0", batch_size: int = 1,
+               use_icp: bool = False, icp_distance: float = 0.10) -> np.ndarray:
     """`pairs`: dicts with src_pts [ns,3], tgt_pts [nt,3], src_desc [ns,D], tgt_desc [nt,D], gt_trans [4,4] (numpy).
     Returns the [num_pair, 12] stats array of the reference's eval_3DMatch_scene.
     batch_size > 1 (r03): the correspondence sets of `batch_size` consecutive pairs -- every pair has its own N, as in the
     reference's evaluation (test_3DMatch.py:126 `num_node='all'`) -- go through ONE ragged call of the model (lists of
-    per-pair tensors); model / data time are then the batch's time divided by its pairs."""
+    per-pair tensors); model / data time are then the batch's time divided by its pairs.
+    use_icp (test_3DMatch.py:79-80): the predicted poses are refined by point-to-point ICP of the correspondence endpoints
+    (benchmark_utils.icp_refine, max_correspondence_distance = icp_distance) -- the group's pairs in one ragged device call,
+    inside the model time as in the reference; the stats rows then use the refined poses."""
     rows: List[np.ndarray] = []
     dev = torch.device(device)
     g = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
@@ -157,6 +163,9 @@ def eval_scene(model, pairs: Iterable[Dict[str, np.ndarray]], scene_ind: int = 0
             res = model({"corr_pos": [x["corr"]["corr_pos"][0] for x in group], "src_keypts": [x["corr"]["src_keypts"][0] for x in group],
                          "tgt_keypts": [x["corr"]["tgt_keypts"][0] for x in group], "testing": True})
             trans, labels = res["final_trans"], res["final_labels"]
+        if use_icp:                                                                                        # test_3DMatch.py:79-80
+            trans = icp_refine([x["corr"]["src_keypts"][0] for x in group], [x["corr"]["tgt_keypts"][0] for x in group], trans,
+                               icp_distance)
         torch.cuda.synchronize(dev)
         model_time = (time.perf_counter() - t0) / len(group)
         for i, x in enumerate(group):

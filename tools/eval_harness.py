@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """The reference's evaluation loop / demo around pointdsc_amd.PointDSC (pointdsc_amd/harness.py).
 
-    python tools/eval_harness.py [--pcd1 a.ply --pcd2 b.ply] [--num-pairs 8] [--snapshot model_best.pkl] [--kitti]
+    python tools/eval_harness.py [--pcd1 a.ply --pcd2 b.ply] [--num-pairs 8] [--snapshot model_best.pkl] [--kitti] [--use-icp]
 
 Without --pcd1 the down-sampled demo cloud of tests/golden/demo_clouds_vox005.npz (reference demo_data/cloud_bin_0.ply at
 0.05 m) is used.  Every pair = the cloud against a seeded second view of it (partial overlap, noise, random rigid motion),
@@ -31,6 +31,8 @@ def main():
     ap.add_argument("--snapshot", default=None, help="released model_best.pkl (load_state_dict(strict=False)); default: seeded weights")
     ap.add_argument("--mutual", action="store_true", help="mutual nearest neighbours only (datasets/ThreeDMatch.py:286-288)")
     ap.add_argument("--batch-size", type=int, default=1, help="pairs per (ragged) model call; the reference evaluates one pair per call")
+    ap.add_argument("--use-icp", action="store_true", help="refine every pose by point-to-point ICP on the device (test_3DMatch.py --use_icp)")
+    ap.add_argument("--icp-distance", type=float, default=0.10, help="max_correspondence_distance of the ICP post-step")
     ap.add_argument("--json", action="store_true")
     a = ap.parse_args()
     if a.pcd1:
@@ -45,12 +47,13 @@ def main():
         model.load_state_dict(workloads.state_dict("n5000_b32", model.state_dict()))
     model = model.eval().cuda()
     stats = harness.eval_scene(model, harness.demo_pairs(cloud, a.num_pairs, corrupt=a.outlier_share), scene_ind=0,
-                               inlier_threshold=kw["inlier_threshold"], use_mutual=a.mutual, batch_size=a.batch_size)
+                               inlier_threshold=kw["inlier_threshold"], use_mutual=a.mutual, batch_size=a.batch_size,
+                               use_icp=a.use_icp, icp_distance=a.icp_distance)
     summ = harness.summarize(stats)
     if a.json:
         print(json.dumps({"stats_columns": harness.STATS_NAMES, "stats": stats.tolist(), "summary": summ}))
         return
-    print(f"{len(cloud)} points after {a.voxel} m voxel down-sampling; {a.num_pairs} pairs")
+    print(f"{len(cloud)} points after {a.voxel} m voxel down-sampling; {a.num_pairs} pairs" + (" (ICP post-step)" if a.use_icp else ""))
     print(" ".join(f"{n[:10]:>10s}" for n in harness.STATS_NAMES))
     for row in stats:
         print(" ".join(f"{v:10.4f}" for v in row))
