@@ -72,7 +72,27 @@ typedef struct pdsc_config {
     int compat_format;       /* enum pdsc_compat_format: how the forward stores the N x N spatial-consistency matrix  */
     int layer_gemm;          /* enum pdsc_layer_gemm: arithmetic of the fc_message / PointCN GEMMs in the fused layer kernel */
     int att_leaves;          /* enum pdsc_att_leaves: summation tree of the attention's key dimension (split-precision modes) */
+    int value_fold;          /* enum pdsc_value_fold: fc_message's first conv folded into the value projection                */
 } pdsc_config;
+
+/* fc_message's first conv (+ its BatchNorm, W1f / b1f) folded into the value projection (models/PointDSC.py:12-20,36-44).  Each
+ * softmax row sums to 1, so  W1f (sum_j p_ij (Wv f_j + bv)) + b1f = sum_j p_ij (W1f Wv) f_j + (W1f bv + b1f)  exactly in real
+ * arithmetic: the head projects V' = (W1f Wv) f with C/2 = 64 channels, the attention contracts P V' over 64 channels instead
+ * of 128 (half the P V MFMAs, half the V^T planes and partials), and the layer kernel adds b' = W1f bv + b1f to the merged
+ * 64-channel message and goes straight to ReLU -> fc2 (no fc1 GEMM).  Same three-MFMA split arithmetic per product; only the
+ * association order of an fp32-class computation changes.  W1f Wv is formed in fp64 from the packed fp32 matrices and rounded
+ * once to fp32 (pdsc_wsplit_build).
+ *   OFF (0): the 128-channel value path, layouts and bits of library version 8.
+ *   ON  (1): valid with a split-precision attention and layer_gemm = PDSC_LAYER_GEMM_H3 only (config check).  pdsc_forward_*
+ *            folds on the point-fragment hand-offs (leaf form, and key splits of 2..8) of calls with N <= PDSC_VALUE_FOLD_MAX_N
+ *            (N = the longest pair of a ragged batch); a per-launch plan whose key split is 1 or more than 8, and larger N, keep
+ *            the 128-channel path.                                                             [default of the Python module]
+ * The size bound: at the multiway evaluation size (N = 20000) the reference's recorded outputs pin a golden pair whose winning
+ * seed has its k-th and (k+1)-th neighbour distances 1.2e-7 apart, resolved by the last bit of the fp32 feature Gram; the
+ * fold's association order resolves it to the other side (both inside the contract).  The calls beyond the bound keep the
+ * 128-channel results that record was made with. */
+enum pdsc_value_fold { PDSC_VALUE_FOLD_OFF = 0, PDSC_VALUE_FOLD_ON = 1 };
+#define PDSC_VALUE_FOLD_MAX_N 16384
 
 /* How the N keys of a query are summed (models/PointDSC.py:41-42: one softmax-weighted sum per query) when the key range is
  * cut so that one pair can fill the chip.  A LEAF is a run of 32-key tiles accumulated from a fresh online-softmax state;
@@ -288,6 +308,15 @@ int pdsc_layer_fused_x3(const float* msg, const float* part_o, const float* part
 #define PDSC_WS_FRAG_HEAD 101
 #define PDSC_WS_FRAG_TAIL_H3 102   /* the same streams built with gemm_format = PDSC_LAYER_GEMM_H3 */
 #define PDSC_WS_FRAG_HEAD_H3 103
+/* value_fold = 1 only (pdsc_wsplit_offset returns -1 otherwise), per layer after the streams above:
+ *   PDSC_WS_FOLD_TAIL_H3: H3 tail stream of the folded layer (fc2, fc3: 6 chunks, their biases, then b' = W1f bv + b1f, 64 fp32)
+ *   PDSC_WS_FOLD_HEAD_H3: H3 head stream (pcn, q, k, v' = W1f Wv: 28 chunks, biases; the v' rows carry no bias)
+ *   PDSC_WS_FOLD_W      : W1f Wv [C/2][C] fp32, then b' [C/2] fp32 (what the streams were built from) */
+#define PDSC_WS_FOLD_TAIL_H3 104
+#define PDSC_WS_FOLD_HEAD_H3 105
+#define PDSC_WS_FOLD_W 106
+size_t pdsc_wfrag_fold_tail_bytes(void);
+size_t pdsc_wfrag_fold_head_bytes(void);
 int pdsc_layer_prefers_block(int bs, int N);   /* 1: with layer_gemm = F32, pdsc_forward_* takes the workgroup-per-tile kernel for this size */
 int pdsc_layer_h3_uses_coop(int bs, int N);    /* 1: with layer_gemm = H3, a launch over bs x N points takes layer_h3_coop_kernel (four
                                                 * wavefronts per 32-point tile: at most 2560 tiles), 0: layer_h3_kernel */

@@ -25,7 +25,7 @@ class PdscConfig(C.Structure):
         ("num_iterations", C.c_int), ("k", C.c_int), ("refine_iters", C.c_int),
         ("inlier_threshold", C.c_float), ("nms_radius", C.c_float), ("refine_threshold", C.c_float),
         ("attention_precision", C.c_int), ("compat_format", C.c_int), ("layer_gemm", C.c_int),
-        ("att_leaves", C.c_int),
+        ("att_leaves", C.c_int), ("value_fold", C.c_int),
     ]
 
 
@@ -67,6 +67,8 @@ SIGNATURES = {
     "pdsc_layer_h3_uses_coop": (_i, [_i, _i]),
     "pdsc_wfrag_tail_bytes": (_sz, []),
     "pdsc_wfrag_head_bytes": (_sz, []),
+    "pdsc_wfrag_fold_tail_bytes": (_sz, []),
+    "pdsc_wfrag_fold_head_bytes": (_sz, []),
     "pdsc_wfrag_build_tail": (_i, [_vp] * 8),
     "pdsc_wfrag_build_head": (_i, [_vp] * 6),
     "pdsc_wfrag_build_tail_fmt": (_i, [_vp] * 7 + [_i, _vp]),

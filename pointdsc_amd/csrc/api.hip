@@ -9,6 +9,7 @@
 #include "pdsc_common.h"
 #include "ragged.h"
 #include "attention_common.h"
+#include "layer_args.h"
 
 namespace pdsc {
 
@@ -146,6 +147,12 @@ static bool config_ok(const pdsc_config* c) {
     if (c->compat_format != PDSC_COMPAT_U16 && c->compat_format != PDSC_COMPAT_F32) { set_error("compat_format=%d", c->compat_format); return false; }
     if (c->layer_gemm != PDSC_LAYER_GEMM_F32 && c->layer_gemm != PDSC_LAYER_GEMM_H3) { set_error("layer_gemm=%d", c->layer_gemm); return false; }
     if (c->att_leaves < PDSC_LEAVES_PER_LAUNCH || c->att_leaves > PDSC_ATT_MAX_LEAVES) { set_error("att_leaves=%d (enum pdsc_att_leaves, or 2..%d leaves)", c->att_leaves, PDSC_ATT_MAX_LEAVES); return false; }
+    if (c->value_fold != PDSC_VALUE_FOLD_OFF && c->value_fold != PDSC_VALUE_FOLD_ON) { set_error("value_fold=%d (enum pdsc_value_fold)", c->value_fold); return false; }
+    if (c->value_fold == PDSC_VALUE_FOLD_ON && (c->attention_precision != PDSC_ATT_FP16X3 || c->layer_gemm != PDSC_LAYER_GEMM_H3)) {
+        set_error("value_fold=1 needs attention_precision=PDSC_ATT_FP16X3 and layer_gemm=PDSC_LAYER_GEMM_H3 (got %d, %d)",
+                  c->attention_precision, c->layer_gemm);
+        return false;
+    }
     return true;
 }
 
@@ -495,15 +502,22 @@ static int run_forward(int mode, const pdsc_config* cfg, const float* wpack, con
                          "pdsc_forward_testing_ragged: the shortest pair (%d correspondences) has fewer 32-key tiles than the key split "
                          "planned for bs=%d, N=%d (%d): batch pairs of more similar size", n_min, bs, N, pdsc_attention_split_default_split(bs, N));
         const bool pf = leaves || (pf_ok && fuse_merge);
+        // value fold (enum pdsc_value_fold): fc1 inside the value projection -- 64-channel V', partials and P V' on the point-fragment
+        // hand-offs (leaves and key splits of 2..8) up to N = PDSC_VALUE_FOLD_MAX_N (a function of N alone, so canonical leaves stay
+        // batch invariant); the row-order hand-offs and larger N keep the 128-channel path
+        const bool fold = cfg->value_fold == PDSC_VALUE_FOLD_ON && pf && !x3_gemm && N <= PDSC_VALUE_FOLD_MAX_N;
+        const int vw = fold ? C / 2 : C;
+        const int pf_tail = fold ? PDSC_WS_FOLD_TAIL_H3 : ws_tail, pf_head = fold ? PDSC_WS_FOLD_HEAD_H3 : ws_head;
+        const float* part_ml_pf = pf && !leaves ? part_o + (size_t)bs * ns * Npad * vw : part_ml;
         const float* lf_o = (const float*)att_scratch;
-        const float* lf_ml = lf_o + (size_t)bs * lf_leaves * Npad * C;
+        const float* lf_ml = lf_o + (size_t)bs * lf_leaves * Npad * vw;
         if (x3_gemm)
             PDSC_TRY(pdsc_layer_fused_x3(nullptr, nullptr, nullptr, 0, 0, nullptr, featA, nullptr, featB, nullptr, q_split, kv_tiles,
                                          nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, WS(PDSC_W_PCN_W, 0), W(PDSC_W_PCN_B, 0),
                                          WS(PDSC_W_QKV_W, 0), W(PDSC_W_QKV_B, 0), bs, N, stream));
         else if (pf)
-            PDSC_TRY(pdsc_layer_fused_frag_io(nullptr, nullptr, nullptr, 0, 0, nullptr, featA, nullptr, featB, q_split, kv_tiles,
-                                              nullptr, WS(ws_head, 0), gemm, PDSC_IO_FEATB_PF, bs, N, stream));
+            PDSC_TRY(layer_fused_frag_io(nullptr, nullptr, nullptr, 0, 0, nullptr, featA, nullptr, featB, q_split, kv_tiles,
+                                         nullptr, WS(pf_head, 0), gemm, PDSC_IO_FEATB_PF, bs, N, hst, fold));
         else if (frag)
             PDSC_TRY(pdsc_layer_fused_frag_fmt(nullptr, nullptr, nullptr, 0, 0, nullptr, featA, nullptr, featB, nullptr, q_split, kv_tiles,
                                                nullptr, WS(ws_head, 0), gemm, bs, N, stream));
@@ -515,18 +529,18 @@ static int run_forward(int mode, const pdsc_config* cfg, const float* wpack, con
         for (int i = 0; i < cfg->num_layers; ++i) {
             if (leaves)
                 PDSC_TRY(launch_attention_leaves(q_split, kv_tiles, compat, compat16 ? PDSC_COMPAT_U16 : PDSC_COMPAT_F32, ld, att_scratch,
-                                                 att_bytes, bs, N, cfg->att_leaves, nvalid, n_min, hst));
+                                                 att_bytes, bs, N, cfg->att_leaves, nvalid, n_min, hst, vw));
             else if (pf)
                 PDSC_TRY(launch_attention_split_ex(q_split, kv_tiles, compat, compat16 ? PDSC_COMPAT_U16 : PDSC_COMPAT_F32, ld, nullptr,
-                                                   att_scratch, att_bytes, bs, N, ns, PDSC_PARTIALS_PF, nvalid, hst));
+                                                   att_scratch, att_bytes, bs, N, ns, PDSC_PARTIALS_PF, nvalid, hst, vw));
             else
                 PDSC_TRY(attention_split(fuse_merge ? nullptr : msg, ns));
             const bool last = i + 1 == cfg->num_layers;
             if (pf)
-                PDSC_TRY(pdsc_layer_fused_frag_io(nullptr, leaves ? lf_o : part_o, leaves ? lf_ml : part_ml, leaves ? lf_leaves : ns, Npad, cur, nullptr, last ? featA : nullptr,
-                                                  last ? nullptr : nxt, last ? nullptr : q_split, last ? nullptr : kv_tiles,
-                                                  WS(ws_tail, i), last ? nullptr : WS(ws_head, i + 1), gemm,
-                                                  PDSC_IO_PARTIALS_PF | PDSC_IO_RES_PF | (last ? 0 : PDSC_IO_FEATB_PF), bs, N, stream));
+                PDSC_TRY(layer_fused_frag_io(nullptr, leaves ? lf_o : part_o, leaves ? lf_ml : part_ml_pf, leaves ? lf_leaves : ns, Npad, cur, nullptr,
+                                             last ? featA : nullptr, last ? nullptr : nxt, last ? nullptr : q_split, last ? nullptr : kv_tiles,
+                                             WS(pf_tail, i), last ? nullptr : WS(pf_head, i + 1), gemm,
+                                             PDSC_IO_PARTIALS_PF | PDSC_IO_RES_PF | (last ? 0 : PDSC_IO_FEATB_PF), bs, N, hst, fold));
             else if (x3_gemm)
                 PDSC_TRY(pdsc_layer_fused_x3(fuse_merge ? nullptr : msg, part_o, part_ml, ns, Npad, cur, nullptr, last ? featA : nullptr,
                                              last ? nullptr : nxt, nullptr, last ? nullptr : q_split, last ? nullptr : kv_tiles,

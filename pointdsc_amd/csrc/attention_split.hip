@@ -62,7 +62,6 @@ constexpr float ATT_RESCALE_THR = 8.0f;   // running max is only moved when a lo
 // 2^-32 of the largest term.  The bias is a common factor of o and l (and of every leaf's partials) and cancels in o / l.
 constexpr float ATT_P_BIAS = 7.0f;
 constexpr int SPL_K_BYTES = 2 * SPL_K_PLANE;    // Kh | Kl   16 KiB
-constexpr int SPL_V_BYTES = 2 * SPL_V_PLANE;    // Vh | Vl   16 KiB
 
 // Software pipeline (per wave, per key tile t):  phase A = QK^T of tile t+1 on the matrix pipe WHILE the VALU turns
 // tile t's logits into P (exp2, hi/lo split);  phase B = P V of tile t WHILE the VALU forms tile t+1's logits.  Both
@@ -107,17 +106,23 @@ constexpr int SPL_V_BYTES = 2 * SPL_V_PLANE;    // Vh | Vl   16 KiB
 #endif
 #define PDSC_MFMA_IF(bit, a_, b_, c_) (((PDSC_ATT_ABLATE) & (bit)) ? (c_) : PDSC_MFMA_X3(a_, b_, c_, 0, 0, 0))
 
-template <int NW, int CM = 0, bool TRACE = false, bool PS = false, bool PEEL = true, bool MG = false>
+// VW: channels of V (split_layout.h): 128, or 64 for the folded value projection V' = W1f Wv (pdsc_config.value_fold) -- half the
+// V^T planes (24 KiB tile images), half the P V MFMAs (12 instead of 24 per wave and tile), 32 accumulator registers instead of 64,
+// partials of 64 channels.  The 64-wide form is instantiated for the point-fragment partials (key splits and leaves) only.
+template <int NW, int CM = 0, bool TRACE = false, bool PS = false, bool PEEL = true, bool MG = false, int VW = 128>
 __global__ __launch_bounds__(NW * 64, 2) void sc_attention_split_kernel(AttSplitArgs a) {
     constexpr bool C16 = CM == 1, CREG = CM == 2;
+    static_assert(VW == 128 || VW == 64, "value width 128 or 64");
+    constexpr int NC = VW / 32;                                     // accumulator blocks of 32 channels
+    constexpr int VB = 2 * spl_v_plane<VW>(), VPL = spl_v_plane<VW>();    // V^T hi | lo bytes per stage / per plane
     static_assert(!PS || (!CREG && !TRACE), "the persistent form exists for the LDS-staged compat formats, untraced");
     static_assert(!MG || (!PS && !TRACE && !CREG && PEEL), "the merged form: one-item, untraced, LDS-staged compat, peeled last tile");
     long long tr[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     long long tlast = TRACE ? (long long)__builtin_readcyclecounter() : 0;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     unsigned char* const Ks = lds;                                  // 2 x 16 KiB
-    unsigned char* const Vs = lds + 2 * SPL_K_BYTES;                // 2 x 16 KiB
-    unsigned char* const Cs = Vs + 2 * SPL_V_BYTES;                 // 2 x NW*4 KiB
+    unsigned char* const Vs = lds + 2 * SPL_K_BYTES;                // 2 x 16 KiB (VW = 64: 2 x 8 KiB)
+    unsigned char* const Cs = Vs + 2 * VB;                          // 2 x NW*4 KiB
     constexpr int CROW = C16 ? 64 : 128;         // bytes of compat per query row per tile
     constexpr int CSTAGE = CREG ? 0 : NW * 32 * CROW;
     constexpr int NCS = CREG ? 0 : (C16 ? 2 : 4);     // compat DMA pieces (1 KiB) per wave per tile
@@ -220,7 +225,7 @@ __global__ __launch_bounds__(NW * 64, 2) void sc_attention_split_kernel(AttSplit
     //   slots 0-3: compat_{kt+2} pieces (HBM latency: first), slots 4-8: K_{kt+2} / V_{kt+1} pieces i = wave + NW*u.
     // Straight-line: tiles past the end of the split are fetched like any other (<= 2 wasted tiles per workgroup; past
     // the end of the buffer the descriptor's bounds check returns zeros); they land in stages nobody reads any more.
-    constexpr int KPIECES = SPL_K_BYTES / 1024, PIECES = SPL_TILE_BYTES / 1024, KV_SLOTS = (PIECES + NW - 1) / NW;
+    constexpr int KPIECES = SPL_K_BYTES / 1024, PIECES = spl_tile_bytes<VW>() / 1024, KV_SLOTS = (PIECES + NW - 1) / NW;
     auto dma_slot = [&](int kt, int st, int slot) {
         if (slot < NCS) {
             // the fp32 compat slices are read once per launch: streamed with the non-temporal policy (aux = 2) they leave
@@ -231,7 +236,7 @@ __global__ __launch_bounds__(NW * 64, 2) void sc_attention_split_kernel(AttSplit
         } else {
             const int i = min(wave + NW * (slot - NCS), PIECES - 1);    // surplus slots repeat the last piece
             const bool isk = i < KPIECES;                                // wave-uniform
-            unsigned char* dst = isk ? Ks + st * SPL_K_BYTES + i * 1024 : Vs + (st ^ 1) * SPL_V_BYTES + (i - KPIECES) * 1024;
+            unsigned char* dst = isk ? Ks + st * SPL_K_BYTES + i * 1024 : Vs + (st ^ 1) * VB + (i - KPIECES) * 1024;
             const int src = (isk ? (PS ? kt + dK : kt + 2) : (PS ? kt + dV : kt + 1)) * SPL_TILE_STRIDE + i * 1024;
             __builtin_amdgcn_raw_ptr_buffer_load_lds(PS ? (isk ? kv_rsrc : kv_v) : kv_rsrc, (lptr_t)dst, 16, lane16, src, 0, 0);
         }
@@ -239,7 +244,7 @@ __global__ __launch_bounds__(NW * 64, 2) void sc_attention_split_kernel(AttSplit
     constexpr int DMA_SLOTS = NCS + KV_SLOTS;    // fp32 compat: 9 (NW = 8) or 14 (NW = 4): 8 go after the QK steps, the rest after PV steps
     static_assert(DMA_SLOTS <= 16, "16 places per iteration");
     auto dma_k = [&](int kt) { issue_linear<NW, SPL_K_BYTES>(kv_rsrc, kt * SPL_TILE_STRIDE + SPL_KH, Ks + ((kt - kt0) & 1) * SPL_K_BYTES, wave, lane16); };
-    auto dma_v = [&](int kt) { issue_linear<NW, SPL_V_BYTES>(kv_rsrc, kt * SPL_TILE_STRIDE + SPL_VH, Vs + ((kt - kt0) & 1) * SPL_V_BYTES, wave, lane16); };
+    auto dma_v = [&](int kt) { issue_linear<NW, VB>(kv_rsrc, kt * SPL_TILE_STRIDE + SPL_VH, Vs + ((kt - kt0) & 1) * VB, wave, lane16); };
     auto dma_c = [&](int kt) {
 #pragma unroll
         for (int u = 0; u < NCS; ++u)
@@ -303,9 +308,9 @@ __global__ __launch_bounds__(NW * 64, 2) void sc_attention_split_kernel(AttSplit
     };
     if constexpr (PS) look_ahead();
 
-    f32x16 o[4];
+    f32x16 o[NC];
 #pragma unroll
-    for (int c = 0; c < 4; ++c)
+    for (int c = 0; c < NC; ++c)
 #pragma unroll
         for (int r = 0; r < 16; ++r) o[c][r] = 0.f;
     float m_run = 0.f, l_run = 0.f;              // m_run: reference exponent of this query's p values (set by the first tile)
@@ -315,9 +320,9 @@ __global__ __launch_bounds__(NW * 64, 2) void sc_attention_split_kernel(AttSplit
     bool pend = false;
     auto store_pending = [&]() {
         // point-fragment order (see the one-item epilogue below): the accumulator registers are the layer kernel's operands
-        float* base = a.part_o + slot_prev * PDSC_CHANNELS + lane * 4;
+        float* base = a.part_o + slot_prev * VW + lane * 4;
 #pragma unroll
-        for (int c = 0; c < 4; ++c)
+        for (int c = 0; c < NC; ++c)
 #pragma unroll
             for (int g = 0; g < 4; ++g)
                 *reinterpret_cast<f32x4*>(base + pf_offset_floats(4 * c + g)) = f32x4{o[c][4 * g], o[c][4 * g + 1], o[c][4 * g + 2], o[c][4 * g + 3]};
@@ -326,7 +331,7 @@ __global__ __launch_bounds__(NW * 64, 2) void sc_attention_split_kernel(AttSplit
             a.part_ml[(slot_prev + l31) * 2 + 1] = l_prev;
         }
 #pragma unroll
-        for (int c = 0; c < 4; ++c)
+        for (int c = 0; c < NC; ++c)
 #pragma unroll
             for (int r = 0; r < 16; ++r) o[c][r] = 0.f;
     };
@@ -338,9 +343,9 @@ __global__ __launch_bounds__(NW * 64, 2) void sc_attention_split_kernel(AttSplit
     const int q0w = qb * (NW * 32) + wave * 32;                       // first query of this wave inside the pair
     auto leaf_store = [&](int lf, float m_st, float l_st) {
         const size_t slot = ((size_t)b * a.nleaf + lf) * a.Npad + q0w;
-        float* base = a.part_o + slot * PDSC_CHANNELS + lane * 4;
+        float* base = a.part_o + slot * VW + lane * 4;
 #pragma unroll
-        for (int c = 0; c < 4; ++c)
+        for (int c = 0; c < NC; ++c)
 #pragma unroll
             for (int g = 0; g < 4; ++g)
                 *reinterpret_cast<f32x4*>(base + pf_offset_floats(4 * c + g)) = f32x4{o[c][4 * g], o[c][4 * g + 1], o[c][4 * g + 2], o[c][4 * g + 3]};
@@ -352,7 +357,7 @@ __global__ __launch_bounds__(NW * 64, 2) void sc_attention_split_kernel(AttSplit
     int leaf_prev = 0;                          // MG: the leaf whose partial is pending (m_prev, l_prev, pend)
 
     const int koff = l31 * 16 + 512 * h;            // K image (chunk-major): chunk 2j+h of key l31 -> + 1024 j   (immediates)
-    const int voff = l31 * 16 + 2048 * h;           // V^T image: chunk 2j+h of channel 32c + l31 -> + 4096 j + 512 c
+    const int voff = l31 * 16 + (VW * 16) * h;      // V^T image: chunk 2j+h of channel 32c + l31 -> + 2 VW 16 j + 512 c (VW = 128: 4096 j)
     const int crow_off = (wave * 32 + l31) * CROW;  // compat row of this lane's query in a compat stage
     const int csw = C16 ? (l31 >> 2) & 3 : ((wave * 32 + l31) >> 1) & 7;
     constexpr float C16_INV = 1.0f / 65535.0f;      // 65535 * fl(1/65535) == 1.0f exactly (and 0 stays 0)
@@ -496,7 +501,7 @@ __global__ __launch_bounds__(NW * 64, 2) void sc_attention_split_kernel(AttSplit
             // zero IN PLACE (one asm statement per register, as scale_acc: plain assignments made the register allocator keep two
             // copies of O and move one per tile when this sat behind a run-time branch, r05a)
 #pragma unroll
-            for (int c = 0; c < 4; ++c)
+            for (int c = 0; c < NC; ++c)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     float v = o[c][r];
@@ -563,27 +568,34 @@ __global__ __launch_bounds__(NW * 64, 2) void sc_attention_split_kernel(AttSplit
         l_run += psum;
         PDSC_TRACE_STAMP(5)                      // 5: phase A
 
-        // ---- phase B: O^T += V^T P^T (8 steps: channel block c, key half j) | logits of tile kt+1 ---------------
+        // ---- phase B: O^T += V^T P^T (2 NC groups: channel block c, key half j) | logits of tile kt+1 -----------
+        //      8 steps either way: VW = 128 issues one group of three MFMAs per step, VW = 64 one per even step (12 MFMAs against
+        //      the same vector work -- the logits of tile kt+1 and the DMA slots keep their steps)
         {
-            const unsigned char* V = Vs + st * SPL_V_BYTES;
+            const unsigned char* V = Vs + st * VB;
             const unsigned char* Cn = Cs + (st ^ 1) * CSTAGE + crow_off;
             unsigned cw[8];
             mx_next = -INFINITY;                 // row maximum of tile kt+1's logits, gathered as they are formed
             sp16x8 vh = *reinterpret_cast<const sp16x8*>(V + voff);
-            sp16x8 vl = *reinterpret_cast<const sp16x8*>(V + SPL_V_PLANE + voff);
+            sp16x8 vl = *reinterpret_cast<const sp16x8*>(V + VPL + voff);
 #pragma unroll
             for (int u = 0; u < 8; ++u) {
-                const int c = u >> 1, j = u & 1;
+                constexpr int NG = 2 * NC;
+                const bool mm = VW == 128 || (u & 1) == 0;       // (compile-time after unrolling)
+                const int gi = VW == 128 ? u : u >> 1;
+                const int c = gi >> 1, j = gi & 1;
                 sp16x8 nvh = vh, nvl = vl;
-                if (u + 1 < 8) {
-                    const int vo = ((u + 1) >> 1) * 512 + voff + 4096 * ((u + 1) & 1);
+                if (mm && gi + 1 < NG) {
+                    const int vo = ((gi + 1) >> 1) * 512 + voff + (2 * VW * 16) * ((gi + 1) & 1);
                     nvh = *reinterpret_cast<const sp16x8*>(V + vo);
-                    nvl = *reinterpret_cast<const sp16x8*>(V + SPL_V_PLANE + vo);
+                    nvl = *reinterpret_cast<const sp16x8*>(V + VPL + vo);
                 }
-                const sp16x8 phj = __builtin_bit_cast(sp16x8, phw[j]), plj = __builtin_bit_cast(sp16x8, plw[j]);
-                o[c] = PDSC_MFMA_IF(2, vl, phj, o[c]);
-                o[c] = PDSC_MFMA_IF(1, vh, plj, o[c]);
-                o[c] = PDSC_MFMA_X3(vh, phj, o[c], 0, 0, 0);
+                if (mm) {
+                    const sp16x8 phj = __builtin_bit_cast(sp16x8, phw[j]), plj = __builtin_bit_cast(sp16x8, plw[j]);
+                    o[c] = PDSC_MFMA_IF(2, vl, phj, o[c]);
+                    o[c] = PDSC_MFMA_IF(1, vh, plj, o[c]);
+                    o[c] = PDSC_MFMA_X3(vh, phj, o[c], 0, 0, 0);
+                }
                 if (!LAST && 8 + u < DMA_SLOTS) dma_slot(kt, st, 8 + u);
                 if (LAST) {
                     // (no tile kt + 1: no logits to form)
@@ -646,7 +658,7 @@ __global__ __launch_bounds__(NW * 64, 2) void sc_attention_split_kernel(AttSplit
 #pragma unroll
                 for (int r = 0; r < 16; ++r) tl[r] -= delta;
 #pragma unroll
-                for (int c = 0; c < 4; ++c) o[c] = scale_acc(o[c], alpha);
+                for (int c = 0; c < NC; ++c) o[c] = scale_acc(o[c], alpha);
             }
         }
         PDSC_TRACE_STAMP(7)
@@ -713,9 +725,9 @@ __global__ __launch_bounds__(NW * 64, 2) void sc_attention_split_kernel(AttSplit
         // point-fragment order (split_layout.h): the accumulator registers of lane (query l31, half h) ARE the 16-byte
         // pieces the fused layer kernel's lane loads -- 1 KiB of consecutive memory per store instruction, no LDS
         // transposition.  Lanes past N hold copies of query N-1 and fill the padding of the pair's last tile.
-        float* base = a.part_o + (((size_t)b * a.nsplit + sp) * a.Npad + q0) * PDSC_CHANNELS + lane * 4;
+        float* base = a.part_o + (((size_t)b * a.nsplit + sp) * a.Npad + q0) * VW + lane * 4;
 #pragma unroll
-        for (int c = 0; c < 4; ++c)
+        for (int c = 0; c < NC; ++c)
 #pragma unroll
             for (int g = 0; g < 4; ++g)
                 *reinterpret_cast<f32x4*>(base + pf_offset_floats(4 * c + g)) = f32x4{o[c][4 * g], o[c][4 * g + 1], o[c][4 * g + 2], o[c][4 * g + 3]};
@@ -735,6 +747,9 @@ __global__ __launch_bounds__(NW * 64, 2) void sc_attention_split_kernel(AttSplit
         }
         return;
     }
+    if constexpr (VW != 128) {
+        return;                                         // (not launched: the 64-wide form leaves point-fragment partials only)
+    } else {
     __syncthreads();                                    // the other waves are done reading K / V
     constexpr int OPITCH = PDSC_CHANNELS * 4 + 16;
     unsigned char* const patch = lds + wave * (32 * OPITCH);
@@ -778,6 +793,7 @@ __global__ __launch_bounds__(NW * 64, 2) void sc_attention_split_kernel(AttSplit
 #pragma unroll
             for (int k = 0; k < 8; ++k) dst[k] = tr[k];
         }
+    }
     }
 }
 
@@ -916,8 +932,10 @@ extern "C" size_t pdsc_attention_leaf_scratch_bytes(int bs, int N, int leaves_mo
 // fragment order) for the H3 layer kernel to merge (C <= MERGE_MAX_SPLIT_H3).
 int pdsc::launch_attention_leaves(const void* q_split, const void* kv_tiles, const void* compat, int compat_format, long long ld,
                                   void* scratch, size_t scratch_bytes, int bs, int N, int leaves_mode, const int* nvalid, int n_min,
-                                  hipStream_t st) {
+                                  hipStream_t st, int value_width) {
     PDSC_REQUIRE(q_split && kv_tiles && compat && scratch, "pdsc_sc_attention_leaves: null pointer");
+    PDSC_REQUIRE(value_width == PDSC_CHANNELS || value_width == PDSC_CHANNELS / 2, "pdsc_sc_attention_leaves: value_width=%d", value_width);
+    const bool v64 = value_width != PDSC_CHANNELS;
     PDSC_REQUIRE(bs > 0 && N > 0, "pdsc_sc_attention_leaves: bs=%d N=%d", bs, N);
     PDSC_REQUIRE(compat_format == PDSC_COMPAT_F32 || compat_format == PDSC_COMPAT_U16, "pdsc_sc_attention_leaves: compat_format=%d", compat_format);
     const bool c16 = compat_format == PDSC_COMPAT_U16;
@@ -928,7 +946,7 @@ int pdsc::launch_attention_leaves(const void* q_split, const void* kv_tiles, con
     // ragged batches: every pair cuts ITS OWN tiles into C leaves -- the shortest pair needs at least C of them
     PDSC_REQUIRE(!nvalid || (n_min + 31) / 32 >= 2 * C, "pdsc_sc_attention_leaves: the shortest pair (%d correspondences) has fewer than two "
                  "32-key tiles for each of the %d leaves planned for bs=%d, N=%d", n_min, C, bs, N);
-    const size_t need = (size_t)bs * C * round_up(N, 256) * (PDSC_CHANNELS + 2) * sizeof(float);
+    const size_t need = (size_t)bs * C * round_up(N, 256) * (value_width + 2) * sizeof(float);
     if (scratch_bytes < need) {
         set_error("pdsc_sc_attention_leaves: scratch %zu < %zu bytes", scratch_bytes, need);
         return PDSC_ERR_WORKSPACE;
@@ -940,27 +958,32 @@ int pdsc::launch_attention_leaves(const void* q_split, const void* kv_tiles, con
     a.nq = ceil_div(N, nw * 32);
     a.nleaf = C;
     a.part_o = (float*)scratch;
-    a.part_ml = a.part_o + (size_t)bs * C * a.Npad * PDSC_CHANNELS;
+    a.part_ml = a.part_o + (size_t)bs * C * a.Npad * value_width;
     a.nvalid = nvalid;
     a.part_frag = 1;
     a.compat_nt = c16 ? 0 : 1;
-    const size_t lds_bytes = 2 * (size_t)(SPL_TILE_BYTES + nw * 32 * (c16 ? 64 : 128));
+    const size_t lds_bytes = 2 * (size_t)((v64 ? spl_tile_bytes<PDSC_CHANNELS / 2>() : SPL_TILE_BYTES) + nw * 32 * (c16 ? 64 : 128));
     const unsigned grid = (unsigned)(a.nq * ns * bs);
     a.items = (int)grid;
     int rc = PDSC_OK;
-#define PDSC_ATT_LAUNCH_MG(NWV, CMV)                                                                                                        \
-    do {                                                                                                                                    \
-        rc = ensure_dynamic_lds(reinterpret_cast<const void*>(&sc_attention_split_kernel<NWV, CMV, false, false, true, true>), lds_bytes,   \
-                                "pdsc_sc_attention_leaves(dynamic LDS)");                                                                   \
-        if (rc != PDSC_OK) return rc;                                                                                                       \
-        profile_mark_begin(PDSC_PROF_ATTENTION, st);                                                                                        \
-        hipLaunchKernelGGL((sc_attention_split_kernel<NWV, CMV, false, false, true, true>), dim3(grid), dim3(NWV * 64), lds_bytes, st, a);  \
-        profile_mark_end(PDSC_PROF_ATTENTION, st);                                                                                          \
+#define PDSC_ATT_LAUNCH_MG(NWV, CMV, VWV)                                                                                                        \
+    do {                                                                                                                                         \
+        rc = ensure_dynamic_lds(reinterpret_cast<const void*>(&sc_attention_split_kernel<NWV, CMV, false, false, true, true, VWV>), lds_bytes,   \
+                                "pdsc_sc_attention_leaves(dynamic LDS)");                                                                        \
+        if (rc != PDSC_OK) return rc;                                                                                                            \
+        profile_mark_begin(PDSC_PROF_ATTENTION, st);                                                                                             \
+        hipLaunchKernelGGL((sc_attention_split_kernel<NWV, CMV, false, false, true, true, VWV>), dim3(grid), dim3(NWV * 64), lds_bytes, st, a);  \
+        profile_mark_end(PDSC_PROF_ATTENTION, st);                                                                                               \
     } while (0)
-    if (nw == 8 && c16) PDSC_ATT_LAUNCH_MG(8, 1);
-    else if (nw == 8) PDSC_ATT_LAUNCH_MG(8, 0);
-    else if (c16) PDSC_ATT_LAUNCH_MG(4, 1);
-    else PDSC_ATT_LAUNCH_MG(4, 0);
+    if (v64) {
+        if (nw == 8 && c16) PDSC_ATT_LAUNCH_MG(8, 1, 64);
+        else if (nw == 8) PDSC_ATT_LAUNCH_MG(8, 0, 64);
+        else if (c16) PDSC_ATT_LAUNCH_MG(4, 1, 64);
+        else PDSC_ATT_LAUNCH_MG(4, 0, 64);
+    } else if (nw == 8 && c16) PDSC_ATT_LAUNCH_MG(8, 1, 128);
+    else if (nw == 8) PDSC_ATT_LAUNCH_MG(8, 0, 128);
+    else if (c16) PDSC_ATT_LAUNCH_MG(4, 1, 128);
+    else PDSC_ATT_LAUNCH_MG(4, 0, 128);
 #undef PDSC_ATT_LAUNCH_MG
     return check_launch("pdsc_sc_attention_leaves");
 }
@@ -1008,8 +1031,10 @@ extern "C" int pdsc_attention_trace(long long* device_buffer) {   // diagnostics
 
 static int launch_attention_split(const void* q_split, const void* kv_tiles, const void* compat, bool c16, long long ld,
                                   float* msg, void* scratch, size_t scratch_bytes, int bs, int N, int nsplit, void* stream,
-                                  int partial_layout = PDSC_PARTIALS_ROWS, const int* nvalid = nullptr) {
+                                  int partial_layout = PDSC_PARTIALS_ROWS, const int* nvalid = nullptr, int value_width = PDSC_CHANNELS) {
     PDSC_REQUIRE(q_split && kv_tiles && compat, "pdsc_sc_attention_split: null pointer");
+    PDSC_REQUIRE(value_width == PDSC_CHANNELS || value_width == PDSC_CHANNELS / 2, "pdsc_sc_attention_split: value_width=%d", value_width);
+    const bool v64 = value_width != PDSC_CHANNELS;
     PDSC_REQUIRE(bs > 0 && N > 0, "pdsc_sc_attention_split: bs=%d N=%d", bs, N);
     PDSC_REQUIRE(ld >= round_up(N, SPL_BK) && ld % (c16 ? 8 : 4) == 0,
                  "pdsc_sc_attention_split: ld=%lld must be a multiple of %d and >= N rounded up to 32", ld, c16 ? 8 : 4);
@@ -1019,7 +1044,7 @@ static int launch_attention_split(const void* q_split, const void* kv_tiles, con
     if (nsplit <= 0) nsplit = ns;
     if (nsplit > tiles) nsplit = tiles;
     PDSC_REQUIRE(msg || nsplit > 1, "pdsc_sc_attention_split: msg == NULL needs a key split > 1 (partials stay in scratch)");
-    const size_t need = nsplit == 1 ? 0 : (size_t)bs * nsplit * round_up(N, 256) * (PDSC_CHANNELS + 2) * sizeof(float);
+    const size_t need = nsplit == 1 ? 0 : (size_t)bs * nsplit * round_up(N, 256) * (value_width + 2) * sizeof(float);
     if (need > 0 && (!scratch || scratch_bytes < need)) {
         set_error("pdsc_sc_attention_split: scratch %zu < %zu bytes", scratch_bytes, need);
         return PDSC_ERR_WORKSPACE;
@@ -1029,7 +1054,7 @@ static int launch_attention_split(const void* q_split, const void* kv_tiles, con
     a.N = N; a.Npad = (int)round_up(N, 256); a.nsplit = nsplit; a.num_tiles = tiles; a.bs = bs;
     a.nq = ceil_div(N, nw * 32);
     a.part_o = (float*)scratch;
-    a.part_ml = a.part_o ? a.part_o + (size_t)bs * nsplit * a.Npad * PDSC_CHANNELS : nullptr;
+    a.part_ml = a.part_o ? a.part_o + (size_t)bs * nsplit * a.Npad * value_width : nullptr;
     a.trace = g_att_trace;
     a.nvalid = nvalid;
     a.prio_mode = env_int("PDSC_ATT_PRIO", 0);
@@ -1038,12 +1063,13 @@ static int launch_attention_split(const void* q_split, const void* kv_tiles, con
     PDSC_REQUIRE(partial_layout == PDSC_PARTIALS_ROWS || partial_layout == PDSC_PARTIALS_PF, "pdsc_sc_attention_split: partial_layout=%d", partial_layout);
     PDSC_REQUIRE(partial_layout == PDSC_PARTIALS_ROWS || (!msg && nsplit > 1), "pdsc_sc_attention_split: point-fragment partials are not merged here (msg must be NULL, key split > 1)");
     a.part_frag = partial_layout == PDSC_PARTIALS_PF;
+    PDSC_REQUIRE(!v64 || a.part_frag, "pdsc_sc_attention_split: a 64-channel value projection leaves point-fragment partials only");
     hipStream_t st = (hipStream_t)stream;
     // 2 stages x (K 16 KiB + V 16 KiB + compat of the workgroup's nw*32 queries: 128 B (fp32) or 64 B (unorm16) per row)
     // ... and at least the epilogue's transposition patches (one 32 x 132-float patch per wave)
     // A/B knob PDSC_ATT_CREG = 1: fp32 compat values straight into registers (no LDS stage)
     const bool creg = !c16 && env_int("PDSC_ATT_CREG", 0) != 0;
-    const size_t stage_bytes = 2 * (size_t)(SPL_TILE_BYTES + (creg ? 0 : nw * 32 * (c16 ? 64 : 128)));
+    const size_t stage_bytes = 2 * (size_t)((v64 ? spl_tile_bytes<PDSC_CHANNELS / 2>() : SPL_TILE_BYTES) + (creg ? 0 : nw * 32 * (c16 ? 64 : 128)));
     const size_t patch_bytes = (size_t)nw * 32 * (PDSC_CHANNELS * 4 + 16);
     // (point-fragment partials leave straight from the accumulators: no transposition patches, so the workgroup asks for its
     //  two stages only -- 96 KiB with the unorm16 matrix -- and leaves the rest of the CU's 160 KiB to other kernels)
@@ -1053,6 +1079,24 @@ static int launch_attention_split(const void* q_split, const void* kv_tiles, con
     const bool trace = nw == 8 && a.trace;
     (void)trace;
     a.items = (int)grid;
+    if (v64) {
+        // the folded value projection (pdsc_config.value_fold): the one-item, peeled form with point-fragment partials
+#define PDSC_ATT_LAUNCH_V64(NWV, CMV)                                                                                                          \
+        do {                                                                                                                                   \
+            rc = ensure_dynamic_lds(reinterpret_cast<const void*>(&sc_attention_split_kernel<NWV, CMV, false, false, true, false, 64>), lds_bytes, \
+                                    "pdsc_sc_attention_split(dynamic LDS)");                                                                   \
+            if (rc != PDSC_OK) return rc;                                                                                                      \
+            profile_mark_begin(PDSC_PROF_ATTENTION, st);                                                                                       \
+            hipLaunchKernelGGL((sc_attention_split_kernel<NWV, CMV, false, false, true, false, 64>), dim3(grid), dim3(NWV * 64), lds_bytes, st, a); \
+            profile_mark_end(PDSC_PROF_ATTENTION, st);                                                                                         \
+        } while (0)
+        if (nw == 8 && c16) PDSC_ATT_LAUNCH_V64(8, 1);
+        else if (nw == 8) PDSC_ATT_LAUNCH_V64(8, 0);
+        else if (c16) PDSC_ATT_LAUNCH_V64(4, 1);
+        else PDSC_ATT_LAUNCH_V64(4, 0);
+#undef PDSC_ATT_LAUNCH_V64
+        return check_launch("pdsc_sc_attention_split(64-channel values)");
+    }
 #ifdef PDSC_EXPERIMENTS
     // A/B knob PDSC_ATT_PERSIST = 1: one workgroup per CU walking its items (point-fragment partials, 8-wave plan, whole
     // multiples of 8 items, at least two per workgroup)
@@ -1126,10 +1170,10 @@ extern "C" int pdsc_sc_attention_split(const void* q_split, const void* kv_tiles
 
 int pdsc::launch_attention_split_ex(const void* q_split, const void* kv_tiles, const void* compat, int compat_format, long long ld,
                                     float* msg, void* scratch, size_t scratch_bytes, int bs, int N, int nsplit, int partial_layout,
-                                    const int* nvalid, hipStream_t st) {
+                                    const int* nvalid, hipStream_t st, int value_width) {
     PDSC_REQUIRE(compat_format == PDSC_COMPAT_F32 || compat_format == PDSC_COMPAT_U16, "pdsc_sc_attention_split: compat_format=%d", compat_format);
     return launch_attention_split(q_split, kv_tiles, compat, compat_format == PDSC_COMPAT_U16, ld, msg, scratch, scratch_bytes, bs, N,
-                                  nsplit, st, partial_layout, nvalid);
+                                  nsplit, st, partial_layout, nvalid, value_width);
 }
 
 extern "C" int pdsc_sc_attention_split_partials(const void* q_split, const void* kv_tiles, const void* compat, int compat_format,

@@ -33,6 +33,8 @@ struct LayerArgs {
     int stagger_cycles, stagger_mode;   // layer_h3.hip: start delay of half the first round's wavefronts (A/B knobs PDSC_LAYER_STAGGER, _MODE)
     long long* trace;        // diagnostics (pdsc_layer_trace): [workgroup][wave][16] shader-clock stamps, else NULL
     unsigned int* range_flag; // fp16 range sentinel (pdsc_common.h): [bs] words, or NULL outside a forward
+    int value_fold;          // 1: the folded layer (pdsc_config.value_fold; layer_h3.hip / layer_coop.hip, point-fragment forms only):
+                             // wf_tail / wf_head are the PDSC_WS_FOLD_*_H3 streams, msg / part_o hold 64 channels, V^T planes are 64 wide
     const int* nvalid;       // ragged batches (ragged.h): [bs] correspondences per pair (<= N): tiles past a pair's own rows are
                              // skipped, its last tile is padded / zeroed from ITS count; NULL = every pair has N rows
 };
@@ -41,5 +43,13 @@ int launch_layer_wave(const LayerArgs& a, bool tail, bool head, hipStream_t st);
 int launch_layer_h3(const LayerArgs& a, bool tail, bool head, hipStream_t st);        // layer_h3.hip (H3 fragment streams only)
 int launch_layer_h3_coop(const LayerArgs& a, bool tail, bool head, hipStream_t st);   // layer_coop.hip (same contract, few tiles)
 bool launch_layer_h3_fits(const LayerArgs& a, bool tail, bool head);                  // ... and only this output set
+// pdsc_layer_fused_frag_io with the folded layer selectable (value_fold = 1: the PDSC_WS_FOLD_*_H3 streams, 64-channel partials)
+int layer_fused_frag_io(const float* msg, const float* part_o, const float* part_ml, int nsplit, int Npad, const float* res,
+                        const float* feat_in, float* feat_out, float* featB_out, void* q_split, void* kv_tiles, const void* wfrag_tail,
+                        const void* wfrag_head, int gemm_format, int io_flags, int bs, int N, hipStream_t stream, int value_fold);
+// the folded layer's weights of one layer (layer_wave.hip): wfold = W1f Wv [64][128] | b' [64] fp32, and its H3 tail / head streams
+int build_value_fold(const float* w1, const float* b1, const float* wqkv, const float* bqkv, const float* w2, const float* b2,
+                     const float* w3, const float* b3, const float* wp, const float* bp, float* wfold, void* tail_out, void* head_out,
+                     hipStream_t st);
 
 }  // namespace pdsc

@@ -59,7 +59,9 @@ __device__ __forceinline__ void coop_finish(const f32x16& acc, const f32x16& cro
 // batches, fits 256 registers (236), so two workgroups share a CU: launches of 257..512 tiles (the per-GPU shares of the 8-GPU
 // configurations: 2 pairs of N = 5000, 1 pair of N = 10000) run in one round.  A ring of 6 (382 registers, one workgroup per
 // CU) measured 1-2 % SLOWER even at 32 tiles (profiles/r03_k_ab_coop.txt) and is not instantiated.
-template <bool T, bool H, bool FB_PF, int NB>
+// F: the folded layer (layer_h3_kernel's F): no fc1 stage -- waves 0 and 1 merge the 64-channel message, add b' and hand relu(.) to
+// fc2 -- and q | k | v' has 10 output tiles (the V' tiles 8, 9 on waves 0 and 1)
+template <bool T, bool H, bool FB_PF, int NB, bool F = false>
 __global__ __launch_bounds__(64 * LC_WAVES, NB <= 4 ? 2 : 1) void layer_h3_coop_kernel(LayerArgs a) {
     __shared__ __attribute__((aligned(16))) CoopOps ops;
     __shared__ __attribute__((aligned(16))) float Vs_all[LC_WAVES][32 * LW_VLD];
@@ -84,20 +86,24 @@ __global__ __launch_bounds__(64 * LC_WAVES, NB <= 4 ? 2 : 1) void layer_h3_coop_
     // tail stream: fc1 tile t = chunks 2t, 2t+1; fc2 tile t = 4 + t; fc3 tile t = 6 + t.  head stream: pcn tile t = 2t, 2t+1;
     // q|k|v tile t = 8 + 2t, 9 + 2t.  Bias fragments by tile ordinal (layer_wave.h).  Position k lives in ring slot k % NB and
     // is requested as soon as position k - NB has been consumed.
-    constexpr int K0 = T ? 0 : 4, K1 = H ? 12 : 4;
+    //   (folded, F: positions 0, 1 are empty; fc2 tile t = chunk t, fc3 tile t = 2 + t, bias ordinals the same; positions 10, 11 --
+    //    V' -- on waves 0, 1 only)
+    constexpr int K0 = T ? (F ? 2 : 0) : 4, K1 = H ? 12 : 4;
+    constexpr int TC = tail_chunks<F>(), HC = head_chunks<F>(), TO = F ? 2 : 0;
+    constexpr int VW = F ? LW_FOLD_VW : PDSC_CHANNELS;
     WChunk W[NB];
-    const bool low = w < 2;                                          // fc1 / fc2 have two output tiles: waves 0 and 1
+    const bool low = w < 2;                                          // fc1 / fc2 (and the folded V') have two output tiles: waves 0 and 1
     auto issue = [&](auto kc) {
         constexpr int k = decltype(kc)::value;
         if constexpr (k >= K0 && k < K1) {
             WChunk& dst = W[k % NB];
-            if constexpr (k < 2) { if (low) load_chunk_frag(dst, a.wf_tail, 2 * w + k, LW_TAIL_CHUNKS, k == 0 ? w : -1, lane); }
-            else if constexpr (k == 2) { if (low) load_chunk_frag(dst, a.wf_tail, 4 + w, LW_TAIL_CHUNKS, 2 + w, lane); }
-            else if constexpr (k == 3) load_chunk_frag(dst, a.wf_tail, 6 + w, LW_TAIL_CHUNKS, 4 + w, lane);
-            else if constexpr (k < 6) load_chunk_frag(dst, a.wf_head, 2 * w + (k - 4), LW_HEAD_CHUNKS, k == 4 ? w : -1, lane);
+            if constexpr (k < 2) { if (low) load_chunk_frag(dst, a.wf_tail, 2 * w + k, TC, k == 0 ? w : -1, lane); }
+            else if constexpr (k == 2) { if (low) load_chunk_frag(dst, a.wf_tail, 4 - 2 * TO + w, TC, 2 - TO + w, lane); }
+            else if constexpr (k == 3) load_chunk_frag(dst, a.wf_tail, 6 - 2 * TO + w, TC, 4 - TO + w, lane);
+            else if constexpr (k < 6) load_chunk_frag(dst, a.wf_head, 2 * w + (k - 4), HC, k == 4 ? w : -1, lane);
             else {
                 const int t = w + 4 * ((k - 6) >> 1);
-                load_chunk_frag(dst, a.wf_head, 8 + 2 * t + (k & 1), LW_HEAD_CHUNKS, (k & 1) ? -1 : 4 + t, lane);
+                if (!F || k < 10 || low) load_chunk_frag(dst, a.wf_head, 8 + 2 * t + (k & 1), HC, (k & 1) ? -1 : 4 + t, lane);
             }
         }
     };
@@ -120,16 +126,18 @@ __global__ __launch_bounds__(64 * LC_WAVES, NB <= 4 ? 2 : 1) void layer_h3_coop_
     if constexpr (T) {
         // ---- stage 0: operand of fc1 = the attention's message; this wave converts channels 32w .. 32w+31 (k-steps 2w, 2w+1)
         f32x4 x0[4];
-        if (a.msg) {
+        if (F && !low) {
+            // (folded: the 64-channel message is waves 0 and 1's)
+        } else if (a.msg) {
 #pragma unroll
-            for (int q = 0; q < 4; ++q) x0[q] = *reinterpret_cast<const f32x4*>(a.msg + row * PDSC_CHANNELS + 8 * (4 * w + q) + 4 * h);
+            for (int q = 0; q < 4; ++q) x0[q] = *reinterpret_cast<const f32x4*>(a.msg + row * VW + 8 * (4 * w + q) + 4 * h);
         } else {
             // merge of the attention's key-split partials, the arithmetic of merge_partials_finish (merge_partials.h)
             auto run = [&](auto ns_tag) {
                 constexpr int NS = decltype(ns_tag)::value;
                 const size_t slot0 = (size_t)b * NS * a.Npad + (row - (size_t)b * a.N);
                 const bool pf = a.io_flags & PDSC_IO_PARTIALS_PF;
-                const size_t e0 = pf ? ((size_t)b * NS * a.Npad + (size_t)tile * 32) * PDSC_CHANNELS + lane * 4 : slot0 * PDSC_CHANNELS + 4 * h;
+                const size_t e0 = pf ? ((size_t)b * NS * a.Npad + (size_t)tile * 32) * VW + lane * 4 : slot0 * VW + 4 * h;
                 const int eq = pf ? 256 : 8;
                 // q per batch of loads: everything at once in the latency form; <= 32 registers of partials in flight in the
                 // two-workgroups-per-CU form (256 registers)
@@ -157,7 +165,7 @@ __global__ __launch_bounds__(64 * LC_WAVES, NB <= 4 ? 2 : 1) void layer_h3_coop_
                     for (int q = 0; q < GQ; ++q)
 #pragma unroll
                         for (int sp = 0; sp < NS; ++sp)
-                            pv[q][sp] = *reinterpret_cast<const f32x4*>(a.part_o + e0 + (size_t)sp * a.Npad * PDSC_CHANNELS + (size_t)eq * (4 * w + q0 + q));
+                            pv[q][sp] = *reinterpret_cast<const f32x4*>(a.part_o + e0 + (size_t)sp * a.Npad * VW + (size_t)eq * (4 * w + q0 + q));
 #pragma unroll
                     for (int q = 0; q < GQ; ++q) {
                         f32x4 s = {0.f, 0.f, 0.f, 0.f};
@@ -185,7 +193,21 @@ __global__ __launch_bounds__(64 * LC_WAVES, NB <= 4 ? 2 : 1) void layer_h3_coop_
                 default: run(std::integral_constant<int, 8>{}); break;
             }
         }
-        {
+        if constexpr (F) {
+            // relu(message + b') = fc2's operand (set 1, where fc1's output would go); the arithmetic of layer_h3_kernel's first_operand
+            if (low) {
+                const float* bpr = reinterpret_cast<const float*>(a.wf_tail + LW_FOLD_BPRIME_BYTES);
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const f32x4 bv = *reinterpret_cast<const f32x4*>(bpr + 8 * (4 * w + q) + 4 * h);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) x0[q][e] = fmaxf(x0[q][e] + bv[e], 0.f);
+                }
+                u32x4 ph, pl;
+                make_kstep<true>(x0[0], x0[1], ph, pl, rmax); put(1, 2 * w, ph, pl);
+                make_kstep<true>(x0[2], x0[3], ph, pl, rmax); put(1, 2 * w + 1, ph, pl);
+            }
+        } else {
             u32x4 ph, pl;
             make_kstep<true>(x0[0], x0[1], ph, pl, rmax); put(0, 2 * w, ph, pl);
             make_kstep<true>(x0[2], x0[3], ph, pl, rmax); put(0, 2 * w + 1, ph, pl);
@@ -200,8 +222,9 @@ __global__ __launch_bounds__(64 * LC_WAVES, NB <= 4 ? 2 : 1) void layer_h3_coop_
         }
         __syncthreads();
 
-        // ---- fc1: 128 -> 64, output tile w on waves 0 and 1 --------------------------------------------------------------
-        if (low) {
+        // ---- fc1: 128 -> 64, output tile w on waves 0 and 1 (not in the folded layer) ------------------------------------
+        if constexpr (F) {
+        } else if (low) {
             run_chunk(std::integral_constant<int, 0>{}, 0, 0, true, false_type{});
             run_chunk(std::integral_constant<int, 1>{}, 0, 1, false, false_type{});
             coop_finish<false>(acc, cross, v);
@@ -216,7 +239,7 @@ __global__ __launch_bounds__(64 * LC_WAVES, NB <= 4 ? 2 : 1) void layer_h3_coop_
             issue(std::integral_constant<int, NB>{});                 // (waves 2, 3: positions 0..2 are empty, their slots free)
             issue(std::integral_constant<int, NB + 1>{});
         }
-        __syncthreads();
+        if constexpr (!F) __syncthreads();
 
         // ---- fc2: 64 -> 64, output tile w on waves 0 and 1 ---------------------------------------------------------------
         if (low) {
@@ -328,7 +351,8 @@ __global__ __launch_bounds__(64 * LC_WAVES, NB <= 4 ? 2 : 1) void layer_h3_coop_
             *reinterpret_cast<u32x4*>(img + (h ? SPL_KL : SPL_KH) + spl_k_offset(l31, 4 * w + s)) = chunk_for_store(hi, lo);
         }
 
-        // V^T image: transpose 32 keys x 32 channels through the wave-private LDS patch
+        // V^T image: transpose 32 keys x 32 channels through the wave-private LDS patch (folded: V' tiles 8, 9 on waves 0, 1)
+        if (F && !low) { range_report(a.range_flag, b, rmax); return; }
         run_chunk(std::integral_constant<int, 10>{}, 0, 0, true, true_type{});
         run_chunk(std::integral_constant<int, 11>{}, 0, 1, false, true_type{});
         coop_finish<true>(acc, cross, v);
@@ -352,9 +376,9 @@ __global__ __launch_bounds__(64 * LC_WAVES, NB <= 4 ? 2 : 1) void layer_h3_coop_
             unsigned chi[4], clo[4];
 #pragma unroll
             for (int e = 0; e < 8; e += 2) split2(vt[e], vt[e + 1], chi[e / 2], clo[e / 2]);
-            const int off = spl_v_offset(n0 + cl, jh);
+            const int off = spl_v_offset_w<VW>(n0 + cl, jh);
             *reinterpret_cast<u32x4*>(img + SPL_VH + off) = u32x4{chi[0], chi[1], chi[2], chi[3]};
-            *reinterpret_cast<u32x4*>(img + SPL_VL + off) = u32x4{clo[0], clo[1], clo[2], clo[3]};
+            *reinterpret_cast<u32x4*>(img + (F ? spl_v_lo<LW_FOLD_VW>() : SPL_VL) + off) = u32x4{clo[0], clo[1], clo[2], clo[3]};
         }
     }
     range_report(a.range_flag, b, rmax);
@@ -363,7 +387,15 @@ __global__ __launch_bounds__(64 * LC_WAVES, NB <= 4 ? 2 : 1) void layer_h3_coop_
 int launch_layer_h3_coop(const LayerArgs& a, bool tail, bool head, hipStream_t st) {
     const dim3 grid(a.bs * ceil_div(a.N, 32)), block(64 * LC_WAVES);
     const bool fb_pf = a.io_flags & PDSC_IO_FEATB_PF;
-    if (tail && head && fb_pf) hipLaunchKernelGGL((layer_h3_coop_kernel<true, true, true, 4>), grid, block, 0, st, a);
+    if (a.value_fold) {
+        if (tail && head && fb_pf) hipLaunchKernelGGL((layer_h3_coop_kernel<true, true, true, 4, true>), grid, block, 0, st, a);
+        else if (head && !tail && fb_pf) hipLaunchKernelGGL((layer_h3_coop_kernel<false, true, true, 4, true>), grid, block, 0, st, a);
+        else if (tail && !head) hipLaunchKernelGGL((layer_h3_coop_kernel<true, false, false, 4, true>), grid, block, 0, st, a);
+        else {
+            set_error("pdsc_layer_fused_frag(h3, four wavefronts per tile): the folded layer exists with point-fragment featB only");
+            return PDSC_ERR_ARG;
+        }
+    } else if (tail && head && fb_pf) hipLaunchKernelGGL((layer_h3_coop_kernel<true, true, true, 4>), grid, block, 0, st, a);
     else if (head && !tail && fb_pf) hipLaunchKernelGGL((layer_h3_coop_kernel<false, true, true, 4>), grid, block, 0, st, a);
     else if (tail && head) hipLaunchKernelGGL((layer_h3_coop_kernel<true, true, false, 4>), grid, block, 0, st, a);
     else if (tail) hipLaunchKernelGGL((layer_h3_coop_kernel<true, false, false, 4>), grid, block, 0, st, a);

@@ -33,7 +33,8 @@ constexpr int PDSC_H3_COOP_TILES = 2560;
     if (TRACE && lane == 0) a.trace[(size_t)gw * 64 + (k)] = __builtin_readcyclecounter();
 
 // tiles per stage and whether `d` is the last output tile of its stage (its epilogue feeds the next stage's operands)
-constexpr int stage_tiles(int stage) { return stage == ST_FC1 || stage == ST_FC2 ? 2 : stage == ST_FC3 || stage == ST_PCN ? 4 : 12; }
+template <bool F = false>
+constexpr int stage_tiles(int stage) { return stage == ST_FC1 || stage == ST_FC2 ? 2 : stage == ST_FC3 || stage == ST_PCN ? 4 : F ? 10 : 12; }
 
 // Contract (launch_layer_h3_fits): head => the split streams are the only q|k|v output (qs, kv given, qkv_out NULL);
 // tail + head => feat_out NULL; tail only => feat_out given.  With that the chunk loop has no branch at all: every chunk is
@@ -48,7 +49,9 @@ constexpr int stage_tiles(int stage) { return stage == ST_FC1 || stage == ST_FC2
 // PDSC_H3_COOP_TILES tiles go to layer_coop.hip instead (a lone wavefront per tile is one 42-chunk dependency chain, 28 us
 // whatever the tile count); the r03 small-launch shapes (1-2 waves, ring of 3-4: -5 % at 313-625 tiles, superseded by the
 // four-wavefront kernel) are instantiated in experiments builds only (A/B knob PDSC_LAYER_H3_SHAPE).
-template <bool T, bool H, bool TRACE = false, int PIPE = 6, int EXP = 0, bool FB_PF = false, int NWV = LW_WAVES, int NBUF = 2>
+// F: the folded layer (pdsc_config.value_fold, layer_wave.h): the tail merges 64-channel partials / messages of V' = W1f Wv, adds
+// b' and goes to ReLU -> fc2 (no fc1 GEMM); the head projects q | k | v' with v' 64 channels wide (24 KiB tile images)
+template <bool T, bool H, bool TRACE = false, int PIPE = 6, int EXP = 0, bool FB_PF = false, int NWV = LW_WAVES, int NBUF = 2, bool F = false>
 __global__ __launch_bounds__(64 * NWV, NBUF > 2 ? 1 : 2) void layer_h3_kernel(LayerArgs a) {
     __shared__ __attribute__((aligned(16))) float Vs_all[NWV][32 * LW_VLD];
     const int lane = threadIdx.x & 63;
@@ -80,11 +83,14 @@ __global__ __launch_bounds__(64 * NWV, NBUF > 2 ? 1 : 2) void layer_h3_kernel(La
     }
     LH_STAMP(0)
     float rmax = 0.f;            // fp16 range sentinel: largest |activation| this lane converts to an fp16 hi / lo pair
-    constexpr int NCH = num_chunks<T, H>();
+    constexpr int NCH = num_chunks<T, H, F>();
+    constexpr int VW = F ? LW_FOLD_VW : PDSC_CHANNELS;               // channels of the message / partials this launch merges
+    constexpr int NQ = VW / 8;                                       // ... as 4-float pieces per lane
+    constexpr int SVL = F ? spl_v_lo<LW_FOLD_VW>() : SPL_VL;         // V^T lo plane of the tile image
     WChunk w[NBUF];
     static_for<0, NBUF - 1>([&](auto jc) {
         constexpr int j = decltype(jc)::value;
-        if constexpr (j < NCH) load_chunk<T, true, true>(w[j], a, j, lane);
+        if constexpr (j < NCH) load_chunk<T, true, true, F>(w[j], a, j, lane);
     });
 
     // B operands (k-step kk: channels 16kk + 8h .. +7 of this lane's point) of fc1 | fc2 | fc3 | pcn (H3) and q|k|v (fp16)
@@ -92,20 +98,35 @@ __global__ __launch_bounds__(64 * NWV, NBUF > 2 ? 1 : 2) void layer_h3_kernel(La
     f32x4 y3[16];                                                    // residual rows, then feat (fp32)
     if (T) {
         f32x4 x0[16];
+        // the first GEMM's operand from the merged message: fc1's k-steps, or (folded) relu(message + b') as fc2's k-steps
+        auto first_operand = [&](int kk) __attribute__((always_inline)) {
+            if constexpr (F) {
+                const float* bpr = reinterpret_cast<const float*>(a.wf_tail + LW_FOLD_BPRIME_BYTES);
+#pragma unroll
+                for (int u = 0; u < 2; ++u) {
+                    const f32x4 bv = *reinterpret_cast<const f32x4*>(bpr + 8 * (2 * kk + u) + 4 * h);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) x0[2 * kk + u][e] = fmaxf(x0[2 * kk + u][e] + bv[e], 0.f);
+                }
+                make_kstep<true>(x0[2 * kk], x0[2 * kk + 1], a1h[kk], a1l[kk], rmax);
+            } else {
+                make_kstep<true>(x0[2 * kk], x0[2 * kk + 1], a0h[kk], a0l[kk], rmax);
+            }
+        };
         if (a.msg) {
 #pragma unroll
-            for (int q = 0; q < 16; ++q) x0[q] = *reinterpret_cast<const f32x4*>(a.msg + row * PDSC_CHANNELS + 8 * q + 4 * h);
+            for (int q = 0; q < NQ; ++q) x0[q] = *reinterpret_cast<const f32x4*>(a.msg + row * VW + 8 * q + 4 * h);
 #pragma unroll
-            for (int kk = 0; kk < 8; ++kk) make_kstep<true>(x0[2 * kk], x0[2 * kk + 1], a0h[kk], a0l[kk], rmax);
+            for (int kk = 0; kk < NQ / 2; ++kk) first_operand(kk);
         } else {
             // merge of the attention's key-split partials, the arithmetic of merge_partials_finish (merge_partials.h)
             auto run = [&](auto ns_tag) {
                 constexpr int NS = decltype(ns_tag)::value;
-                constexpr int GQ = NS <= 2 ? 16 : NS <= 4 ? 8 : 4;   // k-steps per batch of loads (up to 128 registers in flight)
+                constexpr int GQ = (NS <= 2 ? 16 : NS <= 4 ? 8 : 4) < NQ ? (NS <= 2 ? 16 : NS <= 4 ? 8 : 4) : NQ;   // pieces per batch of loads (<= 128 registers in flight)
                 const size_t slot0 = (size_t)b * NS * a.Npad + (row - (size_t)b * a.N);
                 // element q of split sp: rows order = row `slot`, floats 8q + 4h; point-fragment order = tile base + 256 q + 4 lane
                 const bool pf = a.io_flags & PDSC_IO_PARTIALS_PF;
-                const size_t e0 = pf ? ((size_t)b * NS * a.Npad + (size_t)tile * 32) * PDSC_CHANNELS + lane * 4 : slot0 * PDSC_CHANNELS + 4 * h;
+                const size_t e0 = pf ? ((size_t)b * NS * a.Npad + (size_t)tile * 32) * VW + lane * 4 : slot0 * VW + 4 * h;
                 const int eq = pf ? 256 : 8;
                 float wsp[NS], ls[NS];
 #pragma unroll
@@ -124,14 +145,14 @@ __global__ __launch_bounds__(64 * NWV, NBUF > 2 ? 1 : 2) void layer_h3_kernel(La
                 }
                 const float rden = 1.0f / den;
 #pragma unroll
-                for (int q0 = 0; q0 < 16; q0 += GQ) {
+                for (int q0 = 0; q0 < NQ; q0 += GQ) {
                     f32x4 pv[GQ][NS];
 #pragma unroll
                     for (int q = 0; q < GQ; ++q)
 #pragma unroll
                         for (int sp = 0; sp < NS; ++sp)
                             pv[q][sp] = (EXP & 4) ? f32x4{1.f, 2.f, 3.f, (float)lane}
-                                                  : *reinterpret_cast<const f32x4*>(a.part_o + e0 + (size_t)sp * a.Npad * PDSC_CHANNELS + eq * (q0 + q));
+                                                  : *reinterpret_cast<const f32x4*>(a.part_o + e0 + (size_t)sp * a.Npad * VW + eq * (q0 + q));
 #pragma unroll
                     for (int q = 0; q < GQ; ++q) {
                         f32x4 acc = {0.f, 0.f, 0.f, 0.f};
@@ -146,7 +167,7 @@ __global__ __launch_bounds__(64 * NWV, NBUF > 2 ? 1 : 2) void layer_h3_kernel(La
                         }                                               // to the first MFMA and keeps every batch of loads live)
                     }
 #pragma unroll
-                    for (int kk = q0 / 2; kk < (q0 + GQ) / 2; ++kk) make_kstep<true>(x0[2 * kk], x0[2 * kk + 1], a0h[kk], a0l[kk], rmax);
+                    for (int kk = q0 / 2; kk < (q0 + GQ) / 2; ++kk) first_operand(kk);
                     __builtin_amdgcn_sched_barrier(0);               // keep the next batch's loads behind this batch's use
                 }
             };
@@ -278,10 +299,10 @@ __global__ __launch_bounds__(64 * NWV, NBUF > 2 ? 1 : 2) void layer_h3_kernel(La
                         unsigned chi[4], clo[4];
 #pragma unroll
                         for (int e = 0; e < 8; e += 2) split2(vt[e], vt[e + 1], chi[e / 2], clo[e / 2]);
-                        const int off = spl_v_offset(32 * (d.tile - 8) + cl, jh);
+                        const int off = spl_v_offset_w<VW>(32 * (d.tile - 8) + cl, jh);
                         if constexpr (!(EXP & (2 | 32))) {
                             *reinterpret_cast<u32x4*>(img + SPL_VH + off) = u32x4{chi[0], chi[1], chi[2], chi[3]};
-                            *reinterpret_cast<u32x4*>(img + SPL_VL + off) = u32x4{clo[0], clo[1], clo[2], clo[3]};
+                            *reinterpret_cast<u32x4*>(img + SVL + off) = u32x4{clo[0], clo[1], clo[2], clo[3]};
                         } else asm volatile("" :: "v"(chi[0]), "v"(chi[1]), "v"(chi[2]), "v"(chi[3]), "v"(clo[0]), "v"(clo[1]), "v"(clo[2]), "v"(clo[3]), "v"(off));
                     }
                 }
@@ -291,8 +312,8 @@ __global__ __launch_bounds__(64 * NWV, NBUF > 2 ? 1 : 2) void layer_h3_kernel(La
 
     static_for<0, NCH>([&](auto ic) {
         constexpr int i = decltype(ic)::value;
-        constexpr ChunkDesc d = chunk_desc<T>(i);
-        if constexpr (i + NBUF - 1 < NCH && !((EXP & 1) && i >= 1)) load_chunk<T, true, true>(w[(i + NBUF - 1) % NBUF], a, i + NBUF - 1, lane);
+        constexpr ChunkDesc d = chunk_desc<T, F>(i);
+        if constexpr (i + NBUF - 1 < NCH && !((EXP & 1) && i >= 1)) load_chunk<T, true, true, F>(w[(i + NBUF - 1) % NBUF], a, i + NBUF - 1, lane);
         if constexpr (T && d.stage == ST_FC2 && d.tile == 0 && !(EXP & 4)) {
             // residual rows for fc3's epilogue (the fc1 operand is dead, its registers are free): they come from HBM
             const bool pf = a.io_flags & PDSC_IO_RES_PF;
@@ -344,7 +365,7 @@ __global__ __launch_bounds__(64 * NWV, NBUF > 2 ? 1 : 2) void layer_h3_kernel(La
             for (int g = 0; g < 4; ++g)
 #pragma unroll
                 for (int e = 0; e < 4; ++e) vp[g][e] = d.stage != ST_QKV ? fmaf(cross[4 * g + e], H3_INV, acc[4 * g + e]) : acc[4 * g + e];
-            if constexpr (d.tile == stage_tiles(d.stage) - 1) {
+            if constexpr (d.tile == stage_tiles<F>(d.stage) - 1) {
                 // the next stage's first MFMA reads what this epilogue produces (or the kernel ends): in line
                 static_for<0, 8>([&](auto sc) { epi(StageC{}, std::integral_constant<int, d.tile>{}, sc, vp); });
             }
@@ -387,6 +408,7 @@ int launch_layer_h3(const LayerArgs& a, bool tail, bool head, hipStream_t st) {
     const int waves = a.bs * ceil_div(a.N, 32);
     int nwv, nbuf;
     h3_launch_shape(waves, &nwv, &nbuf);
+    if (a.value_fold) { nwv = LW_WAVES; nbuf = 2; }                // (the folded layer: product shape only)
     const dim3 grid(ceil_div(waves, nwv)), block(64 * nwv);
     const bool fb_pf = a.io_flags & PDSC_IO_FEATB_PF;
     const bool timed = tail && head;
@@ -418,7 +440,17 @@ int launch_layer_h3(const LayerArgs& a, bool tail, bool head, hipStream_t st) {
         PDSC_H3_LAUNCH_EXTRA(TT, HH, PF)                                                                                            \
         hipLaunchKernelGGL((layer_h3_kernel<TT, HH, false, 6, 0, PF>), grid, block, 0, st, a);                                       \
     } while (0)
-    if (tail && head && fb_pf) {
+    if (a.value_fold) {
+        // the folded layer: the three forms of the point-fragment forward (head of layer 0, tail + head, tail of the last layer)
+        if (tail && head && fb_pf) hipLaunchKernelGGL((layer_h3_kernel<true, true, false, 6, 0, true, LW_WAVES, 2, true>), grid, block, 0, st, a);
+        else if (head && !tail && fb_pf) hipLaunchKernelGGL((layer_h3_kernel<false, true, false, 6, 0, true, LW_WAVES, 2, true>), grid, block, 0, st, a);
+        else if (tail && !head) hipLaunchKernelGGL((layer_h3_kernel<true, false, false, 6, 0, false, LW_WAVES, 2, true>), grid, block, 0, st, a);
+        else {
+            if (timed) profile_mark_end(PDSC_PROF_LAYER, st);
+            set_error("pdsc_layer_fused_frag(h3): the folded layer exists with point-fragment featB only");
+            return PDSC_ERR_ARG;
+        }
+    } else if (tail && head && fb_pf) {
 #ifdef PDSC_LAYER_DIAG      // knock-out build (PDSC_HIPCC_EXTRA=-DPDSC_LAYER_DIAG python -m pointdsc_amd.build --force; tools/layer_bench.py)
         const int ex = env_int("PDSC_LAYER_H3_EXP", 0);
         if (ex == 1) hipLaunchKernelGGL((layer_h3_kernel<true, true, false, 6, 1, true>), grid, block, 0, st, a);
@@ -470,7 +502,17 @@ extern "C" int pdsc_layer_fused_frag_io(const float* msg, const float* part_o, c
                                         const float* res, const float* feat_in, float* feat_out, float* featB_out,
                                         void* q_split, void* kv_tiles, const void* wfrag_tail, const void* wfrag_head,
                                         int gemm_format, int io_flags, int bs, int N, void* stream) {
-    if (io_flags == 0)
+    return pdsc::layer_fused_frag_io(msg, part_o, part_ml, nsplit, Npad, res, feat_in, feat_out, featB_out, q_split, kv_tiles, wfrag_tail,
+                                     wfrag_head, gemm_format, io_flags, bs, N, (hipStream_t)stream, PDSC_VALUE_FOLD_OFF);
+}
+
+int pdsc::layer_fused_frag_io(const float* msg, const float* part_o, const float* part_ml, int nsplit, int Npad, const float* res,
+                              const float* feat_in, float* feat_out, float* featB_out, void* q_split, void* kv_tiles,
+                              const void* wfrag_tail, const void* wfrag_head, int gemm_format, int io_flags, int bs, int N,
+                              hipStream_t stream, int value_fold) {
+    PDSC_REQUIRE(value_fold == PDSC_VALUE_FOLD_OFF || (io_flags & PDSC_IO_PARTIALS_PF) || !(msg || part_o),
+                 "pdsc_layer_fused_frag_io: the folded layer merges point-fragment partials");
+    if (io_flags == 0 && value_fold == PDSC_VALUE_FOLD_OFF)
         return pdsc_layer_fused_frag_fmt(msg, part_o, part_ml, nsplit, Npad, res, feat_in, feat_out, featB_out, nullptr, q_split, kv_tiles,
                                          wfrag_tail, wfrag_head, gemm_format, bs, N, stream);
     const bool tail = msg != nullptr || part_o != nullptr, head = featB_out != nullptr;
@@ -502,6 +544,7 @@ extern "C" int pdsc_layer_fused_frag_io(const float* msg, const float* part_o, c
     a.trace = nullptr;
     a.nvalid = layer_nvalid_slot();
     a.range_flag = range_flag_slot();
+    a.value_fold = value_fold;
     PDSC_REQUIRE(launch_layer_h3_fits(a, tail, head), "pdsc_layer_fused_frag_io: output set not served by the point-fragment kernel "
                                                      "(tail + head: no feat_out; tail only: feat_out)");
     return launch_layer_h3(a, tail, head, (hipStream_t)stream);

@@ -16,6 +16,7 @@
 #include "pdsc_common.h"
 #include "split_layout.h"
 #include "merge_partials.h"
+#include "layer_args.h"
 
 namespace pdsc {
 
@@ -309,8 +310,19 @@ static long long wsplit_layer_elems() {
 // ... in both GEMM formats (enum pdsc_layer_gemm): [tail F32][head F32][tail H3][head H3]
 static long long wsplit_frag_layer_elems() { return (long long)(pdsc_wfrag_tail_bytes() + pdsc_wfrag_head_bytes()); }
 
+// value_fold = 1: after everything above, per layer [fold tail H3][fold head H3][W1f Wv | b' fp32] (16-bit elements)
+static long long wsplit_fold_layer_elems() {
+    return (long long)(pdsc_wfrag_fold_tail_bytes() + pdsc_wfrag_fold_head_bytes()) / 2 + 2LL * (PDSC_CHANNELS / 2) * (PDSC_CHANNELS + 1);
+}
+
 extern "C" long long pdsc_wsplit_offset(const pdsc_config* cfg, int section, int layer) {
     if (!cfg || layer < 0 || layer >= cfg->num_layers) return -1;
+    if (section >= PDSC_WS_FOLD_TAIL_H3 && section <= PDSC_WS_FOLD_W) {
+        if (cfg->value_fold != PDSC_VALUE_FOLD_ON) return -1;
+        const long long tail = (long long)pdsc_wfrag_fold_tail_bytes() / 2, head = (long long)pdsc_wfrag_fold_head_bytes() / 2;
+        const long long inside = section == PDSC_WS_FOLD_TAIL_H3 ? 0 : section == PDSC_WS_FOLD_HEAD_H3 ? tail : tail + head;
+        return (long long)cfg->num_layers * (wsplit_layer_elems() + wsplit_frag_layer_elems()) + (long long)layer * wsplit_fold_layer_elems() + inside;
+    }
     if (section >= PDSC_WS_FRAG_TAIL && section <= PDSC_WS_FRAG_HEAD_H3) {
         const long long tail = (long long)pdsc_wfrag_tail_bytes() / 2, head = (long long)pdsc_wfrag_head_bytes() / 2;
         const long long inside = section == PDSC_WS_FRAG_TAIL ? 0 : section == PDSC_WS_FRAG_HEAD ? tail
@@ -327,7 +339,8 @@ extern "C" long long pdsc_wsplit_offset(const pdsc_config* cfg, int section, int
 
 extern "C" size_t pdsc_wsplit_bytes(const pdsc_config* cfg) {
     if (!cfg || cfg->num_layers < 0) return 0;
-    return (size_t)cfg->num_layers * (wsplit_layer_elems() + wsplit_frag_layer_elems()) * sizeof(sp16);
+    const long long fold = cfg->value_fold == PDSC_VALUE_FOLD_ON ? wsplit_fold_layer_elems() : 0;
+    return (size_t)cfg->num_layers * (wsplit_layer_elems() + wsplit_frag_layer_elems() + fold) * sizeof(sp16);
 }
 
 extern "C" int pdsc_wsplit_build(const pdsc_config* cfg, const float* wpack, void* wsplit, void* stream) {
@@ -350,6 +363,13 @@ extern "C" int pdsc_wsplit_build(const pdsc_config* cfg, const float* wpack, voi
             rc = pdsc_wfrag_build_head_fmt(W(PDSC_W_PCN_W), W(PDSC_W_PCN_B), W(PDSC_W_QKV_W), W(PDSC_W_QKV_B),
                                            (sp16*)wsplit + pdsc_wsplit_offset(cfg, h3 ? PDSC_WS_FRAG_HEAD_H3 : PDSC_WS_FRAG_HEAD, layer),
                                            fmt, stream);
+            if (rc != PDSC_OK) return rc;
+        }
+        if (cfg->value_fold == PDSC_VALUE_FOLD_ON) {
+            auto at = [&](int section) { return (sp16*)wsplit + pdsc_wsplit_offset(cfg, section, layer); };
+            const int rc = build_value_fold(W(PDSC_W_FC1_W), W(PDSC_W_FC1_B), W(PDSC_W_QKV_W), W(PDSC_W_QKV_B), W(PDSC_W_FC2_W), W(PDSC_W_FC2_B),
+                                            W(PDSC_W_FC3_W), W(PDSC_W_FC3_B), W(PDSC_W_PCN_W), W(PDSC_W_PCN_B), (float*)at(PDSC_WS_FOLD_W),
+                                            at(PDSC_WS_FOLD_TAIL_H3), at(PDSC_WS_FOLD_HEAD_H3), (hipStream_t)stream);
             if (rc != PDSC_OK) return rc;
         }
     }

@@ -32,14 +32,18 @@ __device__ __forceinline__ void static_for(F&& f) {
 enum { ST_FC1 = 0, ST_FC2, ST_FC3, ST_PCN, ST_QKV };
 struct ChunkDesc { int stage, tile, chunk, nchunks; };
 
-template <bool T, bool H>
-constexpr int num_chunks() { return (T ? 10 : 0) + (H ? 32 : 0); }
+// F (pdsc_config.value_fold): the folded layer -- fc1 lives in the value projection (V' = W1f Wv, 64 channels), so the tail
+// stream is fc2, fc3 (6 chunks) and the head stream pcn, q, k, v' (28 chunks: q|k|v' has 10 output tiles instead of 12)
+template <bool T, bool H, bool F = false>
+constexpr int num_chunks() { return (T ? (F ? 6 : 10) : 0) + (H ? (F ? 28 : 32) : 0); }
 
-template <bool T>
+template <bool T, bool F = false>
 constexpr ChunkDesc chunk_desc(int i) {
     if (T) {
-        if (i < 4) return {ST_FC1, i / 2, i % 2, 2};
-        i -= 4;
+        if (!F) {
+            if (i < 4) return {ST_FC1, i / 2, i % 2, 2};
+            i -= 4;
+        }
         if (i < 2) return {ST_FC2, i, 0, 1};
         i -= 2;
         if (i < 4) return {ST_FC3, i, 0, 1};
@@ -51,10 +55,19 @@ constexpr ChunkDesc chunk_desc(int i) {
 }
 
 // ordinal of the output tile inside its stream (tail: fc1 0..1, fc2 2..3, fc3 4..7; head: pcn 0..3, q|k|v 4..15)
+// (folded tail: fc2 0..1, fc3 2..5)
+template <bool F = false>
 constexpr int tile_ordinal(const ChunkDesc d) {
-    return d.stage == ST_FC1 ? d.tile : d.stage == ST_FC2 ? 2 + d.tile : d.stage == ST_FC3 ? 4 + d.tile : d.stage == ST_PCN ? d.tile : 4 + d.tile;
+    constexpr int o = F ? 2 : 0;
+    return d.stage == ST_FC1 ? d.tile : d.stage == ST_FC2 ? 2 - o + d.tile : d.stage == ST_FC3 ? 4 - o + d.tile : d.stage == ST_PCN ? d.tile : 4 + d.tile;
 }
 constexpr int LW_TAIL_CHUNKS = 10, LW_HEAD_CHUNKS = 32, LW_TAIL_TILES = 8, LW_HEAD_TILES = 16;
+constexpr int LW_FOLD_TAIL_CHUNKS = 6, LW_FOLD_HEAD_CHUNKS = 28, LW_FOLD_TAIL_TILES = 6, LW_FOLD_HEAD_TILES = 14;
+constexpr int LW_FOLD_VW = PDSC_CHANNELS / 2;      // channels of V' (and of the folded attention's partials / messages)
+template <bool F> constexpr int tail_chunks() { return F ? LW_FOLD_TAIL_CHUNKS : LW_TAIL_CHUNKS; }
+template <bool F> constexpr int head_chunks() { return F ? LW_FOLD_HEAD_CHUNKS : LW_HEAD_CHUNKS; }
+// folded tail stream: chunks, bias fragments, then b' = W1f bv + b1f (64 fp32) -- the bias of the merged 64-channel message
+constexpr int LW_FOLD_BPRIME_BYTES = LW_FOLD_TAIL_CHUNKS * 8192 + LW_FOLD_TAIL_TILES * 256;
 
 __device__ __forceinline__ void load_rows_f32(WChunk& w, const float* __restrict__ p) {
 #pragma unroll
@@ -75,13 +88,14 @@ __device__ __forceinline__ void load_chunk_frag(WChunk& w, const unsigned char* 
     if (bias_tile >= 0) w.bias = *reinterpret_cast<const float*>(stream + (size_t)nchunks * LW_CHUNK_BYTES + bias_tile * 256 + lane * 4);
 }
 
-template <bool T, bool X3, bool FRAG>
+template <bool T, bool X3, bool FRAG, bool F = false>
 __device__ __forceinline__ void load_chunk(WChunk& w, const LayerArgs& a, const int i, int lane) {
-    const ChunkDesc d = chunk_desc<T>(i);
-    const int bias_tile = d.chunk == 0 ? tile_ordinal(d) : -1;
+    const ChunkDesc d = chunk_desc<T, F>(i);
+    const int bias_tile = d.chunk == 0 ? tile_ordinal<F>(d) : -1;
+    static_assert(FRAG || !F, "the folded layer takes fragment streams");
     if (FRAG) {
-        if (T && i < LW_TAIL_CHUNKS) load_chunk_frag(w, a.wf_tail, i, LW_TAIL_CHUNKS, bias_tile, lane);
-        else load_chunk_frag(w, a.wf_head, i - (T ? LW_TAIL_CHUNKS : 0), LW_HEAD_CHUNKS, bias_tile, lane);
+        if (T && i < tail_chunks<F>()) load_chunk_frag(w, a.wf_tail, i, tail_chunks<F>(), bias_tile, lane);
+        else load_chunk_frag(w, a.wf_head, i - (T ? tail_chunks<F>() : 0), head_chunks<F>(), bias_tile, lane);
         return;
     }
     const int l31 = lane & 31, h = lane >> 5;

@@ -340,19 +340,23 @@ __device__ __forceinline__ u32x4 wfrag_h3_slot(const float* __restrict__ src, in
     return u32x4{w[0], w[1], w[2], w[3]};
 }
 
+// F (folded layer, layer_wave.h): fc2, fc3 only, then b' (`bprime`, 64 fp32) behind the bias fragments; w1 / b1 unused
+template <bool F = false>
 __global__ __launch_bounds__(256) void wfrag_tail_kernel(const float* __restrict__ w1, const float* __restrict__ b1,
                                                          const float* __restrict__ w2, const float* __restrict__ b2,
                                                          const float* __restrict__ w3, const float* __restrict__ b3,
-                                                         float* __restrict__ out, int fmt) {
+                                                         const float* __restrict__ bprime, float* __restrict__ out, int fmt) {
+    constexpr int NC = tail_chunks<F>(), NT = F ? LW_FOLD_TAIL_TILES : LW_TAIL_TILES, TO = F ? 2 : 0;
     const int idx = blockIdx.x * 256 + threadIdx.x;                  // one float4 = (chunk, slot, lane)
-    if (idx < LW_TAIL_TILES * 64) {                                  // bias fragments behind the chunks
+    if (idx < NT * 64) {                                             // bias fragments behind the chunks
         const int t = idx >> 6, lane = idx & 63;
-        const float* b = t < 2 ? b1 + 32 * t : t < 4 ? b2 + 32 * (t - 2) : b3 + 32 * (t - 4);
-        out[(size_t)LW_TAIL_CHUNKS * LW_CHUNK_BYTES / 4 + idx] = lane < 32 ? b[lane] : 0.f;
+        const float* b = t < 2 - TO ? b1 + 32 * t : t < 4 - TO ? b2 + 32 * (t - 2 + TO) : b3 + 32 * (t - 4 + TO);
+        out[(size_t)NC * LW_CHUNK_BYTES / 4 + idx] = lane < 32 ? b[lane] : 0.f;
     }
-    if (idx >= LW_TAIL_CHUNKS * 8 * 64) return;
+    if (F && idx < LW_FOLD_VW) out[LW_FOLD_BPRIME_BYTES / 4 + idx] = bprime[idx];
+    if (idx >= NC * 8 * 64) return;
     const int c = idx >> 9, s = (idx >> 6) & 7, lane = idx & 63, l31 = lane & 31, h = lane >> 5;
-    const ChunkDesc d = chunk_desc<true>(c);
+    const ChunkDesc d = chunk_desc<true, F>(c);
     const int n = 32 * d.tile + l31;
     const float* src = d.stage == ST_FC1 ? w1 + (size_t)n * 128 + 64 * d.chunk : d.stage == ST_FC2 ? w2 + (size_t)n * 64 : w3 + (size_t)n * 64;
     if (fmt == PDSC_LAYER_GEMM_H3)      // slot 2k = hi, 2k+1 = lo' of the chunk's k-step k: channels 16k + 8h .. +7
@@ -361,19 +365,23 @@ __global__ __launch_bounds__(256) void wfrag_tail_kernel(const float* __restrict
         *reinterpret_cast<f32x4*>(out + (size_t)idx * 4) = *reinterpret_cast<const f32x4*>(src + 8 * s + 4 * h);
 }
 
+// F (folded layer): q | k | v' with the v' rows (output tiles 8, 9) from `wfold` = W1f Wv [64][128] and no bias
+template <bool F = false>
 __global__ __launch_bounds__(256) void wfrag_head_kernel(const float* __restrict__ wp, const float* __restrict__ bp,
                                                          const float* __restrict__ wq, const float* __restrict__ bq,
-                                                         unsigned char* __restrict__ out, int fmt) {
+                                                         const float* __restrict__ wfold, unsigned char* __restrict__ out, int fmt) {
+    constexpr int NC = head_chunks<F>(), NT = F ? LW_FOLD_HEAD_TILES : LW_HEAD_TILES;
     const int idx = blockIdx.x * 256 + threadIdx.x;
-    if (idx < LW_HEAD_TILES * 64) {
+    if (idx < NT * 64) {
         const int t = idx >> 6, lane = idx & 63;
         const float* b = t < 4 ? bp + 32 * t : bq + 32 * (t - 4);
-        reinterpret_cast<float*>(out + (size_t)LW_HEAD_CHUNKS * LW_CHUNK_BYTES)[idx] = lane < 32 ? b[lane] : 0.f;
+        reinterpret_cast<float*>(out + (size_t)NC * LW_CHUNK_BYTES)[idx] = lane < 32 && !(F && t >= 12) ? b[lane] : 0.f;
     }
-    if (idx >= LW_HEAD_CHUNKS * 8 * 64) return;
+    if (idx >= NC * 8 * 64) return;
     const int c = idx >> 9, s = (idx >> 6) & 7, lane = idx & 63, l31 = lane & 31, h = lane >> 5;
-    const ChunkDesc d = chunk_desc<false>(c);
+    const ChunkDesc d = chunk_desc<false, F>(c);
     const int n = 32 * d.tile + l31;
+    if (F && d.stage == ST_QKV && n >= 2 * PDSC_CHANNELS) wq = wfold - (size_t)2 * PDSC_CHANNELS * 128;     // row n of q|k|v' = row n - 256 of wfold
     if (d.stage == ST_PCN && fmt == PDSC_LAYER_GEMM_H3) {
         *reinterpret_cast<u32x4*>(out + (size_t)idx * 16) = wfrag_h3_slot(wp + (size_t)n * 128 + 64 * d.chunk + 16 * (s >> 1) + 8 * h, s & 1);
     } else if (d.stage == ST_PCN) {
@@ -443,13 +451,48 @@ using namespace pdsc;
 
 extern "C" size_t pdsc_wfrag_tail_bytes(void) { return (size_t)LW_TAIL_CHUNKS * LW_CHUNK_BYTES + LW_TAIL_TILES * 256; }
 extern "C" size_t pdsc_wfrag_head_bytes(void) { return (size_t)LW_HEAD_CHUNKS * LW_CHUNK_BYTES + LW_HEAD_TILES * 256; }
+extern "C" size_t pdsc_wfrag_fold_tail_bytes(void) { return (size_t)LW_FOLD_BPRIME_BYTES + LW_FOLD_VW * sizeof(float); }
+extern "C" size_t pdsc_wfrag_fold_head_bytes(void) { return (size_t)LW_FOLD_HEAD_CHUNKS * LW_CHUNK_BYTES + LW_FOLD_HEAD_TILES * 256; }
+
+// ---- the folded layer's weights (pdsc_config.value_fold) -------------------------------------------------------------------
+// wfold = W1f Wv [64][128] accumulated in fp64 from the packed fp32 matrices and rounded once; then b' = W1f bv + b1f (64), the
+// same way.  One thread per output element.
+__global__ __launch_bounds__(256) void value_fold_kernel(const float* __restrict__ w1, const float* __restrict__ b1,
+                                                         const float* __restrict__ wv, const float* __restrict__ bv,
+                                                         float* __restrict__ wfold) {
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    constexpr int C = PDSC_CHANNELS, H = PDSC_CHANNELS / 2;
+    if (idx < H * C) {
+        const int o = idx / C, c = idx % C;
+        double acc = 0.0;
+        for (int m = 0; m < C; ++m) acc = fma((double)w1[o * C + m], (double)wv[m * C + c], acc);
+        wfold[idx] = (float)acc;
+    } else if (idx < H * C + H) {
+        const int o = idx - H * C;
+        double acc = (double)b1[o];
+        for (int m = 0; m < C; ++m) acc = fma((double)w1[o * C + m], (double)bv[m], acc);
+        wfold[idx] = (float)acc;
+    }
+}
+
+int pdsc::build_value_fold(const float* w1, const float* b1, const float* wqkv, const float* bqkv, const float* w2, const float* b2,
+                           const float* w3, const float* b3, const float* wp, const float* bp, float* wfold, void* tail_out,
+                           void* head_out, hipStream_t st) {
+    constexpr int C = PDSC_CHANNELS, H = PDSC_CHANNELS / 2;
+    hipLaunchKernelGGL(value_fold_kernel, dim3((H * C + H + 255) / 256), dim3(256), 0, st, w1, b1, wqkv + (size_t)2 * C * C, bqkv + 2 * C, wfold);
+    hipLaunchKernelGGL(wfrag_tail_kernel<true>, dim3(LW_FOLD_TAIL_CHUNKS * 8 * 64 / 256), dim3(256), 0, st, w1, b1, w2, b2, w3, b3,
+                       wfold + H * C, (float*)tail_out, (int)PDSC_LAYER_GEMM_H3);
+    hipLaunchKernelGGL(wfrag_head_kernel<true>, dim3(LW_FOLD_HEAD_CHUNKS * 8 * 64 / 256), dim3(256), 0, st, wp, bp, wqkv, bqkv, wfold,
+                       (unsigned char*)head_out, (int)PDSC_LAYER_GEMM_H3);
+    return check_launch("pdsc_wsplit_build(value fold)");
+}
 
 extern "C" int pdsc_wfrag_build_tail_fmt(const float* w1, const float* b1, const float* w2, const float* b2, const float* w3,
                                          const float* b3, void* out, int gemm_format, void* stream) {
     PDSC_REQUIRE(w1 && b1 && w2 && b2 && w3 && b3 && out, "pdsc_wfrag_build_tail: null pointer");
     PDSC_REQUIRE(gemm_format == PDSC_LAYER_GEMM_F32 || gemm_format == PDSC_LAYER_GEMM_H3, "pdsc_wfrag_build_tail: gemm_format=%d", gemm_format);
-    hipLaunchKernelGGL(wfrag_tail_kernel, dim3(LW_TAIL_CHUNKS * 8 * 64 / 256), dim3(256), 0, (hipStream_t)stream, w1, b1, w2, b2, w3, b3,
-                       (float*)out, gemm_format);
+    hipLaunchKernelGGL(wfrag_tail_kernel<false>, dim3(LW_TAIL_CHUNKS * 8 * 64 / 256), dim3(256), 0, (hipStream_t)stream, w1, b1, w2, b2, w3, b3,
+                       nullptr, (float*)out, gemm_format);
     return check_launch("pdsc_wfrag_build_tail");
 }
 
@@ -457,8 +500,8 @@ extern "C" int pdsc_wfrag_build_head_fmt(const float* wp, const float* bp, const
                                          int gemm_format, void* stream) {
     PDSC_REQUIRE(wp && bp && wq && bq && out, "pdsc_wfrag_build_head: null pointer");
     PDSC_REQUIRE(gemm_format == PDSC_LAYER_GEMM_F32 || gemm_format == PDSC_LAYER_GEMM_H3, "pdsc_wfrag_build_head: gemm_format=%d", gemm_format);
-    hipLaunchKernelGGL(wfrag_head_kernel, dim3(LW_HEAD_CHUNKS * 8 * 64 / 256), dim3(256), 0, (hipStream_t)stream, wp, bp, wq, bq,
-                       (unsigned char*)out, gemm_format);
+    hipLaunchKernelGGL(wfrag_head_kernel<false>, dim3(LW_HEAD_CHUNKS * 8 * 64 / 256), dim3(256), 0, (hipStream_t)stream, wp, bp, wq, bq,
+                       nullptr, (unsigned char*)out, gemm_format);
     return check_launch("pdsc_wfrag_build_head");
 }
 

@@ -50,7 +50,9 @@ constexpr int PDSC_REFINE_TRACE = 24;      // ints per pair in the workspace ent
 // msg != NULL: merged output rows (key split 1, or the combine launch); msg == NULL: the key-split partials stay in `scratch`
 int launch_attention_split_ex(const void* q_split, const void* kv_tiles, const void* compat, int compat_format, long long ld,
                               float* msg, void* scratch, size_t scratch_bytes, int bs, int N, int nsplit, int partial_layout,
-                              const int* nvalid, hipStream_t st);
+                              const int* nvalid, hipStream_t st, int value_width = PDSC_CHANNELS);
+// value_width (both launchers): channels of V in the tile images and of the partials -- PDSC_CHANNELS, or 64 for the folded value
+// projection (pdsc_config.value_fold; point-fragment partials only)
 
 // leaf form (attention_split.hip, sc_attention_split_kernel<..., MG = true>): C leaf partials per query, left in `scratch` in
 // point-fragment order for the H3 layer kernel to merge
@@ -59,7 +61,7 @@ int attention_leaf_count(int N);
 void leaf_plan(int bs, int N, int leaves_mode, int* nw_out, int* nsplit_out, int* nleaf_out);
 int launch_attention_leaves(const void* q_split, const void* kv_tiles, const void* compat, int compat_format, long long ld,
                             void* scratch, size_t scratch_bytes, int bs, int N, int leaves_mode, const int* nvalid, int n_min,
-                            hipStream_t st);
+                            hipStream_t st, int value_width = PDSC_CHANNELS);
 
 // The three fused-layer entry points (pdsc_layer_fused_split / _frag_fmt / _frag_io: 18-24 arguments each) read the count
 // array from this thread-local slot when they fill LayerArgs; run_forward sets it for the duration of a ragged call and

@@ -44,6 +44,13 @@ constexpr int SPL_Q_LD = 2 * PDSC_CHANNELS;     // 16-bit elements per row of th
 
 __host__ __device__ __forceinline__ int spl_k_offset(int key, int chunk) { return (chunk << 9) + (key << 4); }    // chunk 0..15
 __host__ __device__ __forceinline__ int spl_v_offset(int ch, int jh) { return (jh << 11) + (ch << 4); }            // jh 0..3
+// value width VW (128, or 64 for the folded value projection V' = W1f Wv, pdsc_config.value_fold): the V^T planes are
+// [4 chunks of 8 keys][VW channels][16 B] (VW * 64 bytes each), K hi | K lo | V^T hi | V^T lo in one tile image; with VW = 64 the
+// image is 24 KiB, still SPL_TILE_STRIDE apart (the buffers keep their size)
+template <int VW> __host__ __device__ constexpr int spl_v_plane() { return 4 * VW * 16; }
+template <int VW> __host__ __device__ constexpr int spl_v_lo() { return SPL_VH + spl_v_plane<VW>(); }
+template <int VW> __host__ __device__ constexpr int spl_tile_bytes() { return SPL_VH + 2 * spl_v_plane<VW>(); }
+template <int VW> __host__ __device__ __forceinline__ int spl_v_offset_w(int ch, int jh) { return jh * (VW * 16) + (ch << 4); }
 __host__ __device__ __forceinline__ int spl_v_key(int jh, int e) { return 16 * (jh >> 1) + 8 * (e >> 2) + 4 * (jh & 1) + (e & 3); }
 
 __device__ __forceinline__ void split_sp16(float x, sp16& hi, sp16& lo) {

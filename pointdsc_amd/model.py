@@ -141,6 +141,12 @@ class PointDSC(nn.Module):
         # "per_launch" = one partial per key split of the launch plan (the r01-r04 bits: they move with the batch size, within the
         # contract; the fastest form); int 2..8: that many leaves (tuning)
         self.att_leaves = "canonical"
+        # fc_message's first conv folded into the value projection (enum pdsc_value_fold): 1 = the attention contracts P V' over
+        # 64 channels (V' = W1f Wv f, b' = W1f bv + b1f added after the merge) -- half the P V work, same three-MFMA split arithmetic;
+        # 0 = the 128-channel value path.  Applies with the split-precision attention and layer_gemm = "h3" only: the config
+        # carries 0 whenever the exact-fp32 attention (the range guard's fallback included) or the fp32 GEMMs run.  The library folds
+        # calls of up to N = 16384 correspondences (PDSC_VALUE_FOLD_MAX_N, include/pointdsc_hip.h); larger calls keep 128 channels.
+        self.value_fold = 1
         # fp16 range guard of the split-precision arithmetic (r06).  Every forward carries a device-side sentinel (workspace entry
         # "range_flag": one word per pair, set by any activation that reaches 65504 on its way into an fp16 hi / lo pair; the library
         # returns NaN poses for such pairs, never a plausible wrong motion).  What the MODULE does with it:
@@ -193,10 +199,13 @@ class PointDSC(nn.Module):
             leaves = ATT_LEAVES[self.att_leaves]
         else:
             raise ValueError(f"att_leaves must be one of {sorted(ATT_LEAVES)} or an int in [2, 8], got {self.att_leaves!r}")
+        if self.value_fold not in (0, 1) or isinstance(self.value_fold, float):
+            raise ValueError(f"value_fold must be 0 or 1, got {self.value_fold!r}")
+        fold = int(bool(self.value_fold) and self.attention_precision == "fp16x3" and self.layer_gemm == "h3")
         return _lib.PdscConfig(self.in_dim, self.num_layers, self.num_channels, self.num_iterations, self.k, 20,
                                float(self.inlier_threshold), float(self.nms_radius), float(refine_thr),
                                ATTENTION_PRECISIONS[self.attention_precision], COMPAT_FORMATS[self.compat_format],
-                               LAYER_GEMMS[self.layer_gemm], leaves)
+                               LAYER_GEMMS[self.layer_gemm], leaves, fold)
 
     # The packed buffer is rebuilt after anything that can change weights through the nn.Module API
     # (load_state_dict, .to()/.cuda()/.float(), train()); after editing parameters in place call
@@ -312,15 +321,18 @@ class PointDSC(nn.Module):
         """fp16 hi/lo split of the per-layer matrices for the split-precision GEMMs (pdsc_wsplit_build): built on the
         GPU from the packed buffer, once per packing."""
         pack = self.packed_weights(device)
+        cfg = self._config()
+        if self._wsplit is not None and cfg.value_fold and not getattr(self, "_wsplit_fold", 0):
+            self._wsplit = None                 # built without the folded sections (enum pdsc_value_fold): rebuild with them
         if self._wsplit is None:
             lib = _lib.load()
-            cfg = self._config()
             nb = int(lib.pdsc_wsplit_bytes(C.byref(cfg)))
             wsplit = torch.empty(max(nb, 16), dtype=torch.uint8, device=pack.device)
             with torch.cuda.device(pack.device):
                 _lib.check(lib.pdsc_wsplit_build(C.byref(cfg), C.c_void_p(pack.data_ptr()), C.c_void_p(wsplit.data_ptr()) if wsplit is not None else None,
                                                  torch.cuda.current_stream().cuda_stream), "pdsc_wsplit_build")
             self._wsplit = wsplit
+            self._wsplit_fold = int(cfg.value_fold)
         return self._wsplit
 
     def _get_workspace(self, nbytes: int, device) -> torch.Tensor:
