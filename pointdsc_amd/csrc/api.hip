@@ -15,16 +15,6 @@ namespace pdsc {
 
 static thread_local char g_err[512] = "";
 
-const int*& layer_nvalid_slot() {
-    static thread_local const int* slot = nullptr;
-    return slot;
-}
-
-unsigned int*& range_flag_slot() {
-    static thread_local unsigned int* slot = nullptr;
-    return slot;
-}
-
 // where the NEXT forward of this thread also reports its range words: pinned, device-mapped host memory ([bs] u32), or NULL
 static unsigned int*& range_report_slot() {
     static thread_local unsigned int* slot = nullptr;
@@ -377,6 +367,88 @@ extern "C" int pdsc_profile_read(int kind, double* total_ms, int* launches) {
         if (rc__ != PDSC_OK) return rc__; \
     } while (0)
 
+// Everything the encoder loop of run_forward needs to know, decided once by plan_encoder (pure host code, no launch in it).
+struct EncoderPlan {
+    bool fused;              // one launch per (tail of layer i, head of layer i + 1); false: one pdsc_linear launch per conv
+    bool split;              // split-precision attention; every field below but `kernel` is set for the fused split path only
+    LayerKernel kernel;      // the fused-layer kernel of every launch (x3: pdsc_layer_fused_x3, which merges like the wavefront kernel)
+    bool x3, frag;           // layer weights: split fp16 (PDSC_ATT_FP16X3_ALL) / fragment streams / else natural layout
+    bool fuse_merge;         // the layer kernel merges the key-split partials while loading (no combine launch, no msg round trip)
+    bool pf, leaves, fold;   // point-fragment hand-offs; attention in leaf form; the folded layer (64-channel value projection)
+    int gemm;                // arithmetic of fc1..fc3 / PointCN (enum pdsc_layer_gemm)
+    int ns, Npad;            // key split of the attention launch, padded row count of the partials
+    int nleaf, value_width;  // leaves per query (leaf form); channels of V and of the partials
+    int ws_tail, ws_head;    // sections of the split-weight buffer that hold the fragment streams
+};
+
+static int plan_encoder(const pdsc_config* cfg, int bs, int N, const int* nvalid, int n_min, EncoderPlan* plan) {
+    EncoderPlan& p = *plan = EncoderPlan{};
+    p.split = cfg->attention_precision != PDSC_ATT_FP32;
+    p.x3 = cfg->attention_precision == PDSC_ATT_FP16X3_ALL;
+    p.fused = env_int("PDSC_FUSED_LAYERS", 1) != 0 && cfg->num_layers > 0;     // tuning/A-B knob: 0 = one pdsc_linear launch per conv
+    const bool canonical = cfg->att_leaves >= PDSC_LEAVES_CANONICAL;
+    const int min_tiles = (n_min + 31) / 32;         // 32-key tiles of the shortest pair (ragged batches)
+    p.ns = p.split ? pdsc_attention_split_default_split(bs, N) : 0;
+#define PDSC_REQUIRE_SHORTEST_PAIR(cond)                                                                                             \
+    PDSC_REQUIRE(cond, "pdsc_forward_testing_ragged: the shortest pair (%d correspondences) has fewer 32-key tiles than the key split " \
+                 "planned for bs=%d, N=%d (%d): batch pairs of more similar size", n_min, bs, N, p.ns)
+    // Every pair must keep at least one tile per key split.  Two checks, because they do not reject the same calls.  This one
+    // alone catches the un-fused path (PDSC_FUSED_LAYERS = 0, or no layers): whatever the layer kernels, a configuration without
+    // canonical leaves runs the key split ...
+    if (nvalid && p.split && !canonical) PDSC_REQUIRE_SHORTEST_PAIR(min_tiles >= p.ns);
+    // the workgroup-per-tile / wavefront kernel over natural-layout weights, by the size rule (pdsc_layer_prefers_block);
+    // (experiments builds) PDSC_LAYER_VARIANT = b / w forces one
+    const char* var = env_str("PDSC_LAYER_VARIANT");
+    const bool force_block = var && var[0] == 'b', force_wave = var && var[0] == 'w';
+    auto by_size = [&](int pairs, int rows) {
+        return force_block || (!force_wave && pdsc_layer_prefers_block(pairs, rows)) ? LayerKernel::Block : LayerKernel::Wave;
+    };
+    if (!p.fused || !p.split) {
+        // exact fp32 sees the batch as ONE run of bs * N independent rows (see run_forward)
+        p.kernel = by_size(1, bs * N);
+        return PDSC_OK;
+    }
+    // split precision: head of layer 0, then per layer attention (partials left un-merged when the keys are split)
+    // + ONE launch for the merge, the tail of layer i and the head of layer i+1
+    p.Npad = (int)round_up(N, 256);
+    // arithmetic of fc1..fc3 / PointCN (enum pdsc_layer_gemm); A/B knob PDSC_LAYER_GEMM = 0 / 1 overrides
+    p.gemm = env_int("PDSC_LAYER_GEMM", cfg->layer_gemm) == PDSC_LAYER_GEMM_H3 ? PDSC_LAYER_GEMM_H3 : PDSC_LAYER_GEMM_F32;
+    const bool h3 = p.gemm == PDSC_LAYER_GEMM_H3;
+    // Which layer kernel.  H3 GEMMs: layer_h3_kernel, or the bit-identical layer_h3_coop_kernel for launches of at most 2560
+    // tiles (launch_layer_h3 decides) -- never the fp32 kernels: N = 1000 x 1 0.384 ms per forward against 0.557 with the
+    // workgroup-per-tile fp32 kernel (profiles/r03_b_ab_*.txt, r03_k_ab_coop.txt).  fp32 GEMMs: layer_wave_kernel over the
+    // fragment streams, or the workgroup-per-tile kernel of layer.hip over natural-layout weights for small problems.
+    // tuning/A-B knobs: PDSC_LAYER_FRAG = 0 = natural-layout weights whatever the size; PDSC_LAYER_H3_VARIANT = 0 = layer_wave_kernel
+    // with the H3 GEMMs
+    const LayerKernel natural = by_size(bs, N);
+    p.frag = env_int("PDSC_LAYER_FRAG", 1) && !p.x3 && !force_block && (natural == LayerKernel::Wave || h3);
+    p.kernel = p.x3     ? LayerKernel::Wave
+               : !p.frag ? natural
+                         : h3 && env_int("PDSC_LAYER_H3_VARIANT", 1) != 0 ? LayerKernel::H3 : LayerKernel::Wave;
+    // the layer kernels merge the key-split partials while loading (merge_partials.h), up to the limit of the kernel chosen
+    p.fuse_merge = env_int("PDSC_FUSE_MERGE", 1) && p.ns > 1 && p.ns <= layer_merge_limit(p.kernel);      // tuning/A-B knob
+    // H3 kernel: the hand-offs attention -> layer kernel -> next layer kernel can go in point-fragment order (split_layout.h);
+    // A/B knob PDSC_LAYER_PF = 0: plain rows
+    const bool pf_ok = p.kernel == LayerKernel::H3 && env_int("PDSC_LAYER_PF", 1) != 0;
+    // leaf form (r05, enum pdsc_att_leaves): the key range cut into leaves that depend on N alone; the H3 layer kernel merges the
+    // leaf partials exactly as it merges key-split partials (the other layer kernels keep the per-launch key split)
+    int lf_ns = 0, lf_nw = 0;
+    if (canonical) leaf_plan(bs, N, cfg->att_leaves, &lf_nw, &lf_ns, &p.nleaf);
+    p.leaves = pf_ok && canonical && (!nvalid || min_tiles >= 2 * p.nleaf);
+    // ... and this one alone catches a canonical-leaves configuration whose launch ends up not using the leaves
+    if (nvalid && !p.leaves) PDSC_REQUIRE_SHORTEST_PAIR(min_tiles >= p.ns);
+#undef PDSC_REQUIRE_SHORTEST_PAIR
+    p.pf = p.leaves || (pf_ok && p.fuse_merge);
+    // value fold (enum pdsc_value_fold): fc1 inside the value projection -- 64-channel V', partials and P V' on the point-fragment
+    // hand-offs (leaves and key splits of 2..8) up to N = PDSC_VALUE_FOLD_MAX_N (a function of N alone, so canonical leaves stay
+    // batch invariant); the row-order hand-offs and larger N keep the 128-channel path
+    p.fold = cfg->value_fold == PDSC_VALUE_FOLD_ON && p.pf && N <= PDSC_VALUE_FOLD_MAX_N;
+    p.value_width = p.fold ? PDSC_CHANNELS / 2 : PDSC_CHANNELS;
+    p.ws_tail = p.fold ? PDSC_WS_FOLD_TAIL_H3 : h3 ? PDSC_WS_FRAG_TAIL_H3 : PDSC_WS_FRAG_TAIL;
+    p.ws_head = p.fold ? PDSC_WS_FOLD_HEAD_H3 : h3 ? PDSC_WS_FRAG_HEAD_H3 : PDSC_WS_FRAG_HEAD;
+    return PDSC_OK;
+}
+
 // mode 0 = testing forward; mode 1 = validation forward (no 'testing' key, module in eval mode): feature similarity
 // matrix M, seeds = top-S by confidence (no NMS), batch-wide power-iteration exit, no refinement, labels = logits
 // nvalid / svalid (device, [bs]) != NULL: ragged batch (ragged.h) -- N and num_seeds are then those of the longest pair,
@@ -389,13 +461,6 @@ static int run_forward(int mode, const pdsc_config* cfg, const float* wpack, con
     if (!config_ok(cfg)) return PDSC_ERR_ARG;
     PDSC_REQUIRE(!tail_stream || (ev_fork && ev_join && tail_stream != stream),
                  "pdsc_forward_testing_streams: a tail stream (different from the main stream) needs the fork and join events");
-    struct SlotGuard {       // the fused-layer entry points read the count array from the thread-local slot (ragged.h)
-        explicit SlotGuard(const int* p) { layer_nvalid_slot() = p; }
-        ~SlotGuard() { layer_nvalid_slot() = nullptr; }
-    } slot_guard(nvalid);
-    struct RangeGuard {      // ... and the range sentinel's flag array (pdsc_common.h)
-        ~RangeGuard() { range_flag_slot() = nullptr; }
-    } range_guard;
     hipStream_t hst = (hipStream_t)stream;
     if (nvalid) {
         PDSC_REQUIRE(mode == 0 && svalid, "pdsc_forward_testing_ragged: testing forward only, both count arrays needed");
@@ -405,10 +470,6 @@ static int run_forward(int mode, const pdsc_config* cfg, const float* wpack, con
         PDSC_REQUIRE(n_min > (cfg->k < N - 1 ? cfg->k : N - 1), "pdsc_forward_testing_ragged: the shortest pair (%d correspondences) has no "
                      "more than k=%d: the reference clamps k per pair (k = min(k, num_corr - 1)); run such a pair in its own call",
                      n_min, cfg->k < N - 1 ? cfg->k : N - 1);
-        PDSC_REQUIRE(cfg->attention_precision == PDSC_ATT_FP32 || cfg->att_leaves >= PDSC_LEAVES_CANONICAL ||
-                     (n_min + 31) / 32 >= pdsc_attention_split_default_split(bs, N),
-                     "pdsc_forward_testing_ragged: the shortest pair (%d correspondences) has fewer 32-key tiles than the key split "
-                     "planned for bs=%d, N=%d (%d): batch pairs of more similar size", n_min, bs, N, pdsc_attention_split_default_split(bs, N));
     }
     PDSC_REQUIRE(wpack && corr_pos && src && tgt && final_trans && final_labels && workspace,
                  "pdsc_forward_testing: null pointer");
@@ -416,6 +477,8 @@ static int run_forward(int mode, const pdsc_config* cfg, const float* wpack, con
     PDSC_REQUIRE(num_seeds >= 1 && num_seeds <= N,
                  "pdsc_forward_testing: num_seeds=%d (int(N*ratio) must be >= 1; the reference fails on an empty seed set)",
                  num_seeds);
+    EncoderPlan plan;
+    PDSC_TRY(plan_encoder(cfg, bs, N, nvalid, n_min, &plan));
     const WsLayout L = make_layout(cfg, bs, N, num_seeds);
     if (workspace_bytes < L.total) {
         set_error("pdsc_forward_testing: workspace %zu < %zu bytes", workspace_bytes, L.total);
@@ -436,16 +499,15 @@ static int run_forward(int mode, const pdsc_config* cfg, const float* wpack, con
     int *seeds = I("seeds"), *knn_idx = I("knn_idx"), *counts = I("counts"), *best = I("best"), *solves = I("solves");
     unsigned int* conv_mask = (unsigned int*)(ws + L.find("conv_mask"));
     void* att_scratch = ws + L.find("att_scratch");
-    const bool split = cfg->attention_precision != PDSC_ATT_FP32;
-    const bool x3_gemm = cfg->attention_precision == PDSC_ATT_FP16X3_ALL;
+    const bool split = plan.split;
     PDSC_REQUIRE(!split || wsplit, "pdsc_forward_testing: the split-precision modes need the split-weight buffer (pdsc_wsplit_build)");
     auto WS = [&](int section, int layer) { return (const void*)((const unsigned short*)wsplit + pdsc_wsplit_offset(cfg, section, layer)); };
     const size_t att_bytes = L.bytes_of("att_scratch");
     void* q_split = split ? ws + L.find("q_split") : nullptr;
     void* kv_tiles = split ? ws + L.find("kv_tiles") : nullptr;
-    // fp16 range sentinel: zeroed by the layer0 launch, set by the layer kernels' conversion sites, read by the refinement launch
+    // fp16 range sentinel: zeroed by the layer0 launch, set by the layer kernels' conversion sites (LayerArgs.range_flag), read by
+    // the refinement launch
     unsigned int* range_flag = split && !probe ? (unsigned int*)(ws + L.find("range_flag")) : nullptr;
-    range_flag_slot() = range_flag;
 
     // Step 1 (models/PointDSC.py:150-155): compat, then the SCNonlocal encoder
     const bool compat16 = split && cfg->compat_format == PDSC_COMPAT_U16;
@@ -459,127 +521,76 @@ static int run_forward(int mode, const pdsc_config* cfg, const float* wpack, con
     };
     PDSC_TRY(launch_layer0(corr_pos, cfg->in_dim, W(PDSC_W_LAYER0_W, 0), W(PDSC_W_LAYER0_B, 0), featA, M, range_flag, bs, hst));
     // probe != NULL (pdsc_encoder_range_probe): one launch per conv, every intermediate in the workspace, |max| of each kind recorded
-    const int fused = probe ? 0 : env_int("PDSC_FUSED_LAYERS", 1);          // tuning/A-B knob: 0 = one pdsc_linear launch per conv
     auto P = [&](int kind, const float* x, size_t count) { return probe ? launch_absmax(x, count, probe + kind, hst) : PDSC_OK; };
     PDSC_TRY(P(PDSC_RANGE_LAYER0, featA, (size_t)M * C));
-    if (fused && cfg->num_layers > 0 && split) {
-        // split precision: head of layer 0, then per layer attention (partials left un-merged when the keys are split)
-        // + ONE launch for the merge, the tail of layer i and the head of layer i+1
-        const int ns = pdsc_attention_split_default_split(bs, N);
-        const int Npad = (int)round_up(N, 256);
-        const int fuse_env = env_int("PDSC_FUSE_MERGE", 1);      // tuning/A-B knob
-        // the layer kernels merge the key-split partials while loading (merge_partials.h): up to 4 splits, 8 in the
-        // workgroup-per-tile kernel that small problems take
-        const char* var = env_str("PDSC_LAYER_VARIANT");          // (experiments builds) b / w: force the workgroup-per-tile / wavefront kernel
-        // arithmetic of fc1..fc3 / PointCN (enum pdsc_layer_gemm); A/B knob PDSC_LAYER_GEMM = 0 / 1 overrides
-        const int gemm = env_int("PDSC_LAYER_GEMM", cfg->layer_gemm) == PDSC_LAYER_GEMM_H3 ? PDSC_LAYER_GEMM_H3 : PDSC_LAYER_GEMM_F32;
-        // Which layer kernel.  H3 GEMMs: layer_h3_kernel, or the bit-identical layer_h3_coop_kernel for launches of at most 2560
-        // tiles (launch_layer_h3 decides) -- never the fp32 kernels: N = 1000 x 1 0.384 ms per forward against 0.557 with the
-        // workgroup-per-tile fp32 kernel (profiles/r03_b_ab_*.txt, r03_k_ab_coop.txt).  fp32 GEMMs: layer_wave_kernel, or the
-        // workgroup-per-tile kernel of layer.hip for small problems (pdsc_layer_prefers_block).
-        const bool small = pdsc_layer_prefers_block(bs, N) && gemm != PDSC_LAYER_GEMM_H3;
-        const bool block_layer = !x3_gemm && ((var && var[0] == 'b') || (!(var && var[0] == 'w') && small));
-        // tuning/A-B knob: PDSC_LAYER_FRAG = 0 = natural-layout weights (pdsc_layer_fused_split)
-        const bool frag_env = env_int("PDSC_LAYER_FRAG", 1) && !(var && var[0] == 'b');
-        const bool frag = frag_env && !x3_gemm && ((var && var[0] == 'w') || !small);
-        // (merge_partials.h: 4 splits in layer_wave.hip, 8 in the workgroup-per-tile kernel and in layer_h3.hip)
-        const bool h3_kernel = frag && gemm == PDSC_LAYER_GEMM_H3 && env_int("PDSC_LAYER_PF", 1) != 0 && env_int("PDSC_LAYER_H3_VARIANT", 1) != 0;
-        const bool fuse_merge = fuse_env && ns > 1 && ns <= ((block_layer || h3_kernel) ? 8 : 4);
-        const float* part_o = fuse_merge ? (const float*)att_scratch : nullptr;
-        const float* part_ml = fuse_merge ? part_o + (size_t)bs * ns * Npad * C : nullptr;
-        const int ws_tail = gemm == PDSC_LAYER_GEMM_H3 ? PDSC_WS_FRAG_TAIL_H3 : PDSC_WS_FRAG_TAIL;
-        const int ws_head = gemm == PDSC_LAYER_GEMM_H3 ? PDSC_WS_FRAG_HEAD_H3 : PDSC_WS_FRAG_HEAD;
-        // H3 + fused merge: the hand-offs attention -> layer kernel -> next layer kernel in point-fragment order (split_layout.h);
-        // A/B knob PDSC_LAYER_PF = 0: plain rows
-        // leaf form (r05, enum pdsc_att_leaves): the key range cut into leaves that depend on N alone; the H3 layer kernel merges the
-        // leaf partials exactly as it merges key-split partials (the other layer kernels keep the per-launch key split)
-        const bool pf_ok = frag && gemm == PDSC_LAYER_GEMM_H3 && env_int("PDSC_LAYER_PF", 1) != 0 && env_int("PDSC_LAYER_H3_VARIANT", 1) != 0;
-        int lf_ns = 0, lf_leaves = 0, lf_nw = 0;
-        if (cfg->att_leaves >= PDSC_LEAVES_CANONICAL) leaf_plan(bs, N, cfg->att_leaves, &lf_nw, &lf_ns, &lf_leaves);
-        const bool leaves = pf_ok && cfg->att_leaves >= PDSC_LEAVES_CANONICAL && (!nvalid || (n_min + 31) / 32 >= 2 * lf_leaves);
-        if (nvalid && !leaves)
-            PDSC_REQUIRE((n_min + 31) / 32 >= pdsc_attention_split_default_split(bs, N),
-                         "pdsc_forward_testing_ragged: the shortest pair (%d correspondences) has fewer 32-key tiles than the key split "
-                         "planned for bs=%d, N=%d (%d): batch pairs of more similar size", n_min, bs, N, pdsc_attention_split_default_split(bs, N));
-        const bool pf = leaves || (pf_ok && fuse_merge);
-        // value fold (enum pdsc_value_fold): fc1 inside the value projection -- 64-channel V', partials and P V' on the point-fragment
-        // hand-offs (leaves and key splits of 2..8) up to N = PDSC_VALUE_FOLD_MAX_N (a function of N alone, so canonical leaves stay
-        // batch invariant); the row-order hand-offs and larger N keep the 128-channel path
-        const bool fold = cfg->value_fold == PDSC_VALUE_FOLD_ON && pf && !x3_gemm && N <= PDSC_VALUE_FOLD_MAX_N;
-        const int vw = fold ? C / 2 : C;
-        const int pf_tail = fold ? PDSC_WS_FOLD_TAIL_H3 : ws_tail, pf_head = fold ? PDSC_WS_FOLD_HEAD_H3 : ws_head;
-        const float* part_ml_pf = pf && !leaves ? part_o + (size_t)bs * ns * Npad * vw : part_ml;
-        const float* lf_o = (const float*)att_scratch;
-        const float* lf_ml = lf_o + (size_t)bs * lf_leaves * Npad * vw;
-        if (x3_gemm)
-            PDSC_TRY(pdsc_layer_fused_x3(nullptr, nullptr, nullptr, 0, 0, nullptr, featA, nullptr, featB, nullptr, q_split, kv_tiles,
-                                         nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, WS(PDSC_W_PCN_W, 0), W(PDSC_W_PCN_B, 0),
-                                         WS(PDSC_W_QKV_W, 0), W(PDSC_W_QKV_B, 0), bs, N, stream));
-        else if (pf)
-            PDSC_TRY(layer_fused_frag_io(nullptr, nullptr, nullptr, 0, 0, nullptr, featA, nullptr, featB, q_split, kv_tiles,
-                                         nullptr, WS(pf_head, 0), gemm, PDSC_IO_FEATB_PF, bs, N, hst, fold));
-        else if (frag)
-            PDSC_TRY(pdsc_layer_fused_frag_fmt(nullptr, nullptr, nullptr, 0, 0, nullptr, featA, nullptr, featB, nullptr, q_split, kv_tiles,
-                                               nullptr, WS(ws_head, 0), gemm, bs, N, stream));
-        else
-            PDSC_TRY(pdsc_layer_fused_split(nullptr, nullptr, nullptr, 0, 0, nullptr, featA, nullptr, featB, nullptr, q_split, kv_tiles,
-                                            nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, W(PDSC_W_PCN_W, 0), W(PDSC_W_PCN_B, 0),
-                                            W(PDSC_W_QKV_W, 0), W(PDSC_W_QKV_B, 0), WS(PDSC_W_QKV_W, 0), bs, N, stream));
+    if (plan.fused && !probe) {
+        // head of layer 0, then per layer: attention + ONE launch for the merge of the key-split partials (when they are left
+        // un-merged), the tail of layer i and the head of layer i+1
+        const bool parts = plan.pf || plan.fuse_merge;
+        const int nparts = plan.leaves ? plan.nleaf : plan.ns;
+        const float* part_o = parts ? (const float*)att_scratch : nullptr;
+        const float* part_ml = parts ? part_o + (size_t)bs * nparts * plan.Npad * plan.value_width : nullptr;
+        // tail of layer i (i = -1: none, the input is featA) and head of layer i+1 (last: none, the result is featA)
+        auto layer_x3 = [&](int i, bool last, const float* cur, float* nxt) -> int {      // (experiments builds: layer_split.hip)
+            const bool tail = i >= 0, head = !last;
+            return pdsc_layer_fused_x3(tail && !parts ? msg : nullptr, tail ? part_o : nullptr, tail ? part_ml : nullptr, tail ? nparts : 0,
+                                       tail ? plan.Npad : 0, tail ? cur : nullptr, tail ? nullptr : featA, last ? featA : nullptr,
+                                       head ? nxt : nullptr, nullptr, head ? q_split : nullptr, head ? kv_tiles : nullptr,
+                                       tail ? WS(PDSC_W_FC1_W, i) : nullptr, tail ? W(PDSC_W_FC1_B, i) : nullptr,
+                                       tail ? WS(PDSC_W_FC2_W, i) : nullptr, tail ? W(PDSC_W_FC2_B, i) : nullptr,
+                                       tail ? WS(PDSC_W_FC3_W, i) : nullptr, tail ? W(PDSC_W_FC3_B, i) : nullptr,
+                                       head ? WS(PDSC_W_PCN_W, i + 1) : nullptr, head ? W(PDSC_W_PCN_B, i + 1) : nullptr,
+                                       head ? WS(PDSC_W_QKV_W, i + 1) : nullptr, head ? W(PDSC_W_QKV_B, i + 1) : nullptr, bs, N, stream);
+        };
+        auto layer = [&](int i, bool last, const float* cur, float* nxt) -> int {
+            if (plan.x3) return layer_x3(i, last, cur, nxt);
+            const bool tail = i >= 0, head = !last;
+            // exact fp32: the batch is ONE run of M independent rows (bs = 1, N = M), so the per-pair counts of a ragged batch do
+            // not describe it (with them the kernel took counts[0] for the row count of the whole batch).  Padding rows are computed
+            // like any row; nothing valid reads them.
+            LayerArgs a = layer_args_io(tail && !parts ? msg : nullptr, tail ? part_o : nullptr, tail ? part_ml : nullptr, tail ? nparts : 0,
+                                        tail ? plan.Npad : 0, tail ? cur : nullptr, tail ? nullptr : featA, last ? featA : nullptr,
+                                        head ? nxt : nullptr, head && !split ? qkv : nullptr, head ? q_split : nullptr,
+                                        head ? kv_tiles : nullptr, split ? bs : 1, split ? N : M);
+            a.nvalid = split ? nvalid : nullptr;
+            if (plan.frag) {
+                if (tail) a.wf_tail = (const unsigned char*)WS(plan.ws_tail, i);
+                if (head) a.wf_head = (const unsigned char*)WS(plan.ws_head, i + 1);
+                a.gemm_format = plan.gemm;
+            } else {
+                if (tail) {
+                    a.w1 = W(PDSC_W_FC1_W, i); a.b1 = W(PDSC_W_FC1_B, i); a.w2 = W(PDSC_W_FC2_W, i); a.b2 = W(PDSC_W_FC2_B, i);
+                    a.w3 = W(PDSC_W_FC3_W, i); a.b3 = W(PDSC_W_FC3_B, i);
+                }
+                if (head) {
+                    a.wp = W(PDSC_W_PCN_W, i + 1); a.bp = W(PDSC_W_PCN_B, i + 1); a.wq = W(PDSC_W_QKV_W, i + 1); a.bq = W(PDSC_W_QKV_B, i + 1);
+                    if (split) a.wq_split = (const sp16*)WS(PDSC_W_QKV_W, i + 1);
+                }
+            }
+            if (plan.pf) {       // (the table beside layer_args_io: the point-fragment route reports to the sentinel and takes no trace)
+                a.io_flags = (tail ? PDSC_IO_PARTIALS_PF | PDSC_IO_RES_PF : 0) | (head ? PDSC_IO_FEATB_PF : 0);
+                a.value_fold = plan.fold;
+                a.range_flag = range_flag;
+            } else
+                a.trace = pdsc_layer_trace_buffer();      // range_flag stays NULL here: wiring these routes is a follow-up of its own
+            PDSC_TRY(validate_layer_args(a, plan.kernel, "pdsc_forward_testing(layer)"));
+            return dispatch_layer(a, plan.kernel, hst);
+        };
+        const int cfmt = compat16 ? PDSC_COMPAT_U16 : PDSC_COMPAT_F32;
+        PDSC_TRY(layer(-1, false, nullptr, featB));
         float *cur = featB, *nxt = featC;
         for (int i = 0; i < cfg->num_layers; ++i) {
-            if (leaves)
-                PDSC_TRY(launch_attention_leaves(q_split, kv_tiles, compat, compat16 ? PDSC_COMPAT_U16 : PDSC_COMPAT_F32, ld, att_scratch,
-                                                 att_bytes, bs, N, cfg->att_leaves, nvalid, n_min, hst, vw));
-            else if (pf)
-                PDSC_TRY(launch_attention_split_ex(q_split, kv_tiles, compat, compat16 ? PDSC_COMPAT_U16 : PDSC_COMPAT_F32, ld, nullptr,
-                                                   att_scratch, att_bytes, bs, N, ns, PDSC_PARTIALS_PF, nvalid, hst, vw));
+            if (!split)
+                PDSC_TRY(launch_attention_fp32(qkv, compat, ld, msg, att_scratch, att_bytes, bs, N, 0, nvalid, hst));      // (r06: ragged batches too)
+            else if (plan.leaves)
+                PDSC_TRY(launch_attention_leaves(q_split, kv_tiles, compat, cfmt, ld, att_scratch, att_bytes, bs, N, cfg->att_leaves, nvalid,
+                                                 n_min, hst, plan.value_width));
+            else if (plan.pf)
+                PDSC_TRY(launch_attention_split_ex(q_split, kv_tiles, compat, cfmt, ld, nullptr, att_scratch, att_bytes, bs, N, plan.ns,
+                                                   PDSC_PARTIALS_PF, nvalid, hst, plan.value_width));
             else
-                PDSC_TRY(attention_split(fuse_merge ? nullptr : msg, ns));
-            const bool last = i + 1 == cfg->num_layers;
-            if (pf)
-                PDSC_TRY(layer_fused_frag_io(nullptr, leaves ? lf_o : part_o, leaves ? lf_ml : part_ml_pf, leaves ? lf_leaves : ns, Npad, cur, nullptr,
-                                             last ? featA : nullptr, last ? nullptr : nxt, last ? nullptr : q_split, last ? nullptr : kv_tiles,
-                                             WS(pf_tail, i), last ? nullptr : WS(pf_head, i + 1), gemm,
-                                             PDSC_IO_PARTIALS_PF | PDSC_IO_RES_PF | (last ? 0 : PDSC_IO_FEATB_PF), bs, N, hst, fold));
-            else if (x3_gemm)
-                PDSC_TRY(pdsc_layer_fused_x3(fuse_merge ? nullptr : msg, part_o, part_ml, ns, Npad, cur, nullptr, last ? featA : nullptr,
-                                             last ? nullptr : nxt, nullptr, last ? nullptr : q_split, last ? nullptr : kv_tiles,
-                                             WS(PDSC_W_FC1_W, i), W(PDSC_W_FC1_B, i), WS(PDSC_W_FC2_W, i), W(PDSC_W_FC2_B, i),
-                                             WS(PDSC_W_FC3_W, i), W(PDSC_W_FC3_B, i),
-                                             last ? nullptr : WS(PDSC_W_PCN_W, i + 1), last ? nullptr : W(PDSC_W_PCN_B, i + 1),
-                                             last ? nullptr : WS(PDSC_W_QKV_W, i + 1), last ? nullptr : W(PDSC_W_QKV_B, i + 1),
-                                             bs, N, stream));
-            else if (frag)
-                PDSC_TRY(pdsc_layer_fused_frag_fmt(fuse_merge ? nullptr : msg, part_o, part_ml, ns, Npad, cur, nullptr,
-                                                   last ? featA : nullptr, last ? nullptr : nxt, nullptr, last ? nullptr : q_split,
-                                                   last ? nullptr : kv_tiles, WS(ws_tail, i),
-                                                   last ? nullptr : WS(ws_head, i + 1), gemm, bs, N, stream));
-            else
-                PDSC_TRY(pdsc_layer_fused_split(fuse_merge ? nullptr : msg, part_o, part_ml, ns, Npad, cur, nullptr,
-                                                last ? featA : nullptr, last ? nullptr : nxt, nullptr, last ? nullptr : q_split,
-                                                last ? nullptr : kv_tiles,
-                                                W(PDSC_W_FC1_W, i), W(PDSC_W_FC1_B, i), W(PDSC_W_FC2_W, i), W(PDSC_W_FC2_B, i),
-                                                W(PDSC_W_FC3_W, i), W(PDSC_W_FC3_B, i),
-                                                last ? nullptr : W(PDSC_W_PCN_W, i + 1), last ? nullptr : W(PDSC_W_PCN_B, i + 1),
-                                                last ? nullptr : W(PDSC_W_QKV_W, i + 1), last ? nullptr : W(PDSC_W_QKV_B, i + 1),
-                                                last ? nullptr : WS(PDSC_W_QKV_W, i + 1), bs, N, stream));
-            float* tmp = cur; cur = nxt; nxt = tmp;
-        }
-    } else if (fused && cfg->num_layers > 0) {
-        // exact fp32: head of layer 0, then per layer: attention + (tail of layer i fused with head of layer i+1)
-        PDSC_TRY(pdsc_layer_fused(nullptr, nullptr, featA, nullptr, featB, qkv, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                  nullptr, W(PDSC_W_PCN_W, 0), W(PDSC_W_PCN_B, 0), W(PDSC_W_QKV_W, 0), W(PDSC_W_QKV_B, 0), M,
-                                  stream));
-        float *cur = featB, *nxt = featC;
-        for (int i = 0; i < cfg->num_layers; ++i) {
-            PDSC_TRY(launch_attention_fp32(qkv, compat, ld, msg, att_scratch, att_bytes, bs, N, 0, nvalid, hst));      // (r06: ragged batches too)
-            const bool last = i + 1 == cfg->num_layers;
-            PDSC_TRY(pdsc_layer_fused(msg, cur, nullptr, last ? featA : nullptr, last ? nullptr : nxt, last ? nullptr : qkv,
-                                      W(PDSC_W_FC1_W, i), W(PDSC_W_FC1_B, i), W(PDSC_W_FC2_W, i), W(PDSC_W_FC2_B, i),
-                                      W(PDSC_W_FC3_W, i), W(PDSC_W_FC3_B, i),
-                                      last ? nullptr : W(PDSC_W_PCN_W, i + 1), last ? nullptr : W(PDSC_W_PCN_B, i + 1),
-                                      last ? nullptr : W(PDSC_W_QKV_W, i + 1), last ? nullptr : W(PDSC_W_QKV_B, i + 1), M,
-                                      stream));
+                PDSC_TRY(attention_split(plan.fuse_merge ? nullptr : msg, plan.ns));
+            PDSC_TRY(layer(i, i + 1 == cfg->num_layers, cur, nxt));
             float* tmp = cur; cur = nxt; nxt = tmp;
         }
     } else

@@ -15,7 +15,6 @@
 #include "split_layout.h"
 #include "merge_partials.h"
 #include "layer_args.h"
-#include "ragged.h"
 
 namespace pdsc {
 
@@ -402,47 +401,83 @@ extern "C" int pdsc_layer_prefers_block(int bs, int N) {
     return (long long)bs * pdsc::ceil_div(N, pdsc::LF_ROWS) <= 288;
 }
 
+namespace pdsc {
+
+// Every check the fused-layer entry points make, once.  The weights come as fragment streams in the H3 kernel and, in the
+// wavefront kernel, when either stream is given; else in natural layout.
+int validate_layer_args(const LayerArgs& a, LayerKernel kernel, const char* who) {
+    const bool tail = a.msg != nullptr || a.part_o != nullptr, head = a.featB_out != nullptr;
+    const bool h3 = kernel == LayerKernel::H3;
+    const bool frag = h3 || (kernel == LayerKernel::Wave && (a.wf_tail || a.wf_head));
+    const int io = a.io_flags;
+    PDSC_REQUIRE(tail || head, "%s: neither tail (msg / partials) nor head (featB_out) requested", who);
+    PDSC_REQUIRE(a.bs > 0 && a.N > 0, "%s: bs=%d N=%d", who, a.bs, a.N);
+    PDSC_REQUIRE(a.gemm_format == PDSC_LAYER_GEMM_F32 || a.gemm_format == PDSC_LAYER_GEMM_H3, "%s: gemm_format=%d", who, a.gemm_format);
+    PDSC_REQUIRE((io & ~(PDSC_IO_PARTIALS_PF | PDSC_IO_RES_PF | PDSC_IO_FEATB_PF)) == 0, "%s: io_flags=%d", who, io);
+    PDSC_REQUIRE(h3 || (io == 0 && !a.value_fold), "%s: point-fragment hand-offs and the folded layer exist in the H3 kernel only", who);
+    PDSC_REQUIRE(!h3 || a.gemm_format == PDSC_LAYER_GEMM_H3, "%s: point-fragment hand-offs need gemm_format = PDSC_LAYER_GEMM_H3", who);
+    PDSC_REQUIRE(!a.value_fold || (io & PDSC_IO_PARTIALS_PF) || !tail, "%s: the folded layer merges point-fragment partials", who);
+    if (tail) {
+        PDSC_REQUIRE(a.res && (frag ? a.wf_tail != nullptr : a.w1 && a.b1 && a.w2 && a.b2 && a.w3 && a.b3),
+                     "%s: tail needs res and fc1..fc3 (natural layout or the tail stream)", who);
+        if (!a.msg) PDSC_REQUIRE(a.part_ml && a.nsplit >= 1 && a.nsplit <= layer_merge_limit(kernel) && a.Npad >= a.N,
+                                 "%s: partials need part_ml, 1 <= nsplit <= %d (what this launch's kernel merges), Npad >= N", who,
+                                 layer_merge_limit(kernel));
+        PDSC_REQUIRE(!(io & PDSC_IO_PARTIALS_PF) || (!a.msg && a.Npad % 32 == 0), "%s: PF partials come un-merged (msg NULL), Npad a multiple of 32", who);
+    } else {
+        PDSC_REQUIRE(a.feat_in, "%s: head-only needs feat_in", who);
+        PDSC_REQUIRE(!(io & (PDSC_IO_PARTIALS_PF | PDSC_IO_RES_PF)), "%s: head-only takes feat_in in row order", who);
+    }
+    if (head) PDSC_REQUIRE((a.qkv_out || a.qs) && (frag ? a.wf_head != nullptr : a.wp && a.bp && a.wq && a.bq),
+                           "%s: head needs qkv_out or the split streams, and pcn, qkv weights (natural layout or the head stream)", who);
+    else PDSC_REQUIRE(a.feat_out && !(io & PDSC_IO_FEATB_PF), "%s: tail-only needs feat_out (row order)", who);
+    PDSC_REQUIRE((a.qs == nullptr) == (a.kv == nullptr), "%s: q_split and kv_tiles go together", who);
+    PDSC_REQUIRE(!h3 || launch_layer_h3_fits(a, tail, head), "%s: output set not served by the H3 kernel (head: the split streams "
+                 "only; tail + head: no feat_out; tail only: feat_out)", who);
+    return PDSC_OK;
+}
+
+int dispatch_layer(const LayerArgs& a, LayerKernel kernel, hipStream_t st) {
+    const bool tail = a.msg != nullptr || a.part_o != nullptr, head = a.featB_out != nullptr;
+    if (kernel == LayerKernel::H3) {
+        LayerArgs h = a;       // (the start delay is the H3 kernel's alone)
+        h.stagger_cycles = env_int("PDSC_LAYER_STAGGER", 0);
+        h.stagger_mode = env_int("PDSC_LAYER_STAGGER_MODE", 1);
+        return launch_layer_h3(h, tail, head, st);
+    }
+    if (kernel == LayerKernel::Wave) return launch_layer_wave(a, tail, head, st);
+    if (tail && head) {
+        profile_mark_begin(PDSC_PROF_LAYER, st);
+        const int rc = launch_layer<true, true>(a, st);
+        profile_mark_end(PDSC_PROF_LAYER, st);
+        return rc;
+    }
+    if (tail) return launch_layer<true, false>(a, st);
+    return launch_layer<false, true>(a, st);
+}
+
+}  // namespace pdsc
+
 extern "C" int pdsc_layer_fused_split(const float* msg, const float* part_o, const float* part_ml, int nsplit, int Npad,
                                       const float* res, const float* feat_in, float* feat_out,
                                       float* featB_out, float* qkv_out, void* q_split, void* kv_tiles,
                                       const float* w1, const float* b1, const float* w2, const float* b2, const float* w3,
                                       const float* b3, const float* wp, const float* bp, const float* wq, const float* bq,
                                       const void* wq_split, int bs, int N, void* stream) {
-    const bool tail = msg != nullptr || part_o != nullptr, head = featB_out != nullptr;
-    PDSC_REQUIRE(tail || head, "pdsc_layer_fused: neither tail (msg / partials) nor head (featB_out) requested");
-    PDSC_REQUIRE(bs > 0 && N > 0, "pdsc_layer_fused: bs=%d N=%d", bs, N);
-    if (tail) {
-        PDSC_REQUIRE(res && w1 && b1 && w2 && b2 && w3 && b3, "pdsc_layer_fused: tail needs res, fc1..fc3");
-        if (!msg) PDSC_REQUIRE(part_ml && nsplit >= 1 && nsplit <= pdsc::MERGE_MAX_SPLIT_BLOCK && Npad >= N,
-                               "pdsc_layer_fused: partials need part_ml, 1 <= nsplit <= %d, Npad >= N", pdsc::MERGE_MAX_SPLIT_BLOCK);
-    } else PDSC_REQUIRE(feat_in, "pdsc_layer_fused: head-only needs feat_in");
-    if (head) PDSC_REQUIRE((qkv_out || q_split) && wp && bp && wq && bq, "pdsc_layer_fused: head needs qkv_out or the split streams, pcn, qkv weights");
-    else PDSC_REQUIRE(feat_out, "pdsc_layer_fused: tail-only needs feat_out");
-    PDSC_REQUIRE((q_split == nullptr) == (kv_tiles == nullptr), "pdsc_layer_fused: q_split and kv_tiles go together");
-    pdsc::LayerArgs a{msg, part_o, part_ml, nsplit, Npad, res, feat_in, feat_out, featB_out, qkv_out, w1, b1, w2, b2, w3, b3,
-                      wp, bp, wq, bq, (const sp16*)wq_split, (sp16*)q_split, (unsigned char*)kv_tiles, N, bs, nullptr, nullptr, PDSC_LAYER_GEMM_F32, 0, 0, 0, g_layer_trace};
-    a.nvalid = pdsc::layer_nvalid_slot();
-    hipStream_t st = (hipStream_t)stream;
+    pdsc::LayerArgs a = pdsc::layer_args_io(msg, part_o, part_ml, nsplit, Npad, res, feat_in, feat_out, featB_out, qkv_out, q_split,
+                                            kv_tiles, bs, N);
+    a.w1 = w1; a.b1 = b1; a.w2 = w2; a.b2 = b2; a.w3 = w3; a.b3 = b3;
+    a.wp = wp; a.bp = bp; a.wq = wq; a.bq = bq; a.wq_split = (const sp16*)wq_split;
+    a.trace = g_layer_trace;
     // Two implementations.  layer_wave.hip (one wavefront per 32-point tile) wins once the tiles fill the chip; with few
     // tiles its serial 46k matrix-pipe cycles per tile are the launch time, and this file's kernel, which spreads a tile
     // over the four SIMDs of a CU, is faster (N = 1000, one pair: 0.68 vs 1.10 ms per forward).
     // PDSC_LAYER_VARIANT = block | wave overrides the size rule.
     const char* ev = pdsc::env_str("PDSC_LAYER_VARIANT");          // experiments builds only
-    const int variant = !ev ? 0 : ev[0] == 'b' ? 1 : ev[0] == 'w' ? 2 : 0;
-    const bool block_variant = variant == 1 || (variant == 0 && pdsc_layer_prefers_block(bs, N));
-    if (!block_variant) {
-        PDSC_REQUIRE(msg || !tail || nsplit <= pdsc::MERGE_MAX_SPLIT, "pdsc_layer_fused: the wavefront-per-tile kernel merges at most %d splits",
-                     pdsc::MERGE_MAX_SPLIT);
-        return pdsc::launch_layer_wave(a, tail, head, st);
-    }
-    if (tail && head) {
-        pdsc::profile_mark_begin(PDSC_PROF_LAYER, st);
-        const int rc = pdsc::launch_layer<true, true>(a, st);
-        pdsc::profile_mark_end(PDSC_PROF_LAYER, st);
-        return rc;
-    }
-    if (tail) return pdsc::launch_layer<true, false>(a, st);
-    return pdsc::launch_layer<false, true>(a, st);
+    const bool block = ev && (ev[0] == 'b' || ev[0] == 'w') ? ev[0] == 'b' : pdsc_layer_prefers_block(bs, N) != 0;
+    const pdsc::LayerKernel kernel = block ? pdsc::LayerKernel::Block : pdsc::LayerKernel::Wave;
+    const int rc = pdsc::validate_layer_args(a, kernel, "pdsc_layer_fused");
+    return rc != PDSC_OK ? rc : pdsc::dispatch_layer(a, kernel, (hipStream_t)stream);
 }
 
 extern "C" int pdsc_layer_fused(const float* msg, const float* res, const float* feat_in, float* feat_out,
@@ -450,14 +485,7 @@ extern "C" int pdsc_layer_fused(const float* msg, const float* res, const float*
                                 const float* b2, const float* w3, const float* b3, const float* wp, const float* bp,
                                 const float* wq, const float* bq, int M, void* stream) {
     if (featB_out) PDSC_REQUIRE(qkv_out, "pdsc_layer_fused: head needs qkv_out");
-    // this entry point sees the batch as ONE run of M independent rows (bs = 1, N = M): the per-pair counts of a ragged forward
-    // (layer_nvalid_slot) do not describe it -- with them in place the kernel took counts[0] for the row count of the whole batch
-    // (r06: the exact-fp32 path takes ragged batches now).  Padding rows are computed like any row; nothing valid reads them.
-    struct NoCounts {
-        const int* saved;
-        NoCounts() : saved(pdsc::layer_nvalid_slot()) { pdsc::layer_nvalid_slot() = nullptr; }
-        ~NoCounts() { pdsc::layer_nvalid_slot() = saved; }
-    } no_counts;
+    // this entry point sees the batch as ONE run of M independent rows (bs = 1, N = M)
     return pdsc_layer_fused_split(msg, nullptr, nullptr, 0, 0, res, feat_in, feat_out, featB_out, qkv_out, nullptr, nullptr,
                                   w1, b1, w2, b2, w3, b3, wp, bp, wq, bq, nullptr, 1, M, stream);
 }

@@ -2,6 +2,7 @@
 // 32-point tile, activations in LDS; layer_wave.hip: one wavefront per tile, activations in registers).
 #pragma once
 #include "pdsc_common.h"
+#include "merge_partials.h"
 
 namespace pdsc {
 
@@ -39,17 +40,50 @@ struct LayerArgs {
                              // skipped, its last tile is padded / zeroed from ITS count; NULL = every pair has N rows
 };
 
+// Which of the three fused-layer kernels a launch takes: the workgroup-per-tile kernel of layer.hip (natural-layout weights), the
+// wavefront-per-tile kernel of layer_wave.hip (natural weights or fragment streams) or the pipelined H3 kernel of layer_h3.hip
+// (H3 fragment streams; launch_layer_h3 hands launches of few tiles to layer_coop.hip itself).
+enum class LayerKernel { Block, Wave, H3 };
+// key-split partials the kernel merges while it loads (merge_partials.h); larger splits go through attention_combine_kernel
+constexpr int layer_merge_limit(LayerKernel k) {
+    return k == LayerKernel::Block ? MERGE_MAX_SPLIT_BLOCK : k == LayerKernel::H3 ? MERGE_MAX_SPLIT_H3 : MERGE_MAX_SPLIT;
+}
+
+// The input / output fields every route fills the same way; the weights and the fields below are the caller's.  They differ by
+// route, and the differences decide which kernel runs:
+//   route                         weights             trace              range_flag      io_flags / value_fold   wq_split
+//   natural (pdsc_layer_fused*)   w1..bq              pdsc_layer_trace   NULL            0 / 0                   optional
+//   fragment rows (_frag_fmt)     wf_tail / wf_head   pdsc_layer_trace   NULL            0 / 0                   --
+//   point fragments (_frag_io)    wf_tail / wf_head   NULL               forward's flag  caller's                --
+// (trace: launch_layer_h3 leaves the few-tile kernel of layer_coop.hip when it is set, and the product build's launch_layer_wave
+// rejects a launch with it.  range_flag: only the point-fragment route reports to the fp16 range sentinel so far; wiring the other
+// launchers is a follow-up with a test of its own.  nvalid / range_flag are NULL outside a forward.)
+inline LayerArgs layer_args_io(const float* msg, const float* part_o, const float* part_ml, int nsplit, int Npad, const float* res,
+                               const float* feat_in, float* feat_out, float* featB_out, float* qkv_out, void* q_split, void* kv_tiles,
+                               int bs, int N) {
+    LayerArgs a{};
+    a.msg = msg; a.part_o = part_o; a.part_ml = part_ml; a.nsplit = nsplit; a.Npad = Npad;
+    a.res = res; a.feat_in = feat_in; a.feat_out = feat_out; a.featB_out = featB_out; a.qkv_out = qkv_out;
+    a.qs = (sp16*)q_split; a.kv = (unsigned char*)kv_tiles;
+    a.N = N; a.bs = bs;
+    a.gemm_format = PDSC_LAYER_GEMM_F32;
+    return a;
+}
+
+// layer.hip: every argument check of the fused-layer entry points (`who` names the caller in the error text), and the launch.
+// tail = msg or partials given, head = featB_out given.
+int validate_layer_args(const LayerArgs& a, LayerKernel kernel, const char* who);
+int dispatch_layer(const LayerArgs& a, LayerKernel kernel, hipStream_t st);
+
 int launch_layer_wave(const LayerArgs& a, bool tail, bool head, hipStream_t st);      // layer_wave.hip
 int launch_layer_h3(const LayerArgs& a, bool tail, bool head, hipStream_t st);        // layer_h3.hip (H3 fragment streams only)
 int launch_layer_h3_coop(const LayerArgs& a, bool tail, bool head, hipStream_t st);   // layer_coop.hip (same contract, few tiles)
 bool launch_layer_h3_fits(const LayerArgs& a, bool tail, bool head);                  // ... and only this output set
-// pdsc_layer_fused_frag_io with the folded layer selectable (value_fold = 1: the PDSC_WS_FOLD_*_H3 streams, 64-channel partials)
-int layer_fused_frag_io(const float* msg, const float* part_o, const float* part_ml, int nsplit, int Npad, const float* res,
-                        const float* feat_in, float* feat_out, float* featB_out, void* q_split, void* kv_tiles, const void* wfrag_tail,
-                        const void* wfrag_head, int gemm_format, int io_flags, int bs, int N, hipStream_t stream, int value_fold);
 // the folded layer's weights of one layer (layer_wave.hip): wfold = W1f Wv [64][128] | b' [64] fp32, and its H3 tail / head streams
 int build_value_fold(const float* w1, const float* b1, const float* wqkv, const float* bqkv, const float* w2, const float* b2,
                      const float* w3, const float* b3, const float* wp, const float* bp, float* wfold, void* tail_out, void* head_out,
                      hipStream_t st);
 
 }  // namespace pdsc
+
+long long* pdsc_layer_trace_buffer(void);      // layer.hip: the buffer of pdsc_layer_trace, or NULL

@@ -20,7 +20,6 @@
 #include "merge_partials.h"
 #include "layer_args.h"
 #include "layer_wave.h"
-#include "ragged.h"
 
 namespace pdsc {
 
@@ -487,8 +486,6 @@ int launch_layer_h3(const LayerArgs& a, bool tail, bool head, hipStream_t st) {
 
 using namespace pdsc;
 
-extern long long* pdsc_layer_trace_buffer(void);
-
 extern "C" int pdsc_layer_h3_uses_coop(int bs, int N) {
     if (bs <= 0 || N <= 0) return 0;
     int coop_tiles = PDSC_H3_COOP_TILES;
@@ -502,50 +499,13 @@ extern "C" int pdsc_layer_fused_frag_io(const float* msg, const float* part_o, c
                                         const float* res, const float* feat_in, float* feat_out, float* featB_out,
                                         void* q_split, void* kv_tiles, const void* wfrag_tail, const void* wfrag_head,
                                         int gemm_format, int io_flags, int bs, int N, void* stream) {
-    return pdsc::layer_fused_frag_io(msg, part_o, part_ml, nsplit, Npad, res, feat_in, feat_out, featB_out, q_split, kv_tiles, wfrag_tail,
-                                     wfrag_head, gemm_format, io_flags, bs, N, (hipStream_t)stream, PDSC_VALUE_FOLD_OFF);
-}
-
-int pdsc::layer_fused_frag_io(const float* msg, const float* part_o, const float* part_ml, int nsplit, int Npad, const float* res,
-                              const float* feat_in, float* feat_out, float* featB_out, void* q_split, void* kv_tiles,
-                              const void* wfrag_tail, const void* wfrag_head, int gemm_format, int io_flags, int bs, int N,
-                              hipStream_t stream, int value_fold) {
-    PDSC_REQUIRE(value_fold == PDSC_VALUE_FOLD_OFF || (io_flags & PDSC_IO_PARTIALS_PF) || !(msg || part_o),
-                 "pdsc_layer_fused_frag_io: the folded layer merges point-fragment partials");
-    if (io_flags == 0 && value_fold == PDSC_VALUE_FOLD_OFF)
+    if (io_flags == 0)       // no point-fragment hand-off: the fragment-rows route and its kernel rule
         return pdsc_layer_fused_frag_fmt(msg, part_o, part_ml, nsplit, Npad, res, feat_in, feat_out, featB_out, nullptr, q_split, kv_tiles,
                                          wfrag_tail, wfrag_head, gemm_format, bs, N, stream);
-    const bool tail = msg != nullptr || part_o != nullptr, head = featB_out != nullptr;
-    PDSC_REQUIRE(tail || head, "pdsc_layer_fused_frag_io: neither tail (msg / partials) nor head (featB_out) requested");
-    PDSC_REQUIRE(bs > 0 && N > 0, "pdsc_layer_fused_frag_io: bs=%d N=%d", bs, N);
-    PDSC_REQUIRE((io_flags & ~(PDSC_IO_PARTIALS_PF | PDSC_IO_RES_PF | PDSC_IO_FEATB_PF)) == 0, "pdsc_layer_fused_frag_io: io_flags=%d", io_flags);
-    PDSC_REQUIRE(gemm_format == PDSC_LAYER_GEMM_H3, "pdsc_layer_fused_frag_io: point-fragment hand-offs need gemm_format = PDSC_LAYER_GEMM_H3");
-    if (tail) {
-        PDSC_REQUIRE(res && wfrag_tail, "pdsc_layer_fused_frag_io: tail needs res and the tail stream");
-        if (!msg) PDSC_REQUIRE(part_ml && nsplit >= 1 && nsplit <= MERGE_MAX_SPLIT_H3 && Npad >= N,
-                               "pdsc_layer_fused_frag_io: partials need part_ml, 1 <= nsplit <= %d, Npad >= N", MERGE_MAX_SPLIT_H3);
-        PDSC_REQUIRE(!(io_flags & PDSC_IO_PARTIALS_PF) || (!msg && Npad % 32 == 0), "pdsc_layer_fused_frag_io: PF partials come un-merged (msg NULL), Npad a multiple of 32");
-    } else {
-        PDSC_REQUIRE(feat_in, "pdsc_layer_fused_frag_io: head-only needs feat_in");
-        PDSC_REQUIRE(!(io_flags & (PDSC_IO_PARTIALS_PF | PDSC_IO_RES_PF)), "pdsc_layer_fused_frag_io: head-only takes feat_in in row order");
-    }
-    if (head) PDSC_REQUIRE(q_split && kv_tiles && wfrag_head, "pdsc_layer_fused_frag_io: head needs the split streams and the head stream");
-    else PDSC_REQUIRE(feat_out && !(io_flags & PDSC_IO_FEATB_PF), "pdsc_layer_fused_frag_io: tail-only needs feat_out (row order)");
-    LayerArgs a{};
-    a.msg = msg; a.part_o = part_o; a.part_ml = part_ml; a.nsplit = nsplit; a.Npad = Npad;
-    a.res = res; a.feat_in = feat_in; a.feat_out = feat_out; a.featB_out = featB_out;
-    a.qs = (sp16*)q_split; a.kv = (unsigned char*)kv_tiles;
-    a.N = N; a.bs = bs;
+    LayerArgs a = layer_args_io(msg, part_o, part_ml, nsplit, Npad, res, feat_in, feat_out, featB_out, nullptr, q_split, kv_tiles, bs, N);
     a.wf_tail = (const unsigned char*)wfrag_tail; a.wf_head = (const unsigned char*)wfrag_head;
     a.gemm_format = gemm_format;
     a.io_flags = io_flags;
-    a.stagger_cycles = env_int("PDSC_LAYER_STAGGER", 0);
-    a.stagger_mode = env_int("PDSC_LAYER_STAGGER_MODE", 1);
-    a.trace = nullptr;
-    a.nvalid = layer_nvalid_slot();
-    a.range_flag = range_flag_slot();
-    a.value_fold = value_fold;
-    PDSC_REQUIRE(launch_layer_h3_fits(a, tail, head), "pdsc_layer_fused_frag_io: output set not served by the point-fragment kernel "
-                                                     "(tail + head: no feat_out; tail only: feat_out)");
-    return launch_layer_h3(a, tail, head, (hipStream_t)stream);
+    const int rc = validate_layer_args(a, LayerKernel::H3, "pdsc_layer_fused_frag_io");
+    return rc != PDSC_OK ? rc : dispatch_layer(a, LayerKernel::H3, (hipStream_t)stream);
 }

@@ -24,7 +24,6 @@
 #include "layer_args.h"
 
 #include "layer_wave.h"
-#include "ragged.h"
 
 namespace pdsc {
 
@@ -514,39 +513,20 @@ extern "C" int pdsc_wfrag_build_head(const float* wp, const float* bp, const flo
     return pdsc_wfrag_build_head_fmt(wp, bp, wq, bq, out, PDSC_LAYER_GEMM_F32, stream);
 }
 
-extern long long* pdsc_layer_trace_buffer(void);
-
 extern "C" int pdsc_layer_fused_frag_fmt(const float* msg, const float* part_o, const float* part_ml, int nsplit, int Npad,
                                          const float* res, const float* feat_in, float* feat_out, float* featB_out,
                                          float* qkv_out, void* q_split, void* kv_tiles, const void* wfrag_tail,
                                          const void* wfrag_head, int gemm_format, int bs, int N, void* stream) {
-    PDSC_REQUIRE(gemm_format == PDSC_LAYER_GEMM_F32 || gemm_format == PDSC_LAYER_GEMM_H3, "pdsc_layer_fused_frag: gemm_format=%d", gemm_format);
-    const bool tail = msg != nullptr || part_o != nullptr, head = featB_out != nullptr;
-    PDSC_REQUIRE(tail || head, "pdsc_layer_fused_frag: neither tail (msg / partials) nor head (featB_out) requested");
-    PDSC_REQUIRE(bs > 0 && N > 0, "pdsc_layer_fused_frag: bs=%d N=%d", bs, N);
-    if (tail) {
-        PDSC_REQUIRE(res && wfrag_tail, "pdsc_layer_fused_frag: tail needs res and the tail stream");
-        if (!msg) PDSC_REQUIRE(part_ml && nsplit >= 1 && nsplit <= MERGE_MAX_SPLIT && Npad >= N,
-                               "pdsc_layer_fused_frag: partials need part_ml, 1 <= nsplit <= %d, Npad >= N", MERGE_MAX_SPLIT);
-    } else PDSC_REQUIRE(feat_in, "pdsc_layer_fused_frag: head-only needs feat_in");
-    if (head) PDSC_REQUIRE((qkv_out || q_split) && wfrag_head, "pdsc_layer_fused_frag: head needs qkv_out or the split streams, and the head stream");
-    else PDSC_REQUIRE(feat_out, "pdsc_layer_fused_frag: tail-only needs feat_out");
-    PDSC_REQUIRE((q_split == nullptr) == (kv_tiles == nullptr), "pdsc_layer_fused_frag: q_split and kv_tiles go together");
-    LayerArgs a{};
-    a.msg = msg; a.part_o = part_o; a.part_ml = part_ml; a.nsplit = nsplit; a.Npad = Npad;
-    a.res = res; a.feat_in = feat_in; a.feat_out = feat_out; a.featB_out = featB_out; a.qkv_out = qkv_out;
-    a.qs = (sp16*)q_split; a.kv = (unsigned char*)kv_tiles;
-    a.N = N; a.bs = bs;
+    LayerArgs a = layer_args_io(msg, part_o, part_ml, nsplit, Npad, res, feat_in, feat_out, featB_out, qkv_out, q_split, kv_tiles, bs, N);
     a.wf_tail = (const unsigned char*)wfrag_tail; a.wf_head = (const unsigned char*)wfrag_head;
     a.gemm_format = gemm_format;
-    a.stagger_cycles = env_int("PDSC_LAYER_STAGGER", 0);
-    a.stagger_mode = env_int("PDSC_LAYER_STAGGER_MODE", 1);
     a.trace = pdsc_layer_trace_buffer();
-    a.nvalid = layer_nvalid_slot();
     // H3: the pipelined kernel of layer_h3.hip; A/B knob PDSC_LAYER_H3_VARIANT = 0: this file's kernel with the H3 GEMMs
-    if (gemm_format == PDSC_LAYER_GEMM_H3 && env_int("PDSC_LAYER_H3_VARIANT", 1) != 0 && launch_layer_h3_fits(a, tail, head))
-        return launch_layer_h3(a, tail, head, (hipStream_t)stream);
-    return launch_layer_wave(a, tail, head, (hipStream_t)stream);
+    const bool h3 = gemm_format == PDSC_LAYER_GEMM_H3 && env_int("PDSC_LAYER_H3_VARIANT", 1) != 0 &&
+                    launch_layer_h3_fits(a, msg != nullptr || part_o != nullptr, featB_out != nullptr);
+    const LayerKernel kernel = h3 ? LayerKernel::H3 : LayerKernel::Wave;
+    const int rc = validate_layer_args(a, kernel, "pdsc_layer_fused_frag");
+    return rc != PDSC_OK ? rc : dispatch_layer(a, kernel, (hipStream_t)stream);
 }
 
 extern "C" int pdsc_layer_fused_frag(const float* msg, const float* part_o, const float* part_ml, int nsplit, int Npad,

@@ -48,9 +48,8 @@ int launch_classifier_hidden(const float* X, const float* W1, const float* b1, c
 // Every site that converts an activation notes its magnitude (range_note: one v_max3_f32 per two values); a wavefront whose maximum
 // reaches the bound sets the word of its pair in `range_flag` ([bs] u32, workspace entry "range_flag": zeroed by the forward's first
 // launch, read by its last one, which turns the pose of such a pair into NaN -- a result that is wrong is never returned silently).
-// run_forward publishes the array through this thread-local slot for the duration of a call (like layer_nvalid_slot, ragged.h);
-// stage-level calls outside a forward leave it NULL and the kernels skip the report.
-unsigned int*& range_flag_slot();
+// run_forward passes the array to the layer kernels in LayerArgs.range_flag (layer_args.h); stage-level calls outside a forward
+// leave it NULL and the kernels skip the report.
 constexpr float PDSC_F16_RANGE = 65504.0f;
 
 // opt-in event timing of the roofline kernels (api.hip); no-ops unless pdsc_profile_enable() was called

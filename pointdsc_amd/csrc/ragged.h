@@ -2,7 +2,8 @@
 // seed count s_b <= S, while every buffer keeps the strides of the longest pair (rows n_b .. N-1 of a pair are padding).
 // The stages whose result depends on the count -- attention (keys / queries), NMS, seed ranking, kNN columns, hypothesis
 // scoring, best-hypothesis labels, refinement -- take the device arrays `nvalid` / `svalid` ([bs] int32, NULL = uniform
-// batch) through these internal launchers; the public stage entry points are the same launchers with NULL.
+// batch) through these internal launchers (the fused-layer kernels: LayerArgs.nvalid, layer_args.h); the public stage entry
+// points are the same launchers with NULL.
 // Everything row-parallel (layer kernels, classifier, normalisation, Gram rows, per-seed solver) runs unchanged over the
 // padded layout: padding rows carry finite copies / unused values that no valid row ever reads.
 #pragma once
@@ -62,10 +63,5 @@ void leaf_plan(int bs, int N, int leaves_mode, int* nw_out, int* nsplit_out, int
 int launch_attention_leaves(const void* q_split, const void* kv_tiles, const void* compat, int compat_format, long long ld,
                             void* scratch, size_t scratch_bytes, int bs, int N, int leaves_mode, const int* nvalid, int n_min,
                             hipStream_t st, int value_width = PDSC_CHANNELS);
-
-// The three fused-layer entry points (pdsc_layer_fused_split / _frag_fmt / _frag_io: 18-24 arguments each) read the count
-// array from this thread-local slot when they fill LayerArgs; run_forward sets it for the duration of a ragged call and
-// clears it before returning (host-side, per thread: concurrent callers on other threads are unaffected).
-const int*& layer_nvalid_slot();
 
 }  // namespace pdsc
