@@ -45,7 +45,7 @@
 extern "C" {
 #endif
 
-#define PDSC_VERSION 8
+#define PDSC_VERSION 9
 #define PDSC_CHANNELS 128        /* num_channels of every released PointDSC model */
 #define PDSC_MAX_K 64            /* neighbours per seed handled by one wavefront   */
 #define PDSC_MAX_POWER_ITERS 32
@@ -150,7 +150,7 @@ enum pdsc_compat_format { PDSC_COMPAT_F32 = 0, PDSC_COMPAT_U16 = 1 };
  *           confidence logits reach 33, that left the logits up to 0.27 from the reference's; the fp16 pairs leave 0.04
  *           (exact fp32: 0.017) for 1.7 % of the pairs/s (same-box A/B, profiles/r05_j_ab_split16_summary.txt).
  *   FP32  : v_mfma_f32_32x32x2_f32, exact fp32 products, 16/3 x the matrix-pipe time.
- *   FP16X3_ALL: the point-wise GEMMs too (pdsc_layer_fused_x3): their error lands on the residual stream un-averaged.
+ *   FP16X3_ALL: the point-wise GEMMs too (PDSC_LAYER_KERNEL_X3): their error lands on the residual stream un-averaged.
  *           A/B record: accepted by experiments builds only.
  * BREAKING in PDSC_VERSION 8: the names PDSC_ATT_BF16X3 / PDSC_ATT_BF16X3_ALL of rounds 1-4 are GONE (they were aliases of values 0 / 2
  * in version 7).  Those modes split into bf16 pairs and had fp32's range; values 0 / 2 split into fp16 pairs and do not -- a C caller
@@ -253,57 +253,78 @@ int pdsc_layer0(const float* corr_pos, int in_dim, const float* W0, const float*
                 int M, void* stream);
 
 /* Fused point-wise chain between two attention calls (one launch instead of five pdsc_linear calls):
- *   tail (msg != NULL):      feat = res + fc3(relu(fc2(relu(fc1(msg)))))            models/PointDSC.py:43-45
- *   head (featB_out != NULL): featB = relu(pcn(feat)); qkv = Wqkv featB + bqkv       models/PointDSC.py:75,36-38
- * tail only -> feat_out required; head only -> feat_in required.  All matrices [out][in], BN folded
- * (sections PDSC_W_FC1..FC3 of layer i, PDSC_W_PCN/QKV of layer i+1).  Buffers must not alias. */
-int pdsc_layer_fused(const float* msg, const float* res, const float* feat_in, float* feat_out,
-                     float* featB_out, float* qkv_out,
-                     const float* w1, const float* b1, const float* w2, const float* b2,
-                     const float* w3, const float* b3, const float* wp, const float* bp,
-                     const float* wq, const float* bq, int M, void* stream);
+ *   tail (msg or the partials given): feat = res + fc3(relu(fc2(relu(fc1(msg)))))    models/PointDSC.py:43-45
+ *   head (featB_out given):           featB = relu(pcn(feat)); qkv = Wqkv featB + bqkv models/PointDSC.py:75,36-38
+ * tail only -> feat_out required; head only -> feat_in required.  Rows are bs pairs of N points (a 32-point tile never
+ * straddles two pairs); a caller with one run of M independent rows passes bs = 1, N = M.  Buffers must not alias.
+ * One call, pdsc_layer_run, takes one struct; a zero-initialised field means "absent".  The weights come in ONE of two forms:
+ *   natural layout: [out][in] fp32 matrices, BN folded (sections PDSC_W_FC1..FC3 of layer i, PDSC_W_PCN / QKV of layer i+1);
+ *   fragment streams: 8 KiB chunks in exactly the order the wavefront-resident kernels consume them, so every weight load of
+ *     a wave is 1 KiB of consecutive memory -- what pdsc_forward_* uses by default.  Built by pdsc_wfrag_build_tail / _head:
+ *       tail stream: pdsc_wfrag_tail_bytes() bytes from (fc1 [C/2][C], fc2 [C/2][C/2], fc3 [C][C/2]) fp32 and their biases;
+ *       head stream: pdsc_wfrag_head_bytes() bytes from (pcn [C][C], qkv [3C][C] fp32 -> fp16 hi / lo) and their biases
+ *                    (the bias of an output tile is one more k-step of its GEMM: A = bias, B = 1);
+ *     gemm_format (enum pdsc_layer_gemm) chooses the format of the fc1..fc3 / pcn chunks (the q|k|v chunks are fp16 hi / lo in
+ *     both), and the layer call must be told the format its streams were built in.
+ * Giving weights in both forms is PDSC_ERR_ARG.
+ * BREAKING in PDSC_VERSION 9: the six fused-layer entry points of version 8 (one per weight form: natural, with split streams, all
+ * split, fragment streams, with a format, with io flags) are GONE.  pdsc_layer_run does what each did when the struct's fields of
+ * the same names hold the same values (the M-rows form: bs = 1, N = M; the all-split form: kernel = PDSC_LAYER_KERNEL_X3).
+ * pdsc_wfrag_build_tail / _head take gemm_format: PDSC_LAYER_GEMM_F32 is what they built before, and their format-suffixed twins
+ * are gone. */
+enum pdsc_layer_kernel {
+    PDSC_LAYER_KERNEL_AUTO = 0,  /* natural layout: BLOCK if pdsc_layer_prefers_block(bs, N), else WAVE.  Fragment streams: H3 if
+                                  * io_flags != 0; else H3 if gemm_format = PDSC_LAYER_GEMM_H3 and the H3 kernel serves the output
+                                  * set (head: the split streams only, no qkv_out; tail + head: no feat_out), else WAVE */
+    PDSC_LAYER_KERNEL_BLOCK,     /* one 4-wave workgroup per 32-point tile, natural layout; merges up to 8 partials */
+    PDSC_LAYER_KERNEL_WAVE,      /* one wavefront per tile, natural layout or fragment streams; merges up to 4 partials */
+    PDSC_LAYER_KERNEL_H3,        /* the pipelined kernel over PDSC_LAYER_GEMM_H3 streams (layer_h3_coop_kernel for few tiles); up to 8 */
+    PDSC_LAYER_KERNEL_X3         /* every GEMM as three f16 MFMAs per operand pair (PDSC_ATT_FP16X3_ALL); never chosen by AUTO;
+                                  * up to 4 partials; experiments builds only, PDSC_ERR_ARG in the product library */
+};
+/* A kernel other than AUTO that the arguments do not fit is PDSC_ERR_ARG. */
+typedef struct pdsc_layer_call {
+    const float* msg;        /* [bs*N][C] tail input: the merged attention output, or NULL when the partials below are given */
+    const float* part_o;     /* tail input, un-merged: the key-split partials exactly as pdsc_sc_attention_split leaves them in its */
+    const float* part_ml;    /*   scratch when called with msg == NULL, part_o [bs][nsplit][Npad][C], part_ml [bs][nsplit][Npad][2]; */
+    int nsplit, Npad;        /*   the merge happens while the tile is loaded (no combine launch, no round trip of msg through HBM) */
+    const float* res;        /* [bs*N][C] tail residual (featB of this layer) */
+    const float* feat_in;    /* [bs*N][C] head-only input */
+    float* feat_out;         /* [bs*N][C] tail result; required when there is no head, optional otherwise */
+    float* featB_out;        /* [bs*N][C] head result; NULL = no head */
+    float* qkv_out;          /* [bs*N][3C] head, fp32 (q|k|v) rows; optional when the split streams below are given */
+    void* q_split;           /* head, optional, both or neither: the fp16 hi/lo operand streams of the split-precision attention */
+    void* kv_tiles;          /*   (pointdsc_amd/csrc/split_layout.h): q_split [bs*N][256] fp16 (hi | lo), pdsc_split_q_bytes(bs, N)
+                              *   bytes; kv_tiles [bs][ceil(N/32)][37 KiB] (a 32 KiB image per tile of 32 keys, images 37 KiB
+                              *   apart), pdsc_split_kv_bytes(bs, N) bytes */
+    const void* w1; const float* b1;     /* natural layout: fc1 [C/2][C], fc2 [C/2][C/2], fc3 [C][C/2] (tail), pcn [C][C], */
+    const void* w2; const float* b2;     /*   qkv [3C][C] (head) as fp32 [out][in] and their fp32 biases.  PDSC_LAYER_KERNEL_X3: */
+    const void* w3; const float* b3;     /*   the five matrices are those of the split-weight buffer instead (fp16 [out][in] hi, */
+    const void* wp; const float* bp;     /*   then [out][in] lo, at 16-bit element pdsc_wsplit_offset(cfg, section, layer)); */
+    const void* wq; const float* bq;     /*   the biases stay fp32 */
+    const void* wq_split;    /* optional, natural layout: the q|k|v weights as fp16 hi [3C][C] | lo [3C][C] (section PDSC_W_QKV_W of
+                              * the split-weight buffer) -> that one GEMM runs in split precision; q, k, v only feed the attention,
+                              * whose own operand split has an error of the same order, and never touch the residual stream */
+    const void* wfrag_tail;  /* fragment streams (pdsc_wfrag_build_tail / _head) instead of the natural-layout weights; the */
+    const void* wfrag_head;  /*   q|k|v projection then runs in split precision */
+    int gemm_format;         /* enum pdsc_layer_gemm: the format the fragment streams were built in */
+    int io_flags;            /* OR of enum pdsc_layer_io: which of part_o / res / featB_out are in point-fragment order.  Non-zero
+                              * needs gemm_format = PDSC_LAYER_GEMM_H3 and the forward's output set (head: split streams only, no
+                              * qkv_out; tail + head: no feat_out), PDSC_ERR_ARG otherwise; PF res / featB_out buffers hold
+                              * bs * ceil(N / 32) * 32 rows */
+    int bs, N;
+    int kernel;              /* enum pdsc_layer_kernel */
+} pdsc_layer_call;
+int pdsc_layer_run(const pdsc_layer_call* call, void* stream);
 
-/* Same chain, with the head additionally (or instead of qkv_out, which may then be NULL) emitting the fp16 hi/lo
- * operand streams of the split-precision attention (layout: pointdsc_amd/csrc/split_layout.h):
- *   q_split  [bs*N][256] fp16 (hi | lo), pdsc_split_q_bytes(bs, N) bytes;
- *   kv_tiles [bs][ceil(N/32)][37 KiB] (a 32 KiB image per tile of 32 keys, images 37 KiB apart), pdsc_split_kv_bytes(bs, N) bytes.
- * Rows are bs pairs of N points (a 32-point tile never straddles two pairs).
- * The tail input is either `msg` (merged rows) or the un-merged key-split partials (`part_o`, `part_ml`, nsplit, Npad)
- * exactly as pdsc_sc_attention_split leaves them in its scratch when called with msg == NULL: the merge then happens
- * while the tile is loaded (no combine launch, no round trip of msg through HBM).
- * wq_split (optional): the q|k|v weights as fp16 hi [3C][C] | lo [3C][C] (section PDSC_W_QKV_W of the split-weight
- * buffer, pdsc_wsplit_build below) -> that one GEMM runs in split precision; q, k, v only feed the attention, whose
- * own operand split has an error of the same order, and never touch the residual stream. */
-int pdsc_layer_fused_split(const float* msg, const float* part_o, const float* part_ml, int nsplit, int Npad,
-                           const float* res, const float* feat_in, float* feat_out,
-                           float* featB_out, float* qkv_out, void* q_split, void* kv_tiles,
-                           const float* w1, const float* b1, const float* w2, const float* b2,
-                           const float* w3, const float* b3, const float* wp, const float* bp,
-                           const float* wq, const float* bq, const void* wq_split /* optional */, int bs, int N,
-                           void* stream);
-
-/* Split-precision variant of the whole chain (PDSC_ATT_FP16X3_ALL: every GEMM as three f16 MFMAs per operand pair);
- * same tail-input convention.  Weights come from the split-weight buffer:
- *   pdsc_wsplit_bytes(cfg) bytes, filled once per model by pdsc_wsplit_build(cfg, wpack, wsplit, stream);
+/* The split-weight buffer: pdsc_wsplit_bytes(cfg) bytes, filled once per model by pdsc_wsplit_build(cfg, wpack, wsplit, stream);
  *   matrix of `section` (PDSC_W_PCN_W, _QKV_W, _FC1_W, _FC2_W, _FC3_W) of `layer` starts at 16-bit element
- *   pdsc_wsplit_offset(cfg, section, layer): [out][in] hi, then [out][in] lo.  Biases stay fp32 (packed buffer). */
+ *   pdsc_wsplit_offset(cfg, section, layer): [out][in] hi, then [out][in] lo.  Biases stay fp32 (packed buffer).
+ * pdsc_wsplit_build also stores the fragment streams per layer, in both formats, at 16-bit element
+ * pdsc_wsplit_offset(cfg, PDSC_WS_FRAG_TAIL / PDSC_WS_FRAG_HEAD (_H3), layer). */
 size_t    pdsc_wsplit_bytes(const pdsc_config* cfg);
 long long pdsc_wsplit_offset(const pdsc_config* cfg, int section, int layer);
 int       pdsc_wsplit_build(const pdsc_config* cfg, const float* wpack, void* wsplit, void* stream);
-int pdsc_layer_fused_x3(const float* msg, const float* part_o, const float* part_ml, int nsplit, int Npad,
-                        const float* res, const float* feat_in, float* feat_out, float* featB_out, float* qkv_out,
-                        void* q_split, void* kv_tiles,
-                        const void* w1, const float* b1, const void* w2, const float* b2, const void* w3, const float* b3,
-                        const void* wp, const float* bp, const void* wq, const float* bq, int bs, int N, void* stream);
-
-/* The same chain (tail of layer i, head of layer i+1, q|k|v projection in split precision) with the weights supplied as
- * MFMA-fragment-ordered streams: 8 KiB chunks in exactly the order the wavefront-resident kernel consumes them, so every
- * weight load of a wave is 1 KiB of consecutive memory.  This is the entry pdsc_forward_* uses by default.
- *   tail stream: pdsc_wfrag_tail_bytes() bytes from (fc1 [C/2][C], fc2 [C/2][C/2], fc3 [C][C/2]) fp32 and their biases;
- *   head stream: pdsc_wfrag_head_bytes() bytes from (pcn [C][C] fp32 kept fp32, qkv [3C][C] fp32 -> fp16 hi / lo) and
- *                their biases (the bias of an output tile is one more k-step of its GEMM: A = bias, B = 1).
- * pdsc_wsplit_build also stores both per layer inside the split-weight buffer, at 16-bit element
- * pdsc_wsplit_offset(cfg, PDSC_WS_FRAG_TAIL / PDSC_WS_FRAG_HEAD, layer). */
 #define PDSC_WS_FRAG_TAIL 100
 #define PDSC_WS_FRAG_HEAD 101
 #define PDSC_WS_FRAG_TAIL_H3 102   /* the same streams built with gemm_format = PDSC_LAYER_GEMM_H3 */
@@ -323,29 +344,9 @@ int pdsc_layer_h3_uses_coop(int bs, int N);    /* 1: with layer_gemm = H3, a lau
 size_t pdsc_wfrag_tail_bytes(void);
 size_t pdsc_wfrag_head_bytes(void);
 int pdsc_wfrag_build_tail(const float* w1, const float* b1, const float* w2, const float* b2, const float* w3,
-                          const float* b3, void* out, void* stream);
-int pdsc_wfrag_build_head(const float* wp, const float* bp, const float* wq, const float* bq, void* out, void* stream);
-/* ... with the format of the fc1..fc3 / pcn chunks chosen (enum pdsc_layer_gemm; the q|k|v chunks are fp16 hi / lo in
- * both; the un-suffixed entries build PDSC_LAYER_GEMM_F32 streams).  pdsc_layer_fused_frag_fmt must be told the format. */
-int pdsc_wfrag_build_tail_fmt(const float* w1, const float* b1, const float* w2, const float* b2, const float* w3,
-                              const float* b3, void* out, int gemm_format, void* stream);
-int pdsc_wfrag_build_head_fmt(const float* wp, const float* bp, const float* wq, const float* bq, void* out,
-                              int gemm_format, void* stream);
-int pdsc_layer_fused_frag_fmt(const float* msg, const float* part_o, const float* part_ml, int nsplit, int Npad,
-                              const float* res, const float* feat_in, float* feat_out, float* featB_out, float* qkv_out,
-                              void* q_split, void* kv_tiles, const void* wfrag_tail, const void* wfrag_head,
-                              int gemm_format, int bs, int N, void* stream);
-/* ... with point-fragment hand-offs: io_flags = OR of enum pdsc_layer_io (which of part_o / res / featB_out are PF).
- * Needs gemm_format = PDSC_LAYER_GEMM_H3 and the forward's output set (head: split streams only, no qkv_out; tail + head:
- * no feat_out); PDSC_ERR_ARG otherwise.  PF res / featB_out buffers hold bs * ceil(N / 32) * 32 rows. */
-int pdsc_layer_fused_frag_io(const float* msg, const float* part_o, const float* part_ml, int nsplit, int Npad,
-                             const float* res, const float* feat_in, float* feat_out, float* featB_out,
-                             void* q_split, void* kv_tiles, const void* wfrag_tail, const void* wfrag_head,
-                             int gemm_format, int io_flags, int bs, int N, void* stream);
-int pdsc_layer_fused_frag(const float* msg, const float* part_o, const float* part_ml, int nsplit, int Npad,
-                          const float* res, const float* feat_in, float* feat_out, float* featB_out, float* qkv_out,
-                          void* q_split, void* kv_tiles, const void* wfrag_tail, const void* wfrag_head, int bs, int N,
-                          void* stream);
+                          const float* b3, void* out, int gemm_format, void* stream);
+int pdsc_wfrag_build_head(const float* wp, const float* bp, const float* wq, const float* bq, void* out,
+                          int gemm_format, void* stream);
 
 /* ---- a-3  spatial-consistency guided non-local attention ---------------------------------------
  * replaces models/PointDSC.py:39-42 (both einsums and the softmax; N x N scores never materialised).
@@ -378,7 +379,7 @@ int    pdsc_sc_attention_split(const void* q_split, const void* kv_tiles, const 
 int    pdsc_sc_attention_split_u16(const void* q_split, const void* kv_tiles, const unsigned short* compat_u16, long long ld,
                                    float* msg, void* scratch, size_t scratch_bytes, int bs, int N, int nsplit,
                                    void* stream);
-/* msg == NULL (only when the key split is > 1): the partials are left un-merged in `scratch` for pdsc_layer_fused_x3:
+/* msg == NULL (only when the key split is > 1): the partials are left un-merged in `scratch` for pdsc_layer_run:
  * part_o = scratch as [bs][nsplit][Npad][C] floats, Npad = N rounded up to 256, part_ml right behind it as
  * [bs][nsplit][Npad][2]. */
 

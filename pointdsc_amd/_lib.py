@@ -39,6 +39,15 @@ W = {name: i for i, name in enumerate(W_SECTIONS)}
 _vp, _i, _f, _ll, _sz = C.c_void_p, C.c_int, C.c_float, C.c_longlong, C.c_size_t
 _cfgp = C.POINTER(PdscConfig)
 
+
+class PdscLayerCall(C.Structure):
+    """struct pdsc_layer_call (include/pointdsc_hip.h): one fused point-wise layer launch; zero / None = absent."""
+    _fields_ = (
+        [(n, _vp) for n in ("msg", "part_o", "part_ml")] + [("nsplit", _i), ("Npad", _i)] +
+        [(n, _vp) for n in ("res", "feat_in", "feat_out", "featB_out", "qkv_out", "q_split", "kv_tiles",
+                            "w1", "b1", "w2", "b2", "w3", "b3", "wp", "bp", "wq", "bq", "wq_split", "wfrag_tail", "wfrag_head")] +
+        [(n, _i) for n in ("gemm_format", "io_flags", "bs", "N", "kernel")])
+
 # name -> (restype, argtypes); must list every function include/pointdsc_hip.h declares
 SIGNATURES = {
     "pdsc_version": (_i, []),
@@ -57,26 +66,19 @@ SIGNATURES = {
     "pdsc_classifier_hidden": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
     "pdsc_linear": (_i, [_vp, _ll, _vp, _vp, _vp, _ll, _vp, _ll, _i, _i, _i, _i, _vp]),
     "pdsc_layer0": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp]),
-    "pdsc_layer_fused": (_i, [_vp] * 16 + [_i, _vp]),
-    "pdsc_layer_fused_split": (_i, [_vp, _vp, _vp, _i, _i] + [_vp] * 18 + [_i, _i, _vp]),
+    "pdsc_layer_run": (_i, [C.POINTER(PdscLayerCall), _vp]),
     "pdsc_wsplit_bytes": (_sz, [_cfgp]),
     "pdsc_wsplit_offset": (_ll, [_cfgp, _i, _i]),
     "pdsc_wsplit_build": (_i, [_cfgp, _vp, _vp, _vp]),
-    "pdsc_layer_fused_x3": (_i, [_vp, _vp, _vp, _i, _i] + [_vp] * 17 + [_i, _i, _vp]),
     "pdsc_layer_prefers_block": (_i, [_i, _i]),
     "pdsc_layer_h3_uses_coop": (_i, [_i, _i]),
     "pdsc_wfrag_tail_bytes": (_sz, []),
     "pdsc_wfrag_head_bytes": (_sz, []),
     "pdsc_wfrag_fold_tail_bytes": (_sz, []),
     "pdsc_wfrag_fold_head_bytes": (_sz, []),
-    "pdsc_wfrag_build_tail": (_i, [_vp] * 8),
-    "pdsc_wfrag_build_head": (_i, [_vp] * 6),
-    "pdsc_wfrag_build_tail_fmt": (_i, [_vp] * 7 + [_i, _vp]),
-    "pdsc_wfrag_build_head_fmt": (_i, [_vp] * 5 + [_i, _vp]),
-    "pdsc_layer_fused_frag_fmt": (_i, [_vp, _vp, _vp, _i, _i] + [_vp] * 9 + [_i, _i, _i, _vp]),
-    "pdsc_layer_fused_frag_io": (_i, [_vp, _vp, _vp, _i, _i] + [_vp] * 8 + [_i, _i, _i, _i, _vp]),
+    "pdsc_wfrag_build_tail": (_i, [_vp] * 7 + [_i, _vp]),
+    "pdsc_wfrag_build_head": (_i, [_vp] * 5 + [_i, _vp]),
     "pdsc_sc_attention_split_partials": (_i, [_vp, _vp, _vp, _i, _ll, _vp, _sz, _i, _i, _i, _i, _vp]),
-    "pdsc_layer_fused_frag": (_i, [_vp, _vp, _vp, _i, _i] + [_vp] * 9 + [_i, _i, _vp]),
     "pdsc_split_q_bytes": (_sz, [_i, _i]),
     "pdsc_split_kv_bytes": (_sz, [_i, _i]),
     "pdsc_pack_qkv_split": (_i, [_vp, _vp, _vp, _i, _i, _vp]),
@@ -157,7 +159,7 @@ def load() -> C.CDLL:
             raise PointDSCLibraryError(f"{LIB_PATH} does not export {name}") from e
         fn.restype = res
         fn.argtypes = args
-    if lib.pdsc_version() != 8:
+    if lib.pdsc_version() != 9:
         raise PointDSCLibraryError(f"unexpected library version {lib.pdsc_version()}")
     _lib = lib
     return lib

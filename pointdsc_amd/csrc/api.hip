@@ -371,7 +371,7 @@ extern "C" int pdsc_profile_read(int kind, double* total_ms, int* launches) {
 struct EncoderPlan {
     bool fused;              // one launch per (tail of layer i, head of layer i + 1); false: one pdsc_linear launch per conv
     bool split;              // split-precision attention; every field below but `kernel` is set for the fused split path only
-    LayerKernel kernel;      // the fused-layer kernel of every launch (x3: pdsc_layer_fused_x3, which merges like the wavefront kernel)
+    LayerKernel kernel;      // the fused-layer kernel of every launch
     bool x3, frag;           // layer weights: split fp16 (PDSC_ATT_FP16X3_ALL) / fragment streams / else natural layout
     bool fuse_merge;         // the layer kernel merges the key-split partials while loading (no combine launch, no msg round trip)
     bool pf, leaves, fold;   // point-fragment hand-offs; attention in leaf form; the folded layer (64-channel value projection)
@@ -422,7 +422,7 @@ static int plan_encoder(const pdsc_config* cfg, int bs, int N, const int* nvalid
     // with the H3 GEMMs
     const LayerKernel natural = by_size(bs, N);
     p.frag = env_int("PDSC_LAYER_FRAG", 1) && !p.x3 && !force_block && (natural == LayerKernel::Wave || h3);
-    p.kernel = p.x3     ? LayerKernel::Wave
+    p.kernel = p.x3     ? LayerKernel::X3
                : !p.frag ? natural
                          : h3 && env_int("PDSC_LAYER_H3_VARIANT", 1) != 0 ? LayerKernel::H3 : LayerKernel::Wave;
     // the layer kernels merge the key-split partials while loading (merge_partials.h), up to the limit of the kernel chosen
@@ -531,44 +531,45 @@ static int run_forward(int mode, const pdsc_config* cfg, const float* wpack, con
         const float* part_o = parts ? (const float*)att_scratch : nullptr;
         const float* part_ml = parts ? part_o + (size_t)bs * nparts * plan.Npad * plan.value_width : nullptr;
         // tail of layer i (i = -1: none, the input is featA) and head of layer i+1 (last: none, the result is featA)
-        auto layer_x3 = [&](int i, bool last, const float* cur, float* nxt) -> int {      // (experiments builds: layer_split.hip)
-            const bool tail = i >= 0, head = !last;
-            return pdsc_layer_fused_x3(tail && !parts ? msg : nullptr, tail ? part_o : nullptr, tail ? part_ml : nullptr, tail ? nparts : 0,
-                                       tail ? plan.Npad : 0, tail ? cur : nullptr, tail ? nullptr : featA, last ? featA : nullptr,
-                                       head ? nxt : nullptr, nullptr, head ? q_split : nullptr, head ? kv_tiles : nullptr,
-                                       tail ? WS(PDSC_W_FC1_W, i) : nullptr, tail ? W(PDSC_W_FC1_B, i) : nullptr,
-                                       tail ? WS(PDSC_W_FC2_W, i) : nullptr, tail ? W(PDSC_W_FC2_B, i) : nullptr,
-                                       tail ? WS(PDSC_W_FC3_W, i) : nullptr, tail ? W(PDSC_W_FC3_B, i) : nullptr,
-                                       head ? WS(PDSC_W_PCN_W, i + 1) : nullptr, head ? W(PDSC_W_PCN_B, i + 1) : nullptr,
-                                       head ? WS(PDSC_W_QKV_W, i + 1) : nullptr, head ? W(PDSC_W_QKV_B, i + 1) : nullptr, bs, N, stream);
-        };
         auto layer = [&](int i, bool last, const float* cur, float* nxt) -> int {
-            if (plan.x3) return layer_x3(i, last, cur, nxt);
             const bool tail = i >= 0, head = !last;
+            pdsc_layer_call c{};
             // exact fp32: the batch is ONE run of M independent rows (bs = 1, N = M), so the per-pair counts of a ragged batch do
             // not describe it (with them the kernel took counts[0] for the row count of the whole batch).  Padding rows are computed
             // like any row; nothing valid reads them.
-            LayerArgs a = layer_args_io(tail && !parts ? msg : nullptr, tail ? part_o : nullptr, tail ? part_ml : nullptr, tail ? nparts : 0,
-                                        tail ? plan.Npad : 0, tail ? cur : nullptr, tail ? nullptr : featA, last ? featA : nullptr,
-                                        head ? nxt : nullptr, head && !split ? qkv : nullptr, head ? q_split : nullptr,
-                                        head ? kv_tiles : nullptr, split ? bs : 1, split ? N : M);
-            a.nvalid = split ? nvalid : nullptr;
+            c.bs = split ? bs : 1; c.N = split ? N : M;
+            if (tail) {
+                c.msg = parts ? nullptr : msg;
+                c.part_o = part_o; c.part_ml = part_ml; c.nsplit = nparts; c.Npad = plan.Npad;
+                c.res = cur;
+            } else
+                c.feat_in = featA;
+            if (last) c.feat_out = featA;
+            if (head) {
+                c.featB_out = nxt; c.qkv_out = split ? nullptr : qkv;
+                c.q_split = q_split; c.kv_tiles = kv_tiles;
+            }
             if (plan.frag) {
-                if (tail) a.wf_tail = (const unsigned char*)WS(plan.ws_tail, i);
-                if (head) a.wf_head = (const unsigned char*)WS(plan.ws_head, i + 1);
-                a.gemm_format = plan.gemm;
+                if (tail) c.wfrag_tail = WS(plan.ws_tail, i);
+                if (head) c.wfrag_head = WS(plan.ws_head, i + 1);
+                c.gemm_format = plan.gemm;
             } else {
+                // natural layout; x3 (experiments builds: layer_split.hip): the hi|lo matrices of the split-weight buffer instead
+                auto mat = [&](int section, int l) { return plan.x3 ? WS(section, l) : (const void*)W(section, l); };
                 if (tail) {
-                    a.w1 = W(PDSC_W_FC1_W, i); a.b1 = W(PDSC_W_FC1_B, i); a.w2 = W(PDSC_W_FC2_W, i); a.b2 = W(PDSC_W_FC2_B, i);
-                    a.w3 = W(PDSC_W_FC3_W, i); a.b3 = W(PDSC_W_FC3_B, i);
+                    c.w1 = mat(PDSC_W_FC1_W, i); c.b1 = W(PDSC_W_FC1_B, i); c.w2 = mat(PDSC_W_FC2_W, i); c.b2 = W(PDSC_W_FC2_B, i);
+                    c.w3 = mat(PDSC_W_FC3_W, i); c.b3 = W(PDSC_W_FC3_B, i);
                 }
                 if (head) {
-                    a.wp = W(PDSC_W_PCN_W, i + 1); a.bp = W(PDSC_W_PCN_B, i + 1); a.wq = W(PDSC_W_QKV_W, i + 1); a.bq = W(PDSC_W_QKV_B, i + 1);
-                    if (split) a.wq_split = (const sp16*)WS(PDSC_W_QKV_W, i + 1);
+                    c.wp = mat(PDSC_W_PCN_W, i + 1); c.bp = W(PDSC_W_PCN_B, i + 1); c.wq = mat(PDSC_W_QKV_W, i + 1); c.bq = W(PDSC_W_QKV_B, i + 1);
+                    if (split) c.wq_split = WS(PDSC_W_QKV_W, i + 1);
                 }
             }
-            if (plan.pf) {       // (the table beside layer_args_io: the point-fragment route reports to the sentinel and takes no trace)
-                a.io_flags = (tail ? PDSC_IO_PARTIALS_PF | PDSC_IO_RES_PF : 0) | (head ? PDSC_IO_FEATB_PF : 0);
+            if (plan.pf) c.io_flags = (tail ? PDSC_IO_PARTIALS_PF | PDSC_IO_RES_PF : 0) | (head ? PDSC_IO_FEATB_PF : 0);
+            // the forward's own fields: the point-fragment route reports to the range sentinel and takes no trace (layer_args.h)
+            LayerArgs a = layer_args_from_call(c);
+            a.nvalid = split ? nvalid : nullptr;
+            if (plan.pf) {
                 a.value_fold = plan.fold;
                 a.range_flag = range_flag;
             } else

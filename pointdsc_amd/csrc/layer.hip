@@ -378,7 +378,7 @@ static int launch_layer(const LayerArgs& a, hipStream_t st) {
         hipLaunchKernelGGL((layer_fused_kernel<T, H, H>), dim3(ceil_div(a.N, LF_ROWS), a.bs), dim3(256), 0, st, a);
     else
         hipLaunchKernelGGL((layer_fused_kernel<T, H, false>), dim3(ceil_div(a.N, LF_ROWS), a.bs), dim3(256), 0, st, a);
-    return check_launch("pdsc_layer_fused");
+    return check_launch("pdsc_layer_run(block)");
 }
 
 }  // namespace pdsc
@@ -446,6 +446,7 @@ int dispatch_layer(const LayerArgs& a, LayerKernel kernel, hipStream_t st) {
         return launch_layer_h3(h, tail, head, st);
     }
     if (kernel == LayerKernel::Wave) return launch_layer_wave(a, tail, head, st);
+    if (kernel == LayerKernel::X3) return launch_layer_x3(a, tail, head, st);
     if (tail && head) {
         profile_mark_begin(PDSC_PROF_LAYER, st);
         const int rc = launch_layer<true, true>(a, st);
@@ -458,34 +459,50 @@ int dispatch_layer(const LayerArgs& a, LayerKernel kernel, hipStream_t st) {
 
 }  // namespace pdsc
 
-extern "C" int pdsc_layer_fused_split(const float* msg, const float* part_o, const float* part_ml, int nsplit, int Npad,
-                                      const float* res, const float* feat_in, float* feat_out,
-                                      float* featB_out, float* qkv_out, void* q_split, void* kv_tiles,
-                                      const float* w1, const float* b1, const float* w2, const float* b2, const float* w3,
-                                      const float* b3, const float* wp, const float* bp, const float* wq, const float* bq,
-                                      const void* wq_split, int bs, int N, void* stream) {
-    pdsc::LayerArgs a = pdsc::layer_args_io(msg, part_o, part_ml, nsplit, Npad, res, feat_in, feat_out, featB_out, qkv_out, q_split,
-                                            kv_tiles, bs, N);
-    a.w1 = w1; a.b1 = b1; a.w2 = w2; a.b2 = b2; a.w3 = w3; a.b3 = b3;
-    a.wp = wp; a.bp = bp; a.wq = wq; a.bq = bq; a.wq_split = (const sp16*)wq_split;
-    a.trace = g_layer_trace;
-    // Two implementations.  layer_wave.hip (one wavefront per 32-point tile) wins once the tiles fill the chip; with few
-    // tiles its serial 46k matrix-pipe cycles per tile are the launch time, and this file's kernel, which spreads a tile
-    // over the four SIMDs of a CU, is faster (N = 1000, one pair: 0.68 vs 1.10 ms per forward).
-    // PDSC_LAYER_VARIANT = block | wave overrides the size rule.
-    const char* ev = pdsc::env_str("PDSC_LAYER_VARIANT");          // experiments builds only
-    const bool block = ev && (ev[0] == 'b' || ev[0] == 'w') ? ev[0] == 'b' : pdsc_layer_prefers_block(bs, N) != 0;
-    const pdsc::LayerKernel kernel = block ? pdsc::LayerKernel::Block : pdsc::LayerKernel::Wave;
-    const int rc = pdsc::validate_layer_args(a, kernel, "pdsc_layer_fused");
-    return rc != PDSC_OK ? rc : pdsc::dispatch_layer(a, kernel, (hipStream_t)stream);
+// The kernel of a pdsc_layer_run call.  PDSC_LAYER_KERNEL_AUTO:
+//   natural-layout weights: two implementations.  layer_wave.hip (one wavefront per 32-point tile) wins once the tiles fill the
+//     chip; with few tiles its serial 46k matrix-pipe cycles per tile are the launch time, and this file's kernel, which spreads
+//     a tile over the four SIMDs of a CU, is faster (N = 1000, one pair: 0.68 vs 1.10 ms per forward).
+//     (experiments builds) PDSC_LAYER_VARIANT = block | wave overrides the size rule.
+//   fragment streams, point-fragment hand-offs: the H3 kernel alone reads / writes them; validate_layer_args rejects what it
+//     does not serve.
+//   fragment streams, plain rows: the pipelined kernel of layer_h3.hip for H3 streams and the output sets it serves, else
+//     layer_wave.hip (fp32 streams, or its own H3 form); (experiments builds) A/B knob PDSC_LAYER_H3_VARIANT = 0: never H3.
+// A forced kernel is taken as given: validate_layer_args rejects the arguments that do not fit it.
+static bool choose_layer_kernel(const pdsc_layer_call& c, const pdsc::LayerArgs& a, pdsc::LayerKernel* kernel) {
+    using pdsc::LayerKernel;
+    switch (c.kernel) {
+        case PDSC_LAYER_KERNEL_BLOCK: *kernel = LayerKernel::Block; return true;
+        case PDSC_LAYER_KERNEL_WAVE: *kernel = LayerKernel::Wave; return true;
+        case PDSC_LAYER_KERNEL_H3: *kernel = LayerKernel::H3; return true;
+        case PDSC_LAYER_KERNEL_X3: *kernel = LayerKernel::X3; return true;
+        case PDSC_LAYER_KERNEL_AUTO: break;
+        default: return false;
+    }
+    if (!a.wf_tail && !a.wf_head) {
+        const char* ev = pdsc::env_str("PDSC_LAYER_VARIANT");
+        const bool block = ev && (ev[0] == 'b' || ev[0] == 'w') ? ev[0] == 'b' : pdsc_layer_prefers_block(c.bs, c.N) != 0;
+        *kernel = block ? LayerKernel::Block : LayerKernel::Wave;
+    } else if (c.io_flags != 0) {
+        *kernel = LayerKernel::H3;
+    } else {
+        const bool h3 = c.gemm_format == PDSC_LAYER_GEMM_H3 && pdsc::env_int("PDSC_LAYER_H3_VARIANT", 1) != 0 &&
+                        pdsc::launch_layer_h3_fits(a, a.msg != nullptr || a.part_o != nullptr, a.featB_out != nullptr);
+        *kernel = h3 ? LayerKernel::H3 : LayerKernel::Wave;
+    }
+    return true;
 }
 
-extern "C" int pdsc_layer_fused(const float* msg, const float* res, const float* feat_in, float* feat_out,
-                                float* featB_out, float* qkv_out, const float* w1, const float* b1, const float* w2,
-                                const float* b2, const float* w3, const float* b3, const float* wp, const float* bp,
-                                const float* wq, const float* bq, int M, void* stream) {
-    if (featB_out) PDSC_REQUIRE(qkv_out, "pdsc_layer_fused: head needs qkv_out");
-    // this entry point sees the batch as ONE run of M independent rows (bs = 1, N = M)
-    return pdsc_layer_fused_split(msg, nullptr, nullptr, 0, 0, res, feat_in, feat_out, featB_out, qkv_out, nullptr, nullptr,
-                                  w1, b1, w2, b2, w3, b3, wp, bp, wq, bq, nullptr, 1, M, stream);
+extern "C" int pdsc_layer_run(const pdsc_layer_call* call, void* stream) {
+    PDSC_REQUIRE(call, "pdsc_layer_run: null call");
+    const pdsc_layer_call& c = *call;
+    const bool natural = c.w1 || c.b1 || c.w2 || c.b2 || c.w3 || c.b3 || c.wp || c.bp || c.wq || c.bq || c.wq_split;
+    PDSC_REQUIRE(!natural || (!c.wfrag_tail && !c.wfrag_head), "pdsc_layer_run: weights given in natural layout AND as fragment streams");
+    if (c.featB_out && !c.q_split && !c.kv_tiles) PDSC_REQUIRE(c.qkv_out, "pdsc_layer_run: head needs qkv_out when no split streams are given");
+    pdsc::LayerArgs a = pdsc::layer_args_from_call(c);
+    a.trace = c.io_flags ? nullptr : g_layer_trace;      // (the point-fragment route takes no trace: layer_args.h)
+    pdsc::LayerKernel kernel;
+    PDSC_REQUIRE(choose_layer_kernel(c, a, &kernel), "pdsc_layer_run: kernel=%d", c.kernel);
+    const int rc = pdsc::validate_layer_args(a, kernel, "pdsc_layer_run");
+    return rc != PDSC_OK ? rc : pdsc::dispatch_layer(a, kernel, (hipStream_t)stream);
 }

@@ -40,33 +40,30 @@ struct LayerArgs {
                              // skipped, its last tile is padded / zeroed from ITS count; NULL = every pair has N rows
 };
 
-// Which of the three fused-layer kernels a launch takes: the workgroup-per-tile kernel of layer.hip (natural-layout weights), the
-// wavefront-per-tile kernel of layer_wave.hip (natural weights or fragment streams) or the pipelined H3 kernel of layer_h3.hip
-// (H3 fragment streams; launch_layer_h3 hands launches of few tiles to layer_coop.hip itself).
-enum class LayerKernel { Block, Wave, H3 };
+// Which fused-layer kernel a launch takes: the workgroup-per-tile kernel of layer.hip (natural-layout weights), the
+// wavefront-per-tile kernel of layer_wave.hip (natural weights or fragment streams), the pipelined H3 kernel of layer_h3.hip
+// (H3 fragment streams; launch_layer_h3 hands launches of few tiles to layer_coop.hip itself) or the all-split kernel of
+// layer_split.hip (experiments builds; w1, w2, w3, wp, wq then point at the hi|lo matrices of the split-weight buffer).
+enum class LayerKernel { Block, Wave, H3, X3 };
 // key-split partials the kernel merges while it loads (merge_partials.h); larger splits go through attention_combine_kernel
 constexpr int layer_merge_limit(LayerKernel k) {
     return k == LayerKernel::Block ? MERGE_MAX_SPLIT_BLOCK : k == LayerKernel::H3 ? MERGE_MAX_SPLIT_H3 : MERGE_MAX_SPLIT;
 }
 
-// The input / output fields every route fills the same way; the weights and the fields below are the caller's.  They differ by
-// route, and the differences decide which kernel runs:
-//   route                         weights             trace              range_flag      io_flags / value_fold   wq_split
-//   natural (pdsc_layer_fused*)   w1..bq              pdsc_layer_trace   NULL            0 / 0                   optional
-//   fragment rows (_frag_fmt)     wf_tail / wf_head   pdsc_layer_trace   NULL            0 / 0                   --
-//   point fragments (_frag_io)    wf_tail / wf_head   NULL               forward's flag  caller's                --
-// (trace: launch_layer_h3 leaves the few-tile kernel of layer_coop.hip when it is set, and the product build's launch_layer_wave
-// rejects a launch with it.  range_flag: only the point-fragment route reports to the fp16 range sentinel so far; wiring the other
-// launchers is a follow-up with a test of its own.  nvalid / range_flag are NULL outside a forward.)
-inline LayerArgs layer_args_io(const float* msg, const float* part_o, const float* part_ml, int nsplit, int Npad, const float* res,
-                               const float* feat_in, float* feat_out, float* featB_out, float* qkv_out, void* q_split, void* kv_tiles,
-                               int bs, int N) {
+// The one mapping from the public call (include/pointdsc_hip.h) to the kernels' argument.  What the struct does not expose stays
+// zero: nvalid, range_flag and value_fold are the forward's own, trace is set by whoever launches (launch_layer_h3 leaves the
+// few-tile kernel of layer_coop.hip when it is set, and the product build's launch_layer_wave rejects a launch with it; only
+// the point-fragment route reports to the fp16 range sentinel so far).
+inline LayerArgs layer_args_from_call(const pdsc_layer_call& c) {
     LayerArgs a{};
-    a.msg = msg; a.part_o = part_o; a.part_ml = part_ml; a.nsplit = nsplit; a.Npad = Npad;
-    a.res = res; a.feat_in = feat_in; a.feat_out = feat_out; a.featB_out = featB_out; a.qkv_out = qkv_out;
-    a.qs = (sp16*)q_split; a.kv = (unsigned char*)kv_tiles;
-    a.N = N; a.bs = bs;
-    a.gemm_format = PDSC_LAYER_GEMM_F32;
+    a.msg = c.msg; a.part_o = c.part_o; a.part_ml = c.part_ml; a.nsplit = c.nsplit; a.Npad = c.Npad;
+    a.res = c.res; a.feat_in = c.feat_in; a.feat_out = c.feat_out; a.featB_out = c.featB_out; a.qkv_out = c.qkv_out;
+    a.qs = (sp16*)c.q_split; a.kv = (unsigned char*)c.kv_tiles;
+    a.w1 = (const float*)c.w1; a.b1 = c.b1; a.w2 = (const float*)c.w2; a.b2 = c.b2; a.w3 = (const float*)c.w3; a.b3 = c.b3;
+    a.wp = (const float*)c.wp; a.bp = c.bp; a.wq = (const float*)c.wq; a.bq = c.bq; a.wq_split = (const sp16*)c.wq_split;
+    a.wf_tail = (const unsigned char*)c.wfrag_tail; a.wf_head = (const unsigned char*)c.wfrag_head;
+    a.gemm_format = c.gemm_format; a.io_flags = c.io_flags;
+    a.N = c.N; a.bs = c.bs;
     return a;
 }
 
@@ -78,6 +75,7 @@ int dispatch_layer(const LayerArgs& a, LayerKernel kernel, hipStream_t st);
 int launch_layer_wave(const LayerArgs& a, bool tail, bool head, hipStream_t st);      // layer_wave.hip
 int launch_layer_h3(const LayerArgs& a, bool tail, bool head, hipStream_t st);        // layer_h3.hip (H3 fragment streams only)
 int launch_layer_h3_coop(const LayerArgs& a, bool tail, bool head, hipStream_t st);   // layer_coop.hip (same contract, few tiles)
+int launch_layer_x3(const LayerArgs& a, bool tail, bool head, hipStream_t st);        // layer_split.hip (experiments builds, else an error)
 bool launch_layer_h3_fits(const LayerArgs& a, bool tail, bool head);                  // ... and only this output set
 // the folded layer's weights of one layer (layer_wave.hip): wfold = W1f Wv [64][128] | b' [64] fp32, and its H3 tail / head streams
 int build_value_fold(const float* w1, const float* b1, const float* wqkv, const float* bqkv, const float* w2, const float* b2,

@@ -392,7 +392,7 @@ int launch_layer_h3_coop(const LayerArgs& a, bool tail, bool head, hipStream_t s
         else if (head && !tail && fb_pf) hipLaunchKernelGGL((layer_h3_coop_kernel<false, true, true, 4, true>), grid, block, 0, st, a);
         else if (tail && !head) hipLaunchKernelGGL((layer_h3_coop_kernel<true, false, false, 4, true>), grid, block, 0, st, a);
         else {
-            set_error("pdsc_layer_fused_frag(h3, four wavefronts per tile): the folded layer exists with point-fragment featB only");
+            set_error("pdsc_layer_run(h3, four wavefronts per tile): the folded layer exists with point-fragment featB only");
             return PDSC_ERR_ARG;
         }
     } else if (tail && head && fb_pf) hipLaunchKernelGGL((layer_h3_coop_kernel<true, true, true, 4>), grid, block, 0, st, a);
@@ -400,7 +400,7 @@ int launch_layer_h3_coop(const LayerArgs& a, bool tail, bool head, hipStream_t s
     else if (tail && head) hipLaunchKernelGGL((layer_h3_coop_kernel<true, true, false, 4>), grid, block, 0, st, a);
     else if (tail) hipLaunchKernelGGL((layer_h3_coop_kernel<true, false, false, 4>), grid, block, 0, st, a);
     else hipLaunchKernelGGL((layer_h3_coop_kernel<false, true, false, 4>), grid, block, 0, st, a);
-    return check_launch("pdsc_layer_fused_frag(h3, four wavefronts per tile)");
+    return check_launch("pdsc_layer_run(h3, four wavefronts per tile)");
 }
 
 }  // namespace pdsc

@@ -10,7 +10,7 @@
 //     and store work of one tile runs in the shadow of the next tile's matrix work.  Only the last tile of a stage,
 //     whose result the next stage's first MFMA needs, keeps its epilogue in line (5 of 24 tiles);
 //   * LDS round trips never stall the wave: a step reads the patch into a staging register and the NEXT step stores it.
-// Weights come as the PDSC_LAYER_GEMM_H3 fragment streams (pdsc_wfrag_build_*_fmt), one 8 KiB chunk (12 MFMAs) ahead of
+// Weights come as the PDSC_LAYER_GEMM_H3 fragment streams (pdsc_wfrag_build_tail / _head), one 8 KiB chunk (12 MFMAs) ahead of
 // use in two register buffers; eight wavefronts per CU each stream the whole 344 KiB per tile through the CU's vector L1.
 // Bound at 32 pairs: HBM (3.76 KB per point) and that L1 stream (64 B/clk/CU: 1024 clocks per chunk for 8 wavefronts).
 #include <stdlib.h>
@@ -446,7 +446,7 @@ int launch_layer_h3(const LayerArgs& a, bool tail, bool head, hipStream_t st) {
         else if (tail && !head) hipLaunchKernelGGL((layer_h3_kernel<true, false, false, 6, 0, false, LW_WAVES, 2, true>), grid, block, 0, st, a);
         else {
             if (timed) profile_mark_end(PDSC_PROF_LAYER, st);
-            set_error("pdsc_layer_fused_frag(h3): the folded layer exists with point-fragment featB only");
+            set_error("pdsc_layer_run(h3): the folded layer exists with point-fragment featB only");
             return PDSC_ERR_ARG;
         }
     } else if (tail && head && fb_pf) {
@@ -479,7 +479,7 @@ int launch_layer_h3(const LayerArgs& a, bool tail, bool head, hipStream_t st) {
 #undef PDSC_H3_LAUNCH
 #undef PDSC_H3_LAUNCH_EXTRA
     if (timed) profile_mark_end(PDSC_PROF_LAYER, st);
-    return check_launch("pdsc_layer_fused_frag(h3)");
+    return check_launch("pdsc_layer_run(h3)");
 }
 
 }  // namespace pdsc
@@ -493,19 +493,4 @@ extern "C" int pdsc_layer_h3_uses_coop(int bs, int N) {
     coop_tiles = env_int("PDSC_LAYER_H3_COOP", coop_tiles);
 #endif
     return (long long)bs * ceil_div(N, 32) <= coop_tiles ? 1 : 0;
-}
-
-extern "C" int pdsc_layer_fused_frag_io(const float* msg, const float* part_o, const float* part_ml, int nsplit, int Npad,
-                                        const float* res, const float* feat_in, float* feat_out, float* featB_out,
-                                        void* q_split, void* kv_tiles, const void* wfrag_tail, const void* wfrag_head,
-                                        int gemm_format, int io_flags, int bs, int N, void* stream) {
-    if (io_flags == 0)       // no point-fragment hand-off: the fragment-rows route and its kernel rule
-        return pdsc_layer_fused_frag_fmt(msg, part_o, part_ml, nsplit, Npad, res, feat_in, feat_out, featB_out, nullptr, q_split, kv_tiles,
-                                         wfrag_tail, wfrag_head, gemm_format, bs, N, stream);
-    LayerArgs a = layer_args_io(msg, part_o, part_ml, nsplit, Npad, res, feat_in, feat_out, featB_out, nullptr, q_split, kv_tiles, bs, N);
-    a.wf_tail = (const unsigned char*)wfrag_tail; a.wf_head = (const unsigned char*)wfrag_head;
-    a.gemm_format = gemm_format;
-    a.io_flags = io_flags;
-    const int rc = validate_layer_args(a, LayerKernel::H3, "pdsc_layer_fused_frag_io");
-    return rc != PDSC_OK ? rc : dispatch_layer(a, LayerKernel::H3, (hipStream_t)stream);
 }

@@ -272,9 +272,30 @@ __global__ __launch_bounds__(256, 3) void layer_x3_kernel(LayerX3Args a) {
 }
 
 template <bool T, bool H>
-static int launch_layer_x3(const LayerX3Args& a, hipStream_t st) {
+static int launch_x3(const LayerX3Args& a, hipStream_t st) {
     hipLaunchKernelGGL((layer_x3_kernel<T, H>), dim3(ceil_div(a.N, LX_ROWS), a.bs), dim3(256), 0, st, a);
-    return check_launch("pdsc_layer_fused_x3");
+    return check_launch("pdsc_layer_run(x3)");
+}
+
+// LayerKernel::X3 of dispatch_layer: the arguments were checked by validate_layer_args; a.w1 .. a.wq hold the hi|lo matrices
+int launch_layer_x3(const LayerArgs& l, bool tail, bool head, hipStream_t st) {
+    LayerX3Args a{};
+    a.msg = l.msg; a.part_o = l.part_o; a.part_ml = l.part_ml; a.nsplit = l.nsplit; a.Npad = l.Npad;
+    a.res = l.res; a.feat_in = l.feat_in; a.feat_out = l.feat_out; a.featB_out = l.featB_out; a.qkv_out = l.qkv_out;
+    a.qs = l.qs; a.kv = l.kv;
+    a.w1 = (const sp16*)l.w1; a.w2 = (const sp16*)l.w2; a.w3 = (const sp16*)l.w3; a.wp = (const sp16*)l.wp; a.wq = (const sp16*)l.wq;
+    a.b1 = l.b1; a.b2 = l.b2; a.b3 = l.b3; a.bp = l.bp; a.bq = l.bq;
+    a.N = l.N; a.bs = l.bs;
+    if (tail && head) return launch_x3<true, true>(a, st);
+    if (tail) return launch_x3<true, false>(a, st);
+    return launch_x3<false, true>(a, st);
+}
+
+#else
+
+int launch_layer_x3(const LayerArgs&, bool, bool, hipStream_t) {
+    set_error("pdsc_layer_run: the all-split layer kernel exists in experiments builds only (python -m pointdsc_amd.build --experiments)");
+    return PDSC_ERR_ARG;
 }
 
 #endif  // PDSC_EXPERIMENTS
@@ -356,13 +377,13 @@ extern "C" int pdsc_wsplit_build(const pdsc_config* cfg, const float* wpack, voi
         auto W = [&](int section) { return wpack + pdsc_wpack_offset(cfg, section, layer); };
         for (int fmt = PDSC_LAYER_GEMM_F32; fmt <= PDSC_LAYER_GEMM_H3; ++fmt) {
             const bool h3 = fmt == PDSC_LAYER_GEMM_H3;
-            int rc = pdsc_wfrag_build_tail_fmt(W(PDSC_W_FC1_W), W(PDSC_W_FC1_B), W(PDSC_W_FC2_W), W(PDSC_W_FC2_B), W(PDSC_W_FC3_W), W(PDSC_W_FC3_B),
-                                               (sp16*)wsplit + pdsc_wsplit_offset(cfg, h3 ? PDSC_WS_FRAG_TAIL_H3 : PDSC_WS_FRAG_TAIL, layer),
-                                               fmt, stream);
-            if (rc != PDSC_OK) return rc;
-            rc = pdsc_wfrag_build_head_fmt(W(PDSC_W_PCN_W), W(PDSC_W_PCN_B), W(PDSC_W_QKV_W), W(PDSC_W_QKV_B),
-                                           (sp16*)wsplit + pdsc_wsplit_offset(cfg, h3 ? PDSC_WS_FRAG_HEAD_H3 : PDSC_WS_FRAG_HEAD, layer),
+            int rc = pdsc_wfrag_build_tail(W(PDSC_W_FC1_W), W(PDSC_W_FC1_B), W(PDSC_W_FC2_W), W(PDSC_W_FC2_B), W(PDSC_W_FC3_W), W(PDSC_W_FC3_B),
+                                           (sp16*)wsplit + pdsc_wsplit_offset(cfg, h3 ? PDSC_WS_FRAG_TAIL_H3 : PDSC_WS_FRAG_TAIL, layer),
                                            fmt, stream);
+            if (rc != PDSC_OK) return rc;
+            rc = pdsc_wfrag_build_head(W(PDSC_W_PCN_W), W(PDSC_W_PCN_B), W(PDSC_W_QKV_W), W(PDSC_W_QKV_B),
+                                       (sp16*)wsplit + pdsc_wsplit_offset(cfg, h3 ? PDSC_WS_FRAG_HEAD_H3 : PDSC_WS_FRAG_HEAD, layer),
+                                       fmt, stream);
             if (rc != PDSC_OK) return rc;
         }
         if (cfg->value_fold == PDSC_VALUE_FOLD_ON) {
@@ -374,42 +395,4 @@ extern "C" int pdsc_wsplit_build(const pdsc_config* cfg, const float* wpack, voi
         }
     }
     return check_launch("pdsc_wsplit_build");
-}
-
-extern "C" int pdsc_layer_fused_x3(const float* msg, const float* part_o, const float* part_ml, int nsplit, int Npad,
-                                   const float* res, const float* feat_in, float* feat_out, float* featB_out, float* qkv_out,
-                                   void* q_split, void* kv_tiles, const void* w1, const float* b1, const void* w2,
-                                   const float* b2, const void* w3, const float* b3, const void* wp, const float* bp,
-                                   const void* wq, const float* bq, int bs, int N, void* stream) {
-#ifndef PDSC_EXPERIMENTS
-    (void)msg; (void)part_o; (void)part_ml; (void)nsplit; (void)Npad; (void)res; (void)feat_in; (void)feat_out; (void)featB_out; (void)qkv_out;
-    (void)q_split; (void)kv_tiles; (void)w1; (void)b1; (void)w2; (void)b2; (void)w3; (void)b3; (void)wp; (void)bp; (void)wq; (void)bq; (void)bs; (void)N; (void)stream;
-    set_error("pdsc_layer_fused_x3: the all-split layer kernel exists in experiments builds only (python -m pointdsc_amd.build --experiments)");
-    return PDSC_ERR_ARG;
-#else
-    const bool tail = msg != nullptr || part_o != nullptr, head = featB_out != nullptr;
-    PDSC_REQUIRE(tail || head, "pdsc_layer_fused_x3: neither tail (msg / partials) nor head (featB_out) requested");
-    PDSC_REQUIRE(bs > 0 && N > 0, "pdsc_layer_fused_x3: bs=%d N=%d", bs, N);
-    if (tail) {
-        PDSC_REQUIRE(res && w1 && b1 && w2 && b2 && w3 && b3, "pdsc_layer_fused_x3: tail needs res, fc1..fc3");
-        if (!msg) PDSC_REQUIRE(part_ml && nsplit >= 1 && nsplit <= MERGE_MAX_SPLIT && Npad >= N,
-                               "pdsc_layer_fused_x3: partials need part_ml, 1 <= nsplit <= %d, Npad >= N", MERGE_MAX_SPLIT);
-        PDSC_REQUIRE(head || feat_out, "pdsc_layer_fused_x3: tail-only needs feat_out");
-    } else {
-        PDSC_REQUIRE(feat_in, "pdsc_layer_fused_x3: head-only needs feat_in");
-    }
-    if (head) PDSC_REQUIRE((qkv_out || q_split) && wp && bp && wq && bq, "pdsc_layer_fused_x3: head needs qkv_out or the split streams, pcn, qkv weights");
-    PDSC_REQUIRE((q_split == nullptr) == (kv_tiles == nullptr), "pdsc_layer_fused_x3: q_split and kv_tiles go together");
-    LayerX3Args a{};
-    a.msg = msg; a.part_o = part_o; a.part_ml = part_ml; a.nsplit = nsplit; a.Npad = Npad;
-    a.res = res; a.feat_in = feat_in; a.feat_out = feat_out; a.featB_out = featB_out; a.qkv_out = qkv_out;
-    a.qs = (sp16*)q_split; a.kv = (unsigned char*)kv_tiles;
-    a.w1 = (const sp16*)w1; a.w2 = (const sp16*)w2; a.w3 = (const sp16*)w3; a.wp = (const sp16*)wp; a.wq = (const sp16*)wq;
-    a.b1 = b1; a.b2 = b2; a.b3 = b3; a.bp = bp; a.bq = bq;
-    a.N = N; a.bs = bs;
-    hipStream_t st = (hipStream_t)stream;
-    if (tail && head) return launch_layer_x3<true, true>(a, st);
-    if (tail) return launch_layer_x3<true, false>(a, st);
-    return launch_layer_x3<false, true>(a, st);
-#endif
 }

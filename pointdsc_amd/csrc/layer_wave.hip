@@ -411,7 +411,7 @@ int launch_layer_wave(const LayerArgs& a, bool tail, bool head, hipStream_t st) 
     // two do not).  The natural-layout split-weight form and the shader-clock trace are compiled in experiments builds only
     // (python -m pointdsc_amd.build --experiments).
     if (a.trace || (x3 && !frag)) {
-        set_error("pdsc_layer_fused: this form of the wavefront-per-tile kernel (%s) exists in experiments builds of the library only",
+        set_error("pdsc_layer_run: this form of the wavefront-per-tile kernel (%s) exists in experiments builds of the library only",
                   a.trace ? "shader-clock trace" : "split q|k|v weights in natural layout");
         return PDSC_ERR_ARG;
     }
@@ -441,7 +441,7 @@ int launch_layer_wave(const LayerArgs& a, bool tail, bool head, hipStream_t st) 
         else if (frag) hipLaunchKernelGGL((layer_wave_kernel<false, true, true, true>), grid, block, 0, st, a);
         else hipLaunchKernelGGL((layer_wave_kernel<false, true, false, false>), grid, block, 0, st, a);
     }
-    return check_launch("pdsc_layer_fused(wave)");
+    return check_launch("pdsc_layer_run(wave)");
 }
 
 }  // namespace pdsc
@@ -486,8 +486,8 @@ int pdsc::build_value_fold(const float* w1, const float* b1, const float* wqkv, 
     return check_launch("pdsc_wsplit_build(value fold)");
 }
 
-extern "C" int pdsc_wfrag_build_tail_fmt(const float* w1, const float* b1, const float* w2, const float* b2, const float* w3,
-                                         const float* b3, void* out, int gemm_format, void* stream) {
+extern "C" int pdsc_wfrag_build_tail(const float* w1, const float* b1, const float* w2, const float* b2, const float* w3,
+                                     const float* b3, void* out, int gemm_format, void* stream) {
     PDSC_REQUIRE(w1 && b1 && w2 && b2 && w3 && b3 && out, "pdsc_wfrag_build_tail: null pointer");
     PDSC_REQUIRE(gemm_format == PDSC_LAYER_GEMM_F32 || gemm_format == PDSC_LAYER_GEMM_H3, "pdsc_wfrag_build_tail: gemm_format=%d", gemm_format);
     hipLaunchKernelGGL(wfrag_tail_kernel<false>, dim3(LW_TAIL_CHUNKS * 8 * 64 / 256), dim3(256), 0, (hipStream_t)stream, w1, b1, w2, b2, w3, b3,
@@ -495,44 +495,11 @@ extern "C" int pdsc_wfrag_build_tail_fmt(const float* w1, const float* b1, const
     return check_launch("pdsc_wfrag_build_tail");
 }
 
-extern "C" int pdsc_wfrag_build_head_fmt(const float* wp, const float* bp, const float* wq, const float* bq, void* out,
-                                         int gemm_format, void* stream) {
+extern "C" int pdsc_wfrag_build_head(const float* wp, const float* bp, const float* wq, const float* bq, void* out,
+                                     int gemm_format, void* stream) {
     PDSC_REQUIRE(wp && bp && wq && bq && out, "pdsc_wfrag_build_head: null pointer");
     PDSC_REQUIRE(gemm_format == PDSC_LAYER_GEMM_F32 || gemm_format == PDSC_LAYER_GEMM_H3, "pdsc_wfrag_build_head: gemm_format=%d", gemm_format);
     hipLaunchKernelGGL(wfrag_head_kernel<false>, dim3(LW_HEAD_CHUNKS * 8 * 64 / 256), dim3(256), 0, (hipStream_t)stream, wp, bp, wq, bq,
                        nullptr, (unsigned char*)out, gemm_format);
     return check_launch("pdsc_wfrag_build_head");
-}
-
-extern "C" int pdsc_wfrag_build_tail(const float* w1, const float* b1, const float* w2, const float* b2, const float* w3,
-                                     const float* b3, void* out, void* stream) {
-    return pdsc_wfrag_build_tail_fmt(w1, b1, w2, b2, w3, b3, out, PDSC_LAYER_GEMM_F32, stream);
-}
-
-extern "C" int pdsc_wfrag_build_head(const float* wp, const float* bp, const float* wq, const float* bq, void* out, void* stream) {
-    return pdsc_wfrag_build_head_fmt(wp, bp, wq, bq, out, PDSC_LAYER_GEMM_F32, stream);
-}
-
-extern "C" int pdsc_layer_fused_frag_fmt(const float* msg, const float* part_o, const float* part_ml, int nsplit, int Npad,
-                                         const float* res, const float* feat_in, float* feat_out, float* featB_out,
-                                         float* qkv_out, void* q_split, void* kv_tiles, const void* wfrag_tail,
-                                         const void* wfrag_head, int gemm_format, int bs, int N, void* stream) {
-    LayerArgs a = layer_args_io(msg, part_o, part_ml, nsplit, Npad, res, feat_in, feat_out, featB_out, qkv_out, q_split, kv_tiles, bs, N);
-    a.wf_tail = (const unsigned char*)wfrag_tail; a.wf_head = (const unsigned char*)wfrag_head;
-    a.gemm_format = gemm_format;
-    a.trace = pdsc_layer_trace_buffer();
-    // H3: the pipelined kernel of layer_h3.hip; A/B knob PDSC_LAYER_H3_VARIANT = 0: this file's kernel with the H3 GEMMs
-    const bool h3 = gemm_format == PDSC_LAYER_GEMM_H3 && env_int("PDSC_LAYER_H3_VARIANT", 1) != 0 &&
-                    launch_layer_h3_fits(a, msg != nullptr || part_o != nullptr, featB_out != nullptr);
-    const LayerKernel kernel = h3 ? LayerKernel::H3 : LayerKernel::Wave;
-    const int rc = validate_layer_args(a, kernel, "pdsc_layer_fused_frag");
-    return rc != PDSC_OK ? rc : dispatch_layer(a, kernel, (hipStream_t)stream);
-}
-
-extern "C" int pdsc_layer_fused_frag(const float* msg, const float* part_o, const float* part_ml, int nsplit, int Npad,
-                                     const float* res, const float* feat_in, float* feat_out, float* featB_out,
-                                     float* qkv_out, void* q_split, void* kv_tiles, const void* wfrag_tail,
-                                     const void* wfrag_head, int bs, int N, void* stream) {
-    return pdsc_layer_fused_frag_fmt(msg, part_o, part_ml, nsplit, Npad, res, feat_in, feat_out, featB_out, qkv_out, q_split, kv_tiles,
-                                     wfrag_tail, wfrag_head, PDSC_LAYER_GEMM_F32, bs, N, stream);
 }

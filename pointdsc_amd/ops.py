@@ -134,23 +134,68 @@ def layer0(corr_pos: torch.Tensor, w0_padded: torch.Tensor, b0: torch.Tensor) ->
     return y
 
 
+LAYER_GEMMS = {"f32": 0, "h3": 1}      # enum pdsc_layer_gemm
+LAYER_KERNELS = {"auto": 0, "block": 1, "wave": 2, "h3": 3, "x3": 4}      # enum pdsc_layer_kernel
+PF_PARTIALS, PF_RES, PF_FEATB = 1, 2, 4      # enum pdsc_layer_io
+_TAIL_W, _HEAD_W = ("w1", "b1", "w2", "b2", "w3", "b3"), ("wp", "bp", "wq", "bq")
+
+
+def pf_rows(n: int) -> int:
+    """rows per pair of a point-fragment buffer: whole tiles of 32."""
+    return (n + 31) // 32 * 32
+
+
+def _natural_weights(tail_w, head_w) -> dict:
+    """(w1,b1,w2,b2,w3,b3) / (wp,bp,wq,bq), either may be None -> the natural-layout weight fields of pdsc_layer_call."""
+    w = {k: _chk(t, "tail_w") for k, t in zip(_TAIL_W, tail_w or ())}
+    w.update({k: _chk(t, "head_w") for k, t in zip(_HEAD_W, head_w or ())})
+    return w
+
+
+def _layer_run(bs: int, n: int, weights: dict, msg=None, partials=None, res=None, feat_in=None, want_feat=False, want_qkv=False,
+               want_streams=True, gemm: str = "f32", io_flags: int = 0, kernel: str = "auto"):
+    """Every fused-layer wrapper below: allocate the outputs, fill one pdsc_layer_call, pdsc_layer_run.
+    weights: pdsc_layer_call field name -> tensor; the tail runs when it holds w1 or wfrag_tail, the head when it holds wp or
+    wfrag_head.  partials = (scratch, nsplit) of sc_attention_split(..., merge=False) replaces msg.
+    Returns (feat or None, featB or None, qkv or None, q_split or None, kv_tiles or None); feat comes back when asked for or when
+    there is no head, featB holds whole tiles per pair when it is written in point-fragment order."""
+    lib = _lib.load()
+    has_tail, has_head = "w1" in weights or "wfrag_tail" in weights, "wp" in weights or "wfrag_head" in weights
+    dev = next(t for t in (res, feat_in, msg) if t is not None).device
+    m = bs * n
+
+    def new(rows, cols):
+        return torch.empty(rows, cols, device=dev, dtype=torch.float32)
+
+    feat = new(m, 128) if has_tail and (want_feat or not has_head) else None
+    featB = new(bs * pf_rows(n) if io_flags & PF_FEATB else m, 128) if has_head else None
+    qkv = new(m, 384) if has_head and want_qkv else None
+    streams = has_head and want_streams
+    qs = torch.empty(int(lib.pdsc_split_q_bytes(bs, n)), device=dev, dtype=torch.uint8) if streams else None
+    kv = torch.zeros(int(lib.pdsc_split_kv_bytes(bs, n)), device=dev, dtype=torch.uint8) if streams else None
+    call = _lib.PdscLayerCall(bs=bs, N=n, gemm_format=LAYER_GEMMS[gemm], io_flags=io_flags, kernel=LAYER_KERNELS[kernel])
+    if partials is not None:
+        scratch, call.nsplit = partials
+        call.Npad = (n + 255) // 256 * 256
+        call.part_o = scratch.data_ptr()
+        call.part_ml = scratch.data_ptr() + bs * call.nsplit * call.Npad * 128 * 4
+    inputs = {k: _chk(t, k) for k, t in (("msg", msg), ("res", res), ("feat_in", feat_in)) if t is not None}
+    outputs = dict(feat_out=feat, featB_out=featB, qkv_out=qkv, q_split=qs, kv_tiles=kv)
+    for k, t in {**inputs, **outputs, **weights}.items():
+        if t is not None:
+            setattr(call, k, t.data_ptr())
+    _lib.check(lib.pdsc_layer_run(C.byref(call), _stream()), "pdsc_layer_run")
+    return feat, featB, qkv, qs, kv
+
+
 @_on_device
 def layer_fused(msg, res, feat_in, tail_w=None, head_w=None, want_feat=False):
-    """Fused point-wise chain (pdsc_layer_fused).  tail_w = (w1,b1,w2,b2,w3,b3) folded fc_message of layer i,
-    head_w = (wp,bp,wq,bq) folded PointCN / stacked qkv of layer i+1.  Returns (feat or None, featB or None, qkv or None)."""
-    lib = _lib.load()
+    """Fused point-wise chain over one run of independent rows (pdsc_layer_run with bs = 1, N = rows).  tail_w =
+    (w1,b1,w2,b2,w3,b3) folded fc_message of layer i, head_w = (wp,bp,wq,bq) folded PointCN / stacked qkv of layer i+1.
+    Returns (feat or None, featB or None, qkv or None)."""
     src = msg if msg is not None else feat_in
-    m, dev = src.shape[0], src.device
-    tail = [_chk(w, "tail_w") for w in tail_w] if tail_w is not None else [None] * 6
-    head = [_chk(w, "head_w") for w in head_w] if head_w is not None else [None] * 4
-    feat = torch.empty(m, 128, device=dev, dtype=torch.float32) if (want_feat or head_w is None) else None
-    featB = torch.empty(m, 128, device=dev, dtype=torch.float32) if head_w is not None else None
-    qkv = torch.empty(m, 384, device=dev, dtype=torch.float32) if head_w is not None else None
-    args = [_p(_chk(msg, "msg")) if msg is not None else None, _p(_chk(res, "res")) if res is not None else None,
-            _p(_chk(feat_in, "feat_in")) if feat_in is not None else None, _p(feat), _p(featB), _p(qkv)]
-    args += [_p(w) for w in tail] + [_p(w) for w in head]
-    _lib.check(lib.pdsc_layer_fused(*args, m, _stream()), "pdsc_layer_fused")
-    return feat, featB, qkv
+    return _layer_run(1, src.shape[0], _natural_weights(tail_w, head_w), msg=msg, res=res, feat_in=feat_in, want_feat=want_feat,
+                      want_qkv=True, want_streams=False)[:3]
 
 
 @_on_device
@@ -182,7 +227,7 @@ def pack_qkv_split(qkv: torch.Tensor, bs: int, n: int):
 def sc_attention_split(q_split: torch.Tensor, kv_tiles: torch.Tensor, compat: torch.Tensor, bs: int, n: int,
                        nsplit: int = 0, merge: bool = True, layout: str = "rows"):
     """Split-precision (fp16 hi/lo, three MFMAs per operand pair) attention on the packed streams -> msg [bs*N,128].
-    merge=False (needs a key split > 1): returns (scratch, nsplit) with the un-merged partials for layer_fused_x3;
+    merge=False (needs a key split > 1): returns (scratch, nsplit) with the un-merged partials for the fused layer wrappers;
     layout="pf": those partials in point-fragment order (csrc/split_layout.h) for layer_fused_io."""
     lib = _lib.load()
     c16 = compat.dtype == torch.int16                  # unorm16 matrix of spatial_compat_u16
@@ -204,17 +249,14 @@ def sc_attention_split(q_split: torch.Tensor, kv_tiles: torch.Tensor, compat: to
     return msg if merge else (scratch, nsplit)
 
 
-LAYER_GEMMS = {"f32": 0, "h3": 1}      # enum pdsc_layer_gemm
-
-
 @_on_device
 def frag_weights_tail(tail_w, gemm: str = "f32") -> torch.Tensor:
-    """(fc1 w, b, fc2 w, b, fc3 w, b) fp32 [out][in] -> the fragment-ordered tail stream of pdsc_layer_fused_frag(_fmt);
+    """(fc1 w, b, fc2 w, b, fc3 w, b) fp32 [out][in] -> the fragment-ordered tail stream (pdsc_layer_call.wfrag_tail);
     gemm = "h3": the chunks as fp16 hi / scaled-lo pairs (enum pdsc_layer_gemm)."""
     lib = _lib.load()
     out = torch.empty(int(lib.pdsc_wfrag_tail_bytes()), dtype=torch.uint8, device=tail_w[0].device)
-    _lib.check(lib.pdsc_wfrag_build_tail_fmt(*[_p(_chk(w, "tail_w")) for w in tail_w], _p(out), LAYER_GEMMS[gemm], _stream()),
-               "pdsc_wfrag_build_tail_fmt")
+    _lib.check(lib.pdsc_wfrag_build_tail(*[_p(_chk(w, "tail_w")) for w in tail_w], _p(out), LAYER_GEMMS[gemm], _stream()),
+               "pdsc_wfrag_build_tail")
     return out
 
 
@@ -224,64 +266,41 @@ def frag_weights_head(head_w, gemm: str = "f32") -> torch.Tensor:
     one more k-step -> the head stream."""
     lib = _lib.load()
     out = torch.empty(int(lib.pdsc_wfrag_head_bytes()), dtype=torch.uint8, device=head_w[0].device)
-    _lib.check(lib.pdsc_wfrag_build_head_fmt(*[_p(_chk(w, "head_w")) for w in head_w], _p(out), LAYER_GEMMS[gemm], _stream()),
-               "pdsc_wfrag_build_head_fmt")
+    _lib.check(lib.pdsc_wfrag_build_head(*[_p(_chk(w, "head_w")) for w in head_w], _p(out), LAYER_GEMMS[gemm], _stream()),
+               "pdsc_wfrag_build_head")
     return out
+
+
+def _frag_weights(tail_w, head_w, gemm: str) -> dict:
+    """... or the fragment-stream fields, built in `gemm` format from the same tuples."""
+    w = {"wfrag_tail": frag_weights_tail(tail_w, gemm)} if tail_w is not None else {}
+    if head_w is not None:
+        w["wfrag_head"] = frag_weights_head(head_w, gemm)
+    return w
 
 
 @_on_device
 def layer_fused_split(msg, res, feat_in, tail_w, head_w, bs: int, n: int, want_qkv: bool = False, partials=None,
                       qkv_split: bool = False, frag: bool = False, gemm: str = "f32", want_feat: bool = True):
-    """pdsc_layer_fused_split: like layer_fused, rows = bs pairs of n points, head emits the split streams.
+    """Like layer_fused, rows = bs pairs of n points, head emits the split streams (pdsc_layer_run, kernel chosen by the library).
     partials = (scratch, nsplit) from sc_attention_split(..., merge=False) replaces msg.
     qkv_split: run the q|k|v projection in split precision (fp16 hi/lo weights).
-    frag: go through pdsc_layer_fused_frag (weights as fragment-ordered streams; implies qkv_split) -- the entry the
-    forward uses; gemm = "h3" (frag only): fc1..fc3 / PointCN in the fp16 hi / scaled-lo arithmetic.
+    frag: weights as fragment-ordered streams (implies qkv_split) -- what the forward uses; gemm = "h3" (frag only):
+    fc1..fc3 / PointCN in the fp16 hi / scaled-lo arithmetic.
     want_feat = False: no feat output (what the forward asks of every layer but the last); head_w = None (frag only):
     tail only (the forward's last layer).
     Returns (feat or None, featB or None, qkv or None, q_split or None, kv_tiles or None)."""
-    lib = _lib.load()
-    src = res if res is not None else feat_in
-    m, dev = src.shape[0], src.device
-    assert m == bs * n
-    tail = [_chk(w, "tail_w") for w in tail_w] if tail_w is not None else [None] * 6
-    has_head = head_w is not None
-    assert has_head or frag, "tail-only launches exist on fragment streams only"
-    head = [_chk(w, "head_w") for w in head_w] if has_head else [None] * 4
-    feat = torch.empty(m, 128, device=dev, dtype=torch.float32) if tail_w is not None and (want_feat or not has_head) else None
-    featB = torch.empty(m, 128, device=dev, dtype=torch.float32) if has_head else None
-    qkv = torch.empty(m, 384, device=dev, dtype=torch.float32) if want_qkv and has_head else None
-    qs = torch.empty(int(lib.pdsc_split_q_bytes(bs, n)), device=dev, dtype=torch.uint8) if has_head else None
-    kv = torch.zeros(int(lib.pdsc_split_kv_bytes(bs, n)), device=dev, dtype=torch.uint8) if has_head else None
-    part_o = part_ml = None
-    nsplit = npad = 0
-    if partials is not None:
-        scratch, nsplit = partials
-        npad = (n + 255) // 256 * 256
-        part_o = C.c_void_p(scratch.data_ptr())
-        part_ml = C.c_void_p(scratch.data_ptr() + bs * nsplit * npad * 128 * 4)
-    args = [_p(_chk(msg, "msg")) if msg is not None else None, part_o, part_ml, nsplit, npad,
-            _p(_chk(res, "res")) if res is not None else None,
-            _p(_chk(feat_in, "feat_in")) if feat_in is not None else None, _p(feat), _p(featB), _p(qkv), _p(qs), _p(kv)]
+    assert (res if res is not None else feat_in).shape[0] == bs * n
+    assert head_w is not None or frag, "tail-only launches exist on fragment streams only"
     if frag:
-        wf_tail = frag_weights_tail(tail, gemm) if tail_w is not None else None
-        wf_head = frag_weights_head(head, gemm) if has_head else None
-        args += [_p(wf_tail), _p(wf_head)]
-        _lib.check(lib.pdsc_layer_fused_frag_fmt(*args, LAYER_GEMMS[gemm], bs, n, _stream()), "pdsc_layer_fused_frag_fmt")
-        return feat, featB, qkv, qs, kv
-    assert gemm == "f32", "the H3 arithmetic exists on fragment streams only"
-    args += [_p(w) for w in tail] + [_p(w) for w in head]
-    wqs = split_weight(head[2]) if qkv_split else None
-    _lib.check(lib.pdsc_layer_fused_split(*args, _p(wqs), bs, n, _stream()), "pdsc_layer_fused_split")
-    return feat, featB, qkv, qs, kv
-
-
-PF_PARTIALS, PF_RES, PF_FEATB = 1, 2, 4      # enum pdsc_layer_io
-
-
-def pf_rows(n: int) -> int:
-    """rows per pair of a point-fragment buffer: whole tiles of 32."""
-    return (n + 31) // 32 * 32
+        weights = _frag_weights(tail_w, head_w, gemm)
+    else:
+        assert gemm == "f32", "the H3 arithmetic exists on fragment streams only"
+        weights = _natural_weights(tail_w, head_w)
+        if qkv_split:
+            weights["wq_split"] = split_weight(weights["wq"])
+    return _layer_run(bs, n, weights, msg=msg, partials=partials, res=res, feat_in=feat_in, want_feat=want_feat, want_qkv=want_qkv,
+                      gemm=gemm)
 
 
 def rows_to_pf(x: torch.Tensor, bs: int, n: int) -> torch.Tensor:
@@ -302,33 +321,13 @@ def pf_to_rows(x: torch.Tensor, bs: int, rows_per_pair: int) -> torch.Tensor:
 
 @_on_device
 def layer_fused_io(res, feat_in, tail_w, head_w, bs: int, n: int, io_flags: int, partials=None):
-    """pdsc_layer_fused_frag_io (H3 GEMMs, the forward's output set, hand-offs in point-fragment order per io_flags):
+    """H3 fragment streams, the forward's output set, hand-offs in point-fragment order per io_flags (pdsc_layer_call.io_flags):
     partials = (scratch, nsplit) of sc_attention_split(merge=False, layout "pf" if io_flags & PF_PARTIALS);
     res in PF order if io_flags & PF_RES; featB comes back in PF order if io_flags & PF_FEATB.
     tail_w None = head only (feat_in rows), head_w None = tail only.  Returns (feat or None, featB or None, q_split, kv_tiles)."""
-    lib = _lib.load()
-    dev = (res if res is not None else feat_in).device
-    m = bs * n
-    has_tail, has_head = tail_w is not None, head_w is not None
-    feat = torch.empty(m, 128, device=dev, dtype=torch.float32) if has_tail and not has_head else None
-    fb_rows = bs * pf_rows(n) if io_flags & PF_FEATB else m
-    featB = torch.empty(fb_rows * 128, device=dev, dtype=torch.float32) if has_head else None
-    qs = torch.empty(int(lib.pdsc_split_q_bytes(bs, n)), device=dev, dtype=torch.uint8) if has_head else None
-    kv = torch.zeros(int(lib.pdsc_split_kv_bytes(bs, n)), device=dev, dtype=torch.uint8) if has_head else None
-    part_o = part_ml = None
-    nsplit = npad = 0
-    if partials is not None:
-        scratch, nsplit = partials
-        npad = (n + 255) // 256 * 256
-        part_o = C.c_void_p(scratch.data_ptr())
-        part_ml = C.c_void_p(scratch.data_ptr() + bs * nsplit * npad * 128 * 4)
-    wf_tail = frag_weights_tail([_chk(w, "tail_w") for w in tail_w], "h3") if has_tail else None
-    wf_head = frag_weights_head([_chk(w, "head_w") for w in head_w], "h3") if has_head else None
-    _lib.check(lib.pdsc_layer_fused_frag_io(None, part_o, part_ml, nsplit, npad, _p(res) if res is not None else None,
-                                            _p(_chk(feat_in, "feat_in")) if feat_in is not None else None, _p(feat), _p(featB),
-                                            _p(qs), _p(kv), _p(wf_tail), _p(wf_head), LAYER_GEMMS["h3"], io_flags, bs, n, _stream()),
-               "pdsc_layer_fused_frag_io")
-    return feat, featB, qs, kv
+    feat, featB, _, qs, kv = _layer_run(bs, n, _frag_weights(tail_w, head_w, "h3"), partials=partials, res=res, feat_in=feat_in,
+                                        gemm="h3", io_flags=io_flags)
+    return feat, None if featB is None else featB.reshape(-1), qs, kv
 
 
 def split_weight(w: torch.Tensor) -> torch.Tensor:
@@ -342,46 +341,14 @@ def split_weight(w: torch.Tensor) -> torch.Tensor:
 @_on_device
 def layer_fused_x3(msg, res, feat_in, tail_w, head_w, bs: int, n: int, partials=None, want_qkv: bool = False,
                    want_feat: bool = False):
-    """pdsc_layer_fused_x3 (split-precision chain).  tail_w/head_w as in layer_fused (fp32 matrices; split here).
+    """The all-split layer kernel (pdsc_layer_run with PDSC_LAYER_KERNEL_X3; experiments builds).  tail_w/head_w as in
+    layer_fused (fp32 matrices; split here).
     partials = (scratch uint8 tensor, nsplit) left by sc_attention_split(..., merge=False) replaces msg.
     Returns (feat or None, featB or None, qkv or None, q_split or None, kv_tiles or None)."""
-    lib = _lib.load()
-    src = res if res is not None else feat_in
-    m, dev = src.shape[0], src.device
-    assert m == bs * n
-    tail = list(tail_w) if tail_w is not None else [None] * 6
-    head = list(head_w) if head_w is not None else [None] * 4
-    keep = []
-
-    def mat(w):
-        if w is None:
-            return None
-        keep.append(split_weight(w))
-        return _p(keep[-1])
-
-    def vec(b):
-        return None if b is None else _p(_chk(b, "bias"))
-
-    has_tail, has_head = tail_w is not None, head_w is not None
-    feat = torch.empty(m, 128, device=dev, dtype=torch.float32) if (has_tail and (want_feat or not has_head)) else None
-    featB = torch.empty(m, 128, device=dev, dtype=torch.float32) if has_head else None
-    qkv = torch.empty(m, 384, device=dev, dtype=torch.float32) if (has_head and want_qkv) else None
-    qs = torch.empty(int(lib.pdsc_split_q_bytes(bs, n)), device=dev, dtype=torch.uint8) if has_head else None
-    kv = torch.zeros(int(lib.pdsc_split_kv_bytes(bs, n)), device=dev, dtype=torch.uint8) if has_head else None
-    part_o = part_ml = None
-    nsplit = npad = 0
-    if partials is not None:
-        scratch, nsplit = partials
-        npad = (n + 255) // 256 * 256
-        part_o = C.c_void_p(scratch.data_ptr())
-        part_ml = C.c_void_p(scratch.data_ptr() + bs * nsplit * npad * 128 * 4)
-    args = [_p(_chk(msg, "msg")) if msg is not None else None, part_o, part_ml, nsplit, npad,
-            _p(_chk(res, "res")) if res is not None else None, _p(_chk(feat_in, "feat_in")) if feat_in is not None else None,
-            _p(feat), _p(featB), _p(qkv), _p(qs), _p(kv),
-            mat(tail[0]), vec(tail[1]), mat(tail[2]), vec(tail[3]), mat(tail[4]), vec(tail[5]),
-            mat(head[0]), vec(head[1]), mat(head[2]), vec(head[3])]
-    _lib.check(lib.pdsc_layer_fused_x3(*args, bs, n, _stream()), "pdsc_layer_fused_x3")
-    return feat, featB, qkv, qs, kv
+    assert (res if res is not None else feat_in).shape[0] == bs * n
+    weights = {k: split_weight(t) if k[0] == "w" else t for k, t in _natural_weights(tail_w, head_w).items()}
+    return _layer_run(bs, n, weights, msg=msg, partials=partials, res=res, feat_in=feat_in, want_feat=want_feat, want_qkv=want_qkv,
+                      kernel="x3")
 
 
 STATS_COLUMNS = ("success", "RE_deg", "TE_cm", "num_gt_inliers", "gt_inlier_ratio", "num_true_positives", "precision", "recall", "f1")

@@ -217,7 +217,7 @@ def test_forward_with_twelve_input_columns():
 
 @pytest.mark.parametrize("m", [1, 31, 32, 33, 1000])
 def test_layer_fused_matches_fp64_chain(m):
-    """pdsc_layer_fused (tail+head, head only, tail only) vs the five GEMMs in fp64."""
+    """pdsc_layer_run on natural-layout weights (tail+head, head only, tail only) vs the five GEMMs in fp64."""
     gen = torch.Generator().manual_seed(m)
     rnd = lambda *shape: torch.randn(*shape, generator=gen)  # noqa: E731
     msg, res = rnd(m, 128), rnd(m, 128)
@@ -402,8 +402,8 @@ def test_layer_fused_split_precision_qkv_projection(n, bs):
 
 @pytest.mark.parametrize("n,bs", [(1, 1), (33, 2), (1000, 3), (3000, 3)])
 def test_layer_fused_frag_streams_match_natural_weights(n, bs):
-    """pdsc_layer_fused_frag (the forward's entry for large problems: wavefront-resident kernel, weights as
-    MFMA-fragment-ordered streams, bias as one more k-step) against pdsc_layer_fused_split on natural-layout weights
+    """pdsc_layer_run on fragment streams (the forward's form for large problems: wavefront-resident kernel, weights as
+    MFMA-fragment-ordered streams, bias as one more k-step) against pdsc_layer_run on natural-layout weights
     (which takes the workgroup-per-tile kernel for small problems: other summation order, so fp32 round-off apart)
     and against the fp64 chain; its streams are exactly the packing of its own q|k|v; head-only reproduces it."""
     gen = torch.Generator().manual_seed(200 + n)
@@ -478,7 +478,7 @@ def test_block_layer_kernel_merges_up_to_eight_partials(n, bs, nsplit):
 
 @pytest.mark.parametrize("n,bs,nsplit", [(257, 1, 2), (1000, 2, 3), (300, 3, 4), (5000, 2, 2)])
 def test_layer_fused_frag_merges_attention_partials(n, bs, nsplit):
-    """pdsc_layer_fused_frag = layer_wave_kernel (the kernel the bench times) fed the UN-MERGED key-split partials
+    """pdsc_layer_run on fragment streams = layer_wave_kernel (the kernel the bench times) fed the UN-MERGED key-split partials
     (part_o / part_ml, nsplit 2..4) == the same kernel fed the merged msg of the combine kernel, and == the fp64 merge."""
     gen = torch.Generator().manual_seed(n + 1)
     rnd = lambda *shape: torch.randn(*shape, generator=gen)  # noqa: E731
@@ -625,7 +625,7 @@ def test_layer_fused_frag_h3_gemms_match_the_fp32_gemms(n, bs):
 def test_layer_h3_pipelined_kernel_is_bit_identical_to_the_generic_one(n, bs, nsplit):
     """layer_h3_kernel (csrc/layer_h3.hip: branch-free chunk loop, epilogues under the next tile's MFMAs -- what the forward
     runs with layer_gemm = "h3") takes exactly the output set the forward asks for; with any other set
-    pdsc_layer_fused_frag_fmt falls back to layer_wave_kernel's H3 form.  Same MFMAs in the same order: every stream and row
+    pdsc_layer_run falls back to layer_wave_kernel's H3 form.  Same MFMAs in the same order: every stream and row
     must agree bit for bit, for tail + head, head only and tail only, on merged msg and on un-merged partials, with ragged
     last tiles (the pipelined kernel stores unpredicated: rows beyond a pair's end repeat its last row)."""
     gen = torch.Generator().manual_seed(400 + n)

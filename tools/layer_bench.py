@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Times pdsc_layer_fused_frag_fmt alone (merge of the attention partials + tail + head, the forward's output set) at the
+"""Times pdsc_layer_run alone on fragment streams (merge of the attention partials + tail + head, the forward's output set) at the
 bench's size, interleaving variants given as ENV=value lists inside one process.
 
     python tools/layer_bench.py --bs 32 --variants PDSC_LAYER_GEMM=0 PDSC_LAYER_GEMM=1 PDSC_LAYER_GEMM=1,PDSC_LAYER_H3_EXP=2
@@ -24,7 +24,7 @@ ap.add_argument("--bs", type=int, default=32)
 ap.add_argument("--variants", nargs="+", default=["PDSC_LAYER_GEMM=0", "PDSC_LAYER_GEMM=1"])
 ap.add_argument("--rounds", type=int, default=5)
 ap.add_argument("--calls", type=int, default=20)
-ap.add_argument("--pf", action="store_true", help="hand-offs in point-fragment order (pdsc_layer_fused_frag_io, H3 only)")
+ap.add_argument("--pf", action="store_true", help="hand-offs in point-fragment order (pdsc_layer_call.io_flags, H3 only)")
 a = ap.parse_args()
 lib = _lib.load()
 n, bs, dev = a.n, a.bs, "cuda:0"
@@ -44,21 +44,17 @@ streams = {g: (ops.frag_weights_tail(tail_w, g), ops.frag_weights_head(head_w, g
 featB = torch.empty(bs * ops.pf_rows(n), 128, device=dev)
 if a.pf:
     res = ops.rows_to_pf(res, bs, n)
-p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
-part_o = C.c_void_p(scratch.data_ptr())
-part_ml = C.c_void_p(scratch.data_ptr() + bs * nsplit * npad * 128 * 4)
+part_o = scratch.data_ptr()
+base = dict(part_o=part_o, part_ml=part_o + bs * nsplit * npad * 128 * 4, nsplit=nsplit, Npad=npad, res=res.data_ptr(),
+            featB_out=featB.data_ptr(), q_split=qs.data_ptr(), kv_tiles=kv.data_ptr(), io_flags=7 if a.pf else 0, bs=bs, N=n)
 stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def call():
     gemm = int(os.environ.get("PDSC_LAYER_GEMM", "0"))
     wt, wh = streams["h3" if gemm else "f32"]
-    if a.pf:
-        _lib.check(lib.pdsc_layer_fused_frag_io(None, part_o, part_ml, nsplit, npad, p(res), None, None, p(featB), p(qs), p(kv),
-                                                p(wt), p(wh), gemm, 7, bs, n, stream), "pdsc_layer_fused_frag_io")
-        return
-    _lib.check(lib.pdsc_layer_fused_frag_fmt(None, part_o, part_ml, nsplit, npad, p(res), None, None, p(featB), None, p(qs), p(kv),
-                                             p(wt), p(wh), gemm, bs, n, stream), "pdsc_layer_fused_frag_fmt")
+    c = _lib.PdscLayerCall(wfrag_tail=wt.data_ptr(), wfrag_head=wh.data_ptr(), gemm_format=gemm, **base)
+    _lib.check(lib.pdsc_layer_run(C.byref(c), stream), "pdsc_layer_run")
 
 
 def apply(v):
