@@ -12,7 +12,7 @@
  *     pdsc_forward_validation; the weight packers pdsc_wpack_floats / _offset, pdsc_wsplit_bytes / _offset / _build; the workspace
  *     queries pdsc_workspace_bytes / _offset; pdsc_encoder_range_probe; pdsc_version / pdsc_last_error; and, for the callers either
  *     side of the path (SURVEY.md section 8 f-2 .. f-4), pdsc_match_* / pdsc_select_correspondences / pdsc_build_corr_pos,
- *     pdsc_sm_baseline*, pdsc_cal_confidence, pdsc_eval_stats, pdsc_icp_*.
+ *     pdsc_sm_baseline*, pdsc_cal_confidence, pdsc_eval_stats, pdsc_icp_*, pdsc_information_*, pdsc_voxel_*.
  *   STAGE LEVEL -- one entry point per reference stage (sections a-1 .. a-11 below), the plan / size queries that go with them,
  *     pdsc_selftest_* and the diagnostic hooks.  The forward does not go through them (it calls the same launchers directly); they
  *     exist so that every stage can be parity-checked on its own (tests/test_gpu_parity.py), for the tools, and for a maintainer
@@ -649,6 +649,44 @@ int pdsc_icp_refine(const float* src, const float* tgt, const float* init_trans,
                     double max_distance, double relative_fitness, double relative_rmse, int max_iteration, float* out_trans_f32,
                     double* out_trans_f64, double* fitness, double* inlier_rmse, int* num_corr, int* iterations, void* workspace,
                     size_t workspace_bytes, int bs, int Ns, int Nt, void* stream);
+
+/* ---- multiway edge step ------------------------------------------------------------------------
+ * pdsc_information_matrix replaces open3d registration.get_information_matrix_from_point_clouds
+ * (GetInformationMatrixFromPointClouds) as multiway/test_multi_ate.py:69-72 and :141-146 call it, per pair, fp64 throughout:
+ *   P = trans * src (skipped when trans passes Eigen's isIdentity(), as in pdsc_icp_refine); the correspondence set is
+ *   pdsc_icp_refine's evaluate step: each source point's nearest target with fp64 d2 < float(max_distance^2), equal distances:
+ *   the lowest target index; for every correspondence with TARGET point (x, y, z) info += g g^T for the three rows
+ *   g = (0, z, -y, 1, 0, 0), (-z, 0, x, 0, 1, 0), (y, -x, 0, 0, 0, 1).
+ * IDENTITY_RULE: open3d 0.9 is believed to start every OpenMP thread's private accumulator from the 6x6 identity (its result
+ * then depends on the thread count); later versions start from zero.  Not checkable without open3d; this entry returns the
+ * plain sum, so info[3][3] = info[4][4] = info[5][5] = num_corr exactly (what the driver's overlap gate reads, :147).
+ * src [bs][Ns][3], tgt [bs][Nt][3] (fp32, widened exactly), trans [bs][16] fp32; Ns_per_pair / Nt_per_pair [bs] int32 (DEVICE;
+ * NULL = every pair has Ns / Nt points; rows beyond a pair's count are padding and never read).
+ * Outputs: info [bs][36] double (row-major 6x6, symmetric bit for bit, every entry written), num_corr [bs] int32, and
+ * optionally corr [bs][Ns] int32 (NULL = not wanted): the target index of each source point, -1 = none and for padding rows.
+ * max_distance <= 0 or an empty set: the zero matrix; a non-finite pose or point: a NaN matrix and num_corr 0.
+ * One launch, no allocation, no host synchronisation (graph-capturable); a pair's result does not depend on its batch.
+ * workspace: pdsc_information_workspace_bytes(bs, Ns, Nt). */
+size_t pdsc_information_workspace_bytes(int bs, int Ns, int Nt);
+int pdsc_information_matrix(const float* src, const float* tgt, const float* trans, const int* Ns_per_pair, const int* Nt_per_pair,
+                            double max_distance, double* info, int* num_corr, int* corr, void* workspace, size_t workspace_bytes,
+                            int bs, int Ns, int Nt, void* stream);
+
+/* open3d PointCloud.voxel_down_sample (multiway/test_multi_ate.py:58-59) in two launches around a stable sort of the keys that
+ * the caller provides: grid anchored at min - voxel_size / 2, fp64 floor((p - origin) / voxel_size) per axis, one output point per
+ * occupied voxel = the fp64 mean of its points (summed in input order) rounded to fp32, output ordered by ascending voxel
+ * index (ix dy + iy) dz + iz (open3d's own order is a hash-map artefact).
+ *   pdsc_voxel_keys : points [bs][N][3], n_per_cloud [bs] int32 (DEVICE; NULL = N each) -> keys [bs][N] int64.  Padding rows,
+ *                     and every row of a cloud with a non-finite point or a grid beyond 2^20 voxels per axis, get INT64_MAX.
+ *                     voxel_size <= 0 (or not finite): PDSC_ERR_ARG.
+ *   pdsc_voxel_means: sorted_keys [bs][N] = the keys of each cloud in ascending order, perm [bs][N] int64 = the STABLE permutation
+ *                     that sorts them (sorted_keys[i] = keys[perm[i]]) -> out [bs][N][3] (one row per run of equal keys; rows
+ *                     beyond the count are zero), counts [bs] int32.  A cloud whose keys are all INT64_MAX has count 0.  Entries
+ *                     of perm outside [0, N) are skipped (nothing is read outside the cloud); a run left without a point is NaN.
+ *                     Cost: a run of equal keys is summed by one thread in input order, so the time grows with the fullest voxel. */
+int pdsc_voxel_keys(const float* points, const int* n_per_cloud, double voxel_size, long long* keys, int bs, int N, void* stream);
+int pdsc_voxel_means(const float* points, const long long* sorted_keys, const long long* perm, float* out, int* counts, int bs,
+                     int N, void* stream);
 
 /* ---- range probe for layer_gemm = PDSC_LAYER_GEMM_H3 ----------------------------------------------------------------
  * The H3 arithmetic carries every operand of the fc_message / PointCN GEMMs as fp16 hi + lo, so every activation of the

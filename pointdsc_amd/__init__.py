@@ -7,10 +7,14 @@ Only what the path needs lives here:
   model.py     ``PointDSC`` nn.Module: reference constructor, state_dict layout and forward contract
   ops.py       stage-level tensor wrappers (``rigid_transform_3d``, ``knn`` ...) over the C-ABI
   icp.py       the evaluation's optional ICP post-step (``icp_refine``, ``registration_icp``) on the device
+  multiway.py  the multiway driver's edge step (information matrix + overlap gate, voxel down-sampling, multi-scale ICP) on the device
   sharding.py  one-process-per-GPU sharding of pair batches + the single RCCL pose gather
   synthetic.py seeded synthetic correspondence sets / weights (tests + bench)
 """
 from .icp import icp_refine, registration_icp  # noqa: F401
 from .model import PointDSC  # noqa: F401
+from .multiway import (align, information_matrix, local_refinement, loop_closure_edge, multi_scale_icp,  # noqa: F401
+                       voxel_down_sample)
 
-__all__ = ["PointDSC", "icp_refine", "registration_icp"]
+__all__ = ["PointDSC", "icp_refine", "registration_icp", "information_matrix", "voxel_down_sample", "loop_closure_edge",
+           "multi_scale_icp", "local_refinement", "align"]

@@ -127,6 +127,10 @@ SIGNATURES = {
     "pdsc_icp_workspace_bytes": (_sz, [_i, _i, _i]),
     "pdsc_icp_refine": (_i, [_vp, _vp, _vp, _vp, _vp, C.c_double, C.c_double, C.c_double, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                              _sz, _i, _i, _i, _vp]),
+    "pdsc_information_workspace_bytes": (_sz, [_i, _i, _i]),
+    "pdsc_information_matrix": (_i, [_vp, _vp, _vp, _vp, _vp, C.c_double, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _vp]),
+    "pdsc_voxel_keys": (_i, [_vp, _vp, C.c_double, _vp, _i, _i, _vp]),
+    "pdsc_voxel_means": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
     "pdsc_encoder_range_probe": (_i, [_cfgp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
     "pdsc_forward_validation": (_i, [_cfgp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _ll, _vp, _sz, _vp]),
     "pdsc_feature_compat": (_i, [_vp, _vp, _vp, _ll, _i, _i, _vp]),

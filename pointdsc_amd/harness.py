@@ -8,7 +8,7 @@ Replicates, without open3d / easydict (absent here):
   * ``demo_registration.py:37-44,101-117``  cloud -> voxel down-sampling -> descriptors -> nearest-neighbour matching
     -> ``corr_pos`` -> ``model(data)``.
 The arithmetic on the path runs in libpointdsc_hip.so (correspondence construction f-2, forward a-*, stats row f-4, the
-optional ICP post-step f-5);
+optional ICP post-step f-5, the multiway driver's edge step f-6: ``multiway_edges``);
 this module is host plumbing: PLY reading (binary little-endian float xyz), open3d-style voxel
 down-sampling in numpy, the pair loop, timers (``utils/timer.py`` semantics: wall clock, here with a device
 synchronisation so that model time is the GPU's).
@@ -31,6 +31,7 @@ import torch
 from . import ops
 from .correspondences import build_correspondences
 from .icp import icp_refine
+from .multiway import local_refinement, loop_closure_edge
 
 STATS_NAMES = ("success", "RE_deg", "TE_cm", "input_inliers", "input_inlier_ratio", "output_true_positives",
                "precision", "recall", "f1", "model_time_s", "data_time_s", "scene_ind")
@@ -218,3 +219,61 @@ def demo_pairs(cloud: np.ndarray, num_pairs: int, dim: int = 33, cell: float = 0
         yield {"src_pts": cloud, "tgt_pts": tgt, "gt_trans": T,
                "src_desc": standin_descriptors(cloud, dim, cell, seed + i, corrupt, rs),
                "tgt_desc": standin_descriptors(tgt_in_src, dim, cell, seed + i, corrupt * 0.5, rs)}
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# the multiway driver's pair loop (multiway/test_multi_ate.py:98-157)
+# ---------------------------------------------------------------------------------------------------------------
+def demo_views(cloud: np.ndarray, num_views: int, dim: int = 33, cell: float = 0.05, corrupt: float = 0.4, seed: int = 0,
+               odometry_deg: float = 2.0, odometry_cm: float = 5.0) -> List[Dict[str, np.ndarray]]:
+    """Fragments for `multiway_edges` from ONE down-sampled cloud, built like `demo_pairs`: view i = `second_view(cloud, seed + i)`
+    in its own frame, with stand-in descriptors that agree between the views for points of the same cell of the cloud's frame.
+    `pose` [4,4]: p_view = pose p_cloud.  `odometry` [4,4] (all but the last view): the motion onto the next view disturbed by
+    `odometry_deg` / `odometry_cm` -- the stand-in for the fragment odometry the driver starts its local refinement from
+    (multiway/test_multi_ate.py:119-121)."""
+    views = []
+    for i in range(num_views):
+        rs = np.random.RandomState(20_000 + seed + i)
+        pts, T, in_cloud = second_view(cloud, seed + i)
+        views.append({"pts": pts, "pose": T.astype(np.float64), "desc": standin_descriptors(in_cloud, dim, cell, seed, corrupt, rs)})
+    for i in range(num_views - 1):
+        rs = np.random.RandomState(30_000 + seed + i)
+        axis = rs.standard_normal(3)
+        axis /= np.linalg.norm(axis)
+        a = np.radians(odometry_deg)
+        K = np.array([[0, -axis[2], axis[1]], [axis[2], 0, -axis[0]], [-axis[1], axis[0], 0]])
+        D = np.eye(4)
+        D[:3, :3] = np.eye(3) + np.sin(a) * K + (1 - np.cos(a)) * K @ K
+        d = rs.standard_normal(3)
+        D[:3, 3] = d / np.linalg.norm(d) * odometry_cm / 100.0
+        views[i]["odometry"] = (D @ views[i + 1]["pose"] @ np.linalg.inv(views[i]["pose"])).astype(np.float32)
+    return views
+
+
+def multiway_edges(model, views: List[Dict[str, np.ndarray]], use_mutual: bool = False, device: str = "cuda:0"):
+    """The pairwise-registration loop of the multiway driver (multiway/test_multi_ate.py:98-157) over `views` (dicts with pts [n,3],
+    desc [n,D] and, for every view but the last, odometry [4,4]; `demo_views` builds them): every pair s < t in the driver's order.
+      t == s + 1 (odometry case, :117-135): `local_refinement` of the full clouds from views[s]['odometry'] -> a certain edge;
+      otherwise (:136-154): match -> `model(data)` -> `loop_closure_edge`; a pair the gate drops is skipped, the others are
+      uncertain edges.
+    Everything up to the gate stays on the device; the gates of all pairs are read back once, at the end.
+    Returns the edges as the driver would append them: tuples (s, t, T [4,4] float64 numpy, info [6,6] float64 numpy, uncertain)."""
+    dev = torch.device(device)
+    g = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)  # noqa: E731
+    pts = [g(v["pts"]) for v in views]
+    desc = [g(v["desc"]) for v in views]
+    found = []
+    with torch.no_grad():
+        for s in range(len(views)):
+            for t in range(s + 1, len(views)):
+                if t == s + 1:
+                    T, info = local_refinement(pts[s][None], pts[t][None], g(views[s]["odometry"])[None])
+                    found.append((s, t, T[0], info[0], None))
+                else:
+                    c = build_correspondences(desc[s], desc[t], pts[s], pts[t], use_mutual=use_mutual)
+                    res = model({"corr_pos": c["corr_pos"], "src_keypts": c["src_keypts"], "tgt_keypts": c["tgt_keypts"], "testing": True})
+                    edge = loop_closure_edge(c["src_keypts"], c["tgt_keypts"], res["final_trans"])
+                    found.append((s, t, res["final_trans"][0], edge["information"][0], edge["keep"][0]))
+    keep = torch.stack([f[4] if f[4] is not None else torch.ones((), dtype=torch.bool, device=dev) for f in found]).cpu().numpy()
+    return [(s, t, T.double().cpu().numpy(), info.cpu().numpy(), gate is not None)
+            for (s, t, T, info, gate), k in zip(found, keep) if k]

@@ -11,7 +11,7 @@ batch: padded to the longest pair, per-pair counts on the device).  Source and t
 from __future__ import annotations
 
 import math
-from typing import Dict, List, Sequence, Union
+from typing import Dict, List, Optional, Sequence, Union
 
 import torch
 
@@ -56,14 +56,64 @@ def _as_batch(x: Points, name: str):
     return out, counts, torch.tensor(counts, dtype=torch.int32).to(dev, non_blocking=True)
 
 
+def _counts(counts, bs: int, dev, name: str):
+    """Per-pair point counts that are already on the device ([bs] int32): what keeps a chain of calls free of host reads."""
+    if counts is None:
+        return None
+    if not torch.is_tensor(counts):
+        raise TypeError(f"{name} must be a tensor")
+    counts = _chk(counts, name, torch.int32)
+    if tuple(counts.shape) != (bs,) or counts.device != dev:
+        raise ValueError(f"{name} must be [{bs}] int32 on {dev}, got {tuple(counts.shape)} on {counts.device}")
+    return counts
+
+
+def _pair_batches(source: Points, target: Points, source_counts=None, target_counts=None):
+    """-> (src [bs,Ns,3], tgt [bs,Nt,3], ns_dev, nt_dev): both per-pair count tensors, or None for both when every pair is full."""
+    src, _, ns_dev = _as_batch(source, "source")
+    tgt, _, nt_dev = _as_batch(target, "target")
+    bs = src.shape[0]
+    if tgt.shape[0] != bs:
+        raise ValueError(f"source has {bs} pairs, target {tgt.shape[0]}")
+    if src.device != tgt.device:
+        raise ValueError("source and target must live on the same device")
+    dev = src.device
+    if source_counts is not None:
+        if ns_dev is not None:
+            raise ValueError("source_counts goes with a padded [bs,N,3] tensor, not with a list of pairs")
+        ns_dev = _counts(source_counts, bs, dev, "source_counts")
+    if target_counts is not None:
+        if nt_dev is not None:
+            raise ValueError("target_counts goes with a padded [bs,N,3] tensor, not with a list of pairs")
+        nt_dev = _counts(target_counts, bs, dev, "target_counts")
+    if ns_dev is None and nt_dev is not None:
+        ns_dev = torch.full((bs,), src.shape[1], dtype=torch.int32, device=dev)
+    if nt_dev is None and ns_dev is not None:
+        nt_dev = torch.full((bs,), tgt.shape[1], dtype=torch.int32, device=dev)
+    return src, tgt, ns_dev, nt_dev
+
+
+def _as_poses(T: torch.Tensor, bs: int, name: str) -> torch.Tensor:
+    if not torch.is_tensor(T):
+        raise TypeError(f"{name} must be a tensor")
+    T = _chk(T, name)
+    if T.shape == (4, 4):
+        T = T.expand(bs, 4, 4)
+    if tuple(T.shape) != (bs, 4, 4):
+        raise ValueError(f"{name} must be [4,4] or [{bs},4,4], got {tuple(T.shape)}")
+    return T.contiguous()
+
+
 @_on_device
 def registration_icp(source: Points, target: Points, init: torch.Tensor,
                      max_correspondence_distance: float = MAX_CORRESPONDENCE_DISTANCE,
                      relative_fitness: float = RELATIVE_FITNESS, relative_rmse: float = RELATIVE_RMSE,
-                     max_iteration: int = MAX_ITERATION) -> Dict[str, torch.Tensor]:
+                     max_iteration: int = MAX_ITERATION, source_counts: Optional[torch.Tensor] = None,
+                     target_counts: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
     """open3d 0.9 ``registration.registration_icp(source, target, max_correspondence_distance, init,
     TransformationEstimationPointToPoint(), ICPConvergenceCriteria(relative_fitness, relative_rmse, max_iteration))``
-    for every pair of the batch.  ``init`` [bs,4,4] or [4,4] (shared by all pairs), fp32.
+    for every pair of the batch.  ``init`` [bs,4,4] or [4,4] (shared by all pairs), fp32.  ``source_counts`` / ``target_counts``
+    ([bs] int32 on the device) give the valid rows of padded ``[bs,N,3]`` inputs without a host read.
 
     Returns a dict of device tensors: ``transformation`` [bs,4,4] fp32, ``transformation_f64`` [bs,4,4] fp64,
     ``fitness`` [bs] fp64, ``inlier_rmse`` [bs] fp64, ``num_correspondences`` [bs] int32 (the final correspondence set),
@@ -76,26 +126,9 @@ def registration_icp(source: Points, target: Points, init: torch.Tensor,
         raise ValueError("relative_fitness / relative_rmse must not be NaN")
     if int(max_iteration) < 0:
         raise ValueError(f"max_iteration must be >= 0, got {max_iteration}")
-    src, ns_list, ns_dev = _as_batch(source, "source")
-    tgt, nt_list, nt_dev = _as_batch(target, "target")
-    bs = src.shape[0]
-    if tgt.shape[0] != bs:
-        raise ValueError(f"source has {bs} pairs, target {tgt.shape[0]}")
-    if src.device != tgt.device:
-        raise ValueError("source and target must live on the same device")
-    if not torch.is_tensor(init):
-        raise TypeError("init must be a tensor")
-    init = _chk(init, "init")
-    if init.shape == (4, 4):
-        init = init.expand(bs, 4, 4)
-    if tuple(init.shape) != (bs, 4, 4):
-        raise ValueError(f"init must be [4,4] or [{bs},4,4], got {tuple(init.shape)}")
-    init = init.contiguous()
-    dev = src.device
-    if ns_dev is None and nt_dev is not None:
-        ns_dev = torch.full((bs,), src.shape[1], dtype=torch.int32, device=dev)
-    if nt_dev is None and ns_dev is not None:
-        nt_dev = torch.full((bs,), tgt.shape[1], dtype=torch.int32, device=dev)
+    src, tgt, ns_dev, nt_dev = _pair_batches(source, target, source_counts, target_counts)
+    bs, dev = src.shape[0], src.device
+    init = _as_poses(init, bs, "init")
     Ns, Nt = int(src.shape[1]), int(tgt.shape[1])
     ws_bytes = int(lib.pdsc_icp_workspace_bytes(bs, Ns, Nt))
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)

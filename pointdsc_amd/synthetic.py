@@ -60,6 +60,20 @@ def make_batch(batch: int, num_corr: int, seed: int = 0, **kw):
     return {k: torch.cat([p[k] for p in pairs], dim=0).contiguous() for k in pairs[0]}
 
 
+def box_room(n: int = 60000, seed: int = 11, size=(1.2, 1.0, 0.8), noise: float = 0.002) -> np.ndarray:
+    """A dense synthetic scan: n points spread by area over the six faces of a box room of `size` metres plus `noise` m of
+    Gaussian sensor noise, float32 [n,3].  Dense enough that voxel sizes of 0.025 / 0.0125 m -- the finer scales of the multiway
+    driver's multi-scale ICP -- still merge points (tests/test_multiway.py, tools/icp_bench.py)."""
+    rs = np.random.RandomState(seed)
+    size = np.asarray(size, np.float64)
+    areas = np.array([size[1] * size[2], size[1] * size[2], size[0] * size[2], size[0] * size[2], size[0] * size[1], size[0] * size[1]])
+    face = rs.choice(6, n, p=areas / areas.sum())
+    p = rs.uniform(0, 1, (n, 3)) * size
+    axis = face // 2
+    p[np.arange(n), axis] = np.where(face % 2 == 0, 0.0, size[axis])
+    return (p + rs.standard_normal((n, 3)) * noise).astype(np.float32)
+
+
 DEFAULT_LOGIT_SHIFT = 0.05
 
 

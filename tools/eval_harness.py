@@ -2,10 +2,14 @@
 """The reference's evaluation loop / demo around pointdsc_amd.PointDSC (pointdsc_amd/harness.py).
 
     python tools/eval_harness.py [--pcd1 a.ply --pcd2 b.ply] [--num-pairs 8] [--snapshot model_best.pkl] [--kitti] [--use-icp]
+    python tools/eval_harness.py --multiway [--num-views 5]
 
 Without --pcd1 the down-sampled demo cloud of tests/golden/demo_clouds_vox005.npz (reference demo_data/cloud_bin_0.ply at
 0.05 m) is used.  Every pair = the cloud against a seeded second view of it (partial overlap, noise, random rigid motion),
 stand-in descriptors with a known outlier share, GPU correspondence construction, forward, device-side stats row.
+--multiway runs the multiway driver's pairwise loop instead (multiway/test_multi_ate.py:98-157, harness.multiway_edges): every pair
+of --num-views seeded views of the cloud; adjacent views through multi-scale ICP (certain edges), the others through the forward,
+the device-side information matrix and the overlap gate (uncertain edges); prints the edges a pose graph would receive.
 Registration Recall on 3DMatch-FCGF itself needs the released weights and the dataset (both absent here): pass
 --snapshot / real descriptors when they exist; the loop is the same.
 """
@@ -22,6 +26,23 @@ sys.path.insert(0, str(ROOT))
 from pointdsc_amd import PointDSC, harness, workloads  # noqa: E402
 
 
+def multiway(model, cloud, a):
+    views = harness.demo_views(cloud, a.num_views, corrupt=min(a.outlier_share, 0.4))
+    edges = harness.multiway_edges(model, views, use_mutual=a.mutual)
+    if a.json:
+        print(json.dumps({"edges": [{"source": s, "target": t, "transformation": T.tolist(), "information": info.tolist(),
+                                     "uncertain": bool(u)} for s, t, T, info, u in edges]}))
+        return
+    pairs = a.num_views * (a.num_views - 1) // 2
+    print(f"{len(cloud)} points, {a.num_views} views, {pairs} pairs -> {len(edges)} edges ({pairs - len(edges)} dropped by the overlap gate)")
+    for s, t, T, info, u in edges:
+        gt = views[t]["pose"] @ np.linalg.inv(views[s]["pose"])
+        d = T @ np.linalg.inv(gt)
+        re = np.degrees(np.arccos(np.clip((np.trace(d[:3, :3]) - 1) / 2, -1, 1)))
+        print(f"{s:3d} -> {t:3d}  {'uncertain' if u else 'certain  '}  correspondences {info[5, 5]:7.0f}  RE {re:7.3f} deg  "
+              f"TE {np.linalg.norm(T[:3, 3] - gt[:3, 3]) * 100:7.3f} cm")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--pcd1", default=None, help="PLY file (binary LE / ascii, float xyz); default: the demo fixture")
@@ -33,6 +54,8 @@ def main():
     ap.add_argument("--batch-size", type=int, default=1, help="pairs per (ragged) model call; the reference evaluates one pair per call")
     ap.add_argument("--use-icp", action="store_true", help="refine every pose by point-to-point ICP on the device (test_3DMatch.py --use_icp)")
     ap.add_argument("--icp-distance", type=float, default=0.10, help="max_correspondence_distance of the ICP post-step")
+    ap.add_argument("--multiway", action="store_true", help="the multiway driver's edge loop over --num-views views (test_multi_ate.py:98-157)")
+    ap.add_argument("--num-views", type=int, default=5)
     ap.add_argument("--json", action="store_true")
     a = ap.parse_args()
     if a.pcd1:
@@ -46,6 +69,8 @@ def main():
     else:
         model.load_state_dict(workloads.state_dict("n5000_b32", model.state_dict()))
     model = model.eval().cuda()
+    if a.multiway:
+        return multiway(model, cloud, a)
     stats = harness.eval_scene(model, harness.demo_pairs(cloud, a.num_pairs, corrupt=a.outlier_share), scene_ind=0,
                                inlier_threshold=kw["inlier_threshold"], use_mutual=a.mutual, batch_size=a.batch_size,
                                use_icp=a.use_icp, icp_distance=a.icp_distance)

@@ -10,6 +10,13 @@ likewise).
 Every call is timed with device events after warm-up; reported: us per call, us per iteration (call time / the largest
 iteration count of the batch: the launch lasts as long as its slowest pair), the mean iteration count, and per iteration the
 bytes and fp64 operations the shapes imply (a model, not a counter reading).
+
+    python tools/icp_bench.py --multiway [--reps 20] [--warmup 5] [--json]
+
+times the multiway driver's edge step instead (pointdsc_amd.multiway): the information matrix at 0.07 m
+for 1 and 32 pairs of N = 5000 (fixture endpoints at the reference's pose) and 1 pair of N = 20000 (synthetic.make_pair, 30 %
+inliers, at the ground truth), voxel down-sampling of the dense box-room cloud at the three scales, and local_refinement
+(three scales of down-sampling + ICP, then the information matrix) of that cloud against a second view of it.
 """
 import argparse
 import json
@@ -22,7 +29,7 @@ import torch
 
 ROOT = Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(ROOT))
-from pointdsc_amd import registration_icp, synthetic  # noqa: E402
+from pointdsc_amd import harness, multiway, registration_icp, synthetic  # noqa: E402
 
 GOLDEN = ROOT / "tests" / "golden"
 
@@ -104,12 +111,64 @@ def bench(name, src, tgt, init, reps, warmup):
             "bytes_per_iteration": b_it * bs, "fp64_ops_per_iteration": f_it * bs}
 
 
+def _time(fn, reps, warmup):
+    """us per call of fn() by device events after warm-up."""
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(reps):
+        out = fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / reps * 1e3, out
+
+
+def multiway_rows(reps, warmup):
+    dev = torch.device("cuda:0")
+    g = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float32)).to(dev)  # noqa: E731
+    rows = []
+    d = np.load(GOLDEN / "n5000_s5.npz")
+    big = synthetic.make_pair(20000, inlier_ratio=0.3, noise=0.01, seed=7)
+    for name, S, Q, T in (("information 1 x N=5000", d["src_keypts"], d["tgt_keypts"], d["ref_final_trans"]),
+                          ("information 32 x N=5000", np.repeat(d["src_keypts"], 32, 0), np.repeat(d["tgt_keypts"], 32, 0),
+                           np.repeat(d["ref_final_trans"], 32, 0)),
+                          ("information 1 x N=20000", big["src_keypts"].numpy(), big["tgt_keypts"].numpy(), big["gt_trans"].numpy())):
+        Sd, Qd, Td = g(S), g(Q), g(T)
+        us, out = _time(lambda: multiway.information_matrix(Sd, Qd, multiway.EDGE_DISTANCE, Td), reps, warmup)
+        rows.append({"case": name, "us_per_call": us, "mean_correspondences": float(out["num_correspondences"].float().mean())})
+    room = synthetic.box_room()
+    view, G, _ = harness.second_view(room, 6)
+    Rd, Vd = g(room)[None], g(view)[None]
+    for v in multiway.VOXEL_SIZES:
+        us, out = _time(lambda: multiway.voxel_down_sample(Rd, v), reps, warmup)
+        rows.append({"case": f"voxel_down_sample {len(room)} points at {v} m", "us_per_call": us, "points_out": int(out[1][0])})
+    init = g(perturbed(G, 2.0, 5.0, np.random.RandomState(106)))[None]
+    us, out = _time(lambda: multiway.multi_scale_icp(Rd, Vd, trans=init), max(2, reps // 4), min(warmup, 2))
+    rows.append({"case": f"local_refinement {len(room)} x {len(view)} points", "us_per_call": us,
+                 "iterations": [int(s["iterations"][0]) for s in out["scales"]],
+                 "points": [[int(s["source_counts"][0]), int(s["target_counts"][0])] for s in out["scales"]],
+                 "mean_correspondences": float(out["num_correspondences"][0])})
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--json", action="store_true")
+    ap.add_argument("--multiway", action="store_true", help="time the multiway edge step (information matrix, voxel down-sampling, local_refinement)")
     a = ap.parse_args()
+    if a.multiway:
+        rows = multiway_rows(a.reps, a.warmup)
+        if a.json:
+            print(json.dumps(rows))
+            return
+        for r in rows:
+            print(f"{r['case']:>48s}: {r['us_per_call']:10.1f} us/call  " +
+                  "  ".join(f"{k} {v}" for k, v in r.items() if k not in ("case", "us_per_call")))
+        return
     cases = [("1 x N=1000", *case("n1000_s1.npz", "ref_final_trans", 1, 1)),
              ("1 x N=5000", *case("n5000_s5.npz", "ref_final_trans", 1, 2)),
              ("32 x N=5000", *case("n5000_s5.npz", "ref_final_trans", 32, 3)),

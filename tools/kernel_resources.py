@@ -4,7 +4,9 @@
     python tools/kernel_resources.py [path/to/lib.so] [substring ...]
 
 (.vgpr_count / .agpr_count / .sgpr_count / .private_segment_fixed_size = scratch bytes per lane / .group_segment_fixed_size = static
-LDS.)  What DESIGN.md's register and spill figures are read from."""
+LDS.)  What DESIGN.md's register and spill figures are read from, e.g. those of section 8 f-5 / f-6:
+
+    python tools/kernel_resources.py icp_kernel information_kernel voxel_keys_kernel voxel_means_kernel"""
 import re
 import subprocess
 import sys
