@@ -15,6 +15,7 @@
 #include "split_layout.h"
 #include "merge_partials.h"
 #include "layer_args.h"
+#include "layer_block.h"
 
 namespace pdsc {
 
@@ -75,15 +76,7 @@ __device__ __forceinline__ void store_tile(const f32x16& acc, const float* __res
     }
 }
 
-// coalesced copies between a 32x128 LDS tile and row-major global memory (ld floats per row)
-__device__ __forceinline__ void tile_to_global(const float* Xs, float* __restrict__ dst, long long ld, int m0, int M, int t) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int f = t + 256 * i, row = f >> 5, c4 = f & 31;
-        if (m0 + row < M)
-            *reinterpret_cast<f32x4*>(dst + (size_t)(m0 + row) * ld + 4 * c4) = *reinterpret_cast<const f32x4*>(Xs + row * LF_LD + 4 * c4);
-    }
-}
+// coalesced copy of row-major global memory into a 32x128 LDS tile (the other direction: layer_block.h)
 __device__ __forceinline__ void global_to_tile(const float* __restrict__ src, float* Xs, int m0, int M, int t) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -93,105 +86,40 @@ __device__ __forceinline__ void global_to_tile(const float* __restrict__ src, fl
     }
 }
 
-// 32x128 fp32 LDS tile (one of q / k / v for 32 points = one key tile) -> fp16 hi/lo streams (split_layout.h).
-// WHICH: 0 = q rows, 1 = K image, 2 = V^T image.  `valid` = number of real points in the tile (the rest is zero).
-template <int WHICH>
-__device__ __forceinline__ void tile_to_split(const float* Xs, sp16* __restrict__ qrows, unsigned char* __restrict__ img,
-                                              int valid, int t) {
-    if (WHICH == 0) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int f = t + 256 * i, row = f >> 5, c4 = (f & 31) * 4;
-            if (row < valid) {
-                const f32x4 v = *reinterpret_cast<const f32x4*>(Xs + row * LF_LD + c4);
-                sp16x4 hi, lo;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) { sp16 x, y; split_sp16(v[e], x, y); hi[e] = x; lo[e] = y; }
-                sp16* dst = qrows + (size_t)row * SPL_Q_LD + c4;
-                *reinterpret_cast<sp16x4*>(dst) = hi;
-                *reinterpret_cast<sp16x4*>(dst + PDSC_CHANNELS) = lo;
-            }
-        }
-    } else if (WHICH == 1) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int f = t + 256 * i, key = f >> 4, chunk = f & 15;
-            const f32x4 v0 = *reinterpret_cast<const f32x4*>(Xs + key * LF_LD + 8 * chunk);
-            const f32x4 v1 = *reinterpret_cast<const f32x4*>(Xs + key * LF_LD + 8 * chunk + 4);
-            sp16x8 hi, lo;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const float v = key < valid ? (e < 4 ? v0[e & 3] : v1[e & 3]) : 0.f;
-                sp16 x, y; split_sp16(v, x, y); hi[e] = x; lo[e] = y;
-            }
-            *reinterpret_cast<sp16x8*>(img + SPL_KH + spl_k_offset(key, chunk)) = hi;
-            *reinterpret_cast<sp16x8*>(img + SPL_KL + spl_k_offset(key, chunk)) = lo;
-        }
-    } else {
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int f = t + 256 * i, ch = f & 127, jh = f >> 7;
-            sp16x8 hi, lo;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const int key = spl_v_key(jh, e);
-                const float v = key < valid ? Xs[key * LF_LD + ch] : 0.f;
-                sp16 x, y; split_sp16(v, x, y); hi[e] = x; lo[e] = y;
-            }
-            *reinterpret_cast<sp16x8*>(img + SPL_VH + spl_v_offset(ch, jh)) = hi;
-            *reinterpret_cast<sp16x8*>(img + SPL_VL + spl_v_offset(ch, jh)) = lo;
-        }
-    }
-}
-
 // tail input: merged msg rows, or the merge of the attention's key-split partials (merge_partials.h)
 __device__ __forceinline__ void msg_to_tile(const LayerArgs& a, int b, float* Xs, int m0, int M, int t) {
     if (a.msg) {
         global_to_tile(a.msg, Xs, m0, M, t);
         return;
     }
-    // split count as a compile-time constant (wave-uniform switch): registers for exactly that many partials
-    auto run = [&](auto ns_tag) {
-        constexpr int NS = decltype(ns_tag)::value;
-        MergeLoads<NS> L[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int f = t + 256 * i, row = f >> 5, c4 = (f & 31) * 4;
-            const int m = min(m0 + row, M - 1);
-            const size_t slot0 = (size_t)b * NS * a.Npad + (size_t)(m - b * a.N);
-            merge_partials_load<NS>(L[i], a.part_o, a.part_ml, slot0, (size_t)a.Npad, c4);
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int f = t + 256 * i, row = f >> 5, c4 = (f & 31) * 4;
-            *reinterpret_cast<f32x4*>(Xs + row * LF_LD + c4) = merge_partials_finish<NS>(L[i]);
-        }
-    };
-    // 5..8 splits (small problems: the attention plan splits the keys further to fill the chip): one chunk at a time --
+    // 1..4 splits: the loads of all four pieces of a thread are issued before any is used (one round trip of latency).
+    // 5..8 splits (small problems: the attention plan splits the keys further to fill the chip): one piece at a time --
     // registers for a single set of NS partials; costs four dependent round trips instead of one, still cheaper than the
     // attention_combine launch + the msg round trip it replaces
-    auto run_seq = [&](auto ns_tag) {
+    with_split_count<MERGE_MAX_SPLIT_BLOCK>(a.nsplit, [&](auto ns_tag) {
         constexpr int NS = decltype(ns_tag)::value;
+        constexpr int NB = NS <= 4 ? 4 : 1;                          // pieces per batch of loads
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int f = t + 256 * i, row = f >> 5, c4 = (f & 31) * 4;
-            const int m = min(m0 + row, M - 1);
-            const size_t slot0 = (size_t)b * NS * a.Npad + (size_t)(m - b * a.N);
-            MergeLoads<NS> L;
-            merge_partials_load<NS>(L, a.part_o, a.part_ml, slot0, (size_t)a.Npad, c4);
-            *reinterpret_cast<f32x4*>(Xs + row * LF_LD + c4) = merge_partials_finish<NS>(L);
+        for (int i0 = 0; i0 < 4; i0 += NB) {
+            MergeWeights<NS> mw[NB];
+            f32x4 pv[NB][NS];
+#pragma unroll
+            for (int i = 0; i < NB; ++i) {
+                const int f = t + 256 * (i0 + i), row = f >> 5, c4 = (f & 31) * 4;
+                const int m = min(m0 + row, M - 1);
+                const size_t slot0 = (size_t)b * NS * a.Npad + (size_t)(m - b * a.N);
+                mw[i] = merge_row_weights<NS>(a.part_ml, slot0, (size_t)a.Npad);
+#pragma unroll
+                for (int sp = 0; sp < NS; ++sp)
+                    pv[i][sp] = *reinterpret_cast<const f32x4*>(a.part_o + (slot0 + (size_t)sp * a.Npad) * PDSC_CHANNELS + c4);
+            }
+#pragma unroll
+            for (int i = 0; i < NB; ++i) {
+                const int f = t + 256 * (i0 + i), row = f >> 5, c4 = (f & 31) * 4;
+                *reinterpret_cast<f32x4*>(Xs + row * LF_LD + c4) = merge_apply<NS>(pv[i], mw[i]);
+            }
         }
-    };
-    switch (a.nsplit) {
-        case 1: run(std::integral_constant<int, 1>{}); break;
-        case 2: run(std::integral_constant<int, 2>{}); break;
-        case 3: run(std::integral_constant<int, 3>{}); break;
-        case 4: run(std::integral_constant<int, 4>{}); break;
-        case 5: run_seq(std::integral_constant<int, 5>{}); break;
-        case 6: run_seq(std::integral_constant<int, 6>{}); break;
-        case 7: run_seq(std::integral_constant<int, 7>{}); break;
-        default: run_seq(std::integral_constant<int, 8>{}); break;
-    }
+    });
 }
 
 constexpr int LF_XLD16 = PDSC_CHANNELS + 8;          // fp16 elements per row of a hi / lo activation tile (272 B)
@@ -250,7 +178,7 @@ __global__ __launch_bounds__(256, 3) void layer_fused_kernel(LayerArgs a) {
         LF_STAMP(5)
         __syncthreads();
         LF_STAMP(6)
-        if (a.feat_out) tile_to_global(Xb, a.feat_out, PDSC_CHANNELS, m0, M, t);
+        if (a.feat_out) tile_to_global<LF_LD>(Xb, a.feat_out, PDSC_CHANNELS, m0, M, t);
     } else {
         if (HAS_HEAD) load_w<128>(a.wp, 32 * wave, l31, h, wpre);
         global_to_tile(a.feat_in, Xb, m0, M, t);
@@ -267,7 +195,7 @@ __global__ __launch_bounds__(256, 3) void layer_fused_kernel(LayerArgs a) {
             store_tile<true, false>(acc, a.bp, 32 * wave, Xa, 32 * wave, l31, h, nullptr);
         }
         __syncthreads();
-        tile_to_global(Xa, a.featB_out, PDSC_CHANNELS, m0, M, t);
+        tile_to_global<LF_LD>(Xa, a.featB_out, PDSC_CHANNELS, m0, M, t);
         load_x<128>(Xa, l31, h, x);
         // ---- q|k|v: 128 -> 384 in three 128-column chunks staged through Xb ----
 #pragma unroll
@@ -277,13 +205,13 @@ __global__ __launch_bounds__(256, 3) void layer_fused_kernel(LayerArgs a) {
             if (c < 2) load_w<128>(a.wq, n0 + 128, l31, h, w);        // prefetch next chunk's tile
             store_tile<false, false>(acc, a.bq, n0, Xb, 32 * wave, l31, h, nullptr);
             __syncthreads();
-            if (a.qkv_out) tile_to_global(Xb, a.qkv_out + 128 * c, 3 * PDSC_CHANNELS, m0, M, t);
+            if (a.qkv_out) tile_to_global<LF_LD>(Xb, a.qkv_out + 128 * c, 3 * PDSC_CHANNELS, m0, M, t);
             if (a.qs) {
                 unsigned char* img = a.kv + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * SPL_TILE_STRIDE;
                 const int valid = min(LF_ROWS, M - m0);
-                if (c == 0) tile_to_split<0>(Xb, a.qs + (size_t)m0 * SPL_Q_LD, img, valid, t);
-                else if (c == 1) tile_to_split<1>(Xb, nullptr, img, valid, t);
-                else tile_to_split<2>(Xb, nullptr, img, valid, t);
+                if (c == 0) tile_to_split<0, LF_LD>(Xb, a.qs + (size_t)m0 * SPL_Q_LD, img, valid, t);
+                else if (c == 1) tile_to_split<1, LF_LD>(Xb, nullptr, img, valid, t);
+                else tile_to_split<2, LF_LD>(Xb, nullptr, img, valid, t);
             }
             if (c < 2) __syncthreads();
         }
@@ -328,7 +256,7 @@ __global__ __launch_bounds__(256, 3) void layer_fused_kernel(LayerArgs a) {
         }
         LF_STAMP(8)
         __syncthreads();
-        tile_to_global(Xa, a.featB_out, PDSC_CHANNELS, m0, M, t);
+        tile_to_global<LF_LD>(Xa, a.featB_out, PDSC_CHANNELS, m0, M, t);
         LF_STAMP(9)
         // ---- q|k|v: 128 -> 384, three 128-column chunks, hi*hi + hi*lo + lo*hi on the fp16 matrix cores, staged via Xa ----
         unsigned char* img = a.kv ? a.kv + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * SPL_TILE_STRIDE : nullptr;
@@ -360,11 +288,11 @@ __global__ __launch_bounds__(256, 3) void layer_fused_kernel(LayerArgs a) {
             store_tile<false, false>(acc, a.bq, n0, Xa, 32 * wave, l31, h, nullptr);
             __syncthreads();
             if (c == 0) { LF_STAMP(11) }
-            if (a.qkv_out) tile_to_global(Xa, a.qkv_out + 128 * c, 3 * PDSC_CHANNELS, m0, M, t);
+            if (a.qkv_out) tile_to_global<LF_LD>(Xa, a.qkv_out + 128 * c, 3 * PDSC_CHANNELS, m0, M, t);
             if (a.qs) {
-                if (c == 0) tile_to_split<0>(Xa, a.qs + (size_t)m0 * SPL_Q_LD, img, valid, t);
-                else if (c == 1) tile_to_split<1>(Xa, nullptr, img, valid, t);
-                else tile_to_split<2>(Xa, nullptr, img, valid, t);
+                if (c == 0) tile_to_split<0, LF_LD>(Xa, a.qs + (size_t)m0 * SPL_Q_LD, img, valid, t);
+                else if (c == 1) tile_to_split<1, LF_LD>(Xa, nullptr, img, valid, t);
+                else tile_to_split<2, LF_LD>(Xa, nullptr, img, valid, t);
             }
             if (c == 0) { LF_STAMP(12) }
         }

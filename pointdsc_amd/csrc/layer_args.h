@@ -1,5 +1,7 @@
-// Arguments shared by the two implementations of the fused point-wise layer (layer.hip: one 4-wave workgroup per
-// 32-point tile, activations in LDS; layer_wave.hip: one wavefront per tile, activations in registers).
+// Arguments shared by the kernels of the fused point-wise layer: layer.hip (one 4-wave workgroup per 32-point tile, activations
+// in LDS, fp32), layer_wave.hip (one wavefront per tile, activations in registers: the generic form), layer_h3.hip (the pipelined
+// H3 kernel of the forward), layer_coop.hip (four wavefronts per tile, launches of few tiles) and layer_split.hip (the all-split
+// kernel of experiments builds).
 #pragma once
 #include "pdsc_common.h"
 #include "merge_partials.h"
@@ -77,6 +79,10 @@ int launch_layer_h3(const LayerArgs& a, bool tail, bool head, hipStream_t st);  
 int launch_layer_h3_coop(const LayerArgs& a, bool tail, bool head, hipStream_t st);   // layer_coop.hip (same contract, few tiles)
 int launch_layer_x3(const LayerArgs& a, bool tail, bool head, hipStream_t st);        // layer_split.hip (experiments builds, else an error)
 bool launch_layer_h3_fits(const LayerArgs& a, bool tail, bool head);                  // ... and only this output set
+// The forms layer_h3_kernel and layer_h3_coop_kernel are instantiated in: which halves run, featB in point-fragment order (PF), the
+// folded layer.  layer_h3_form (layer_h3.hip) decides; Unserved = the folded layer without point-fragment featB (error text set).
+enum class H3Form { TailHeadPF, HeadPF, TailHead, Tail, Head, FoldTailHeadPF, FoldHeadPF, FoldTail, Unserved };
+H3Form layer_h3_form(const LayerArgs& a, bool tail, bool head);
 // the folded layer's weights of one layer (layer_wave.hip): wfold = W1f Wv [64][128] | b' [64] fp32, and its H3 tail / head streams
 int build_value_fold(const float* w1, const float* b1, const float* wqkv, const float* bqkv, const float* w2, const float* b2,
                      const float* w3, const float* b3, const float* wp, const float* bp, float* wfold, void* tail_out, void* head_out,

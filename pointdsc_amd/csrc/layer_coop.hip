@@ -23,30 +23,6 @@ constexpr int LC_WAVES = 4;
 
 struct CoopOps { u32x4 v[2][8][2][64]; };      // [set][k-step][hi | lo][lane]: the B operands of the next stage, 32 KiB
 
-// one weight chunk on the matrix cores, the instruction order of layer_h3_kernel
-template <bool QKV>
-__device__ __forceinline__ void coop_chunk(f32x16& acc, f32x16& cross, const WChunk& wc, const u32x4* oh, const u32x4* ol, bool first) {
-    const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    if (first) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wc.bias, 1.0f, zero, 0, 0, 0);
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-        if constexpr (QKV) {
-            const sp16x8 wh = __builtin_bit_cast(sp16x8, wc.v[2 * g]), wl = __builtin_bit_cast(sp16x8, wc.v[2 * g + 1]);
-            const sp16x8 bh = __builtin_bit_cast(sp16x8, oh[g]), bl = __builtin_bit_cast(sp16x8, ol[g]);
-            acc = PDSC_MFMA_X3(wl, bh, acc, 0, 0, 0);
-            acc = PDSC_MFMA_X3(wh, bl, acc, 0, 0, 0);
-            acc = PDSC_MFMA_X3(wh, bh, acc, 0, 0, 0);
-        } else {
-            const f16x8 wh = __builtin_bit_cast(f16x8, wc.v[2 * g]), wl = __builtin_bit_cast(f16x8, wc.v[2 * g + 1]);
-            const f16x8 bh = __builtin_bit_cast(f16x8, oh[g]), bl = __builtin_bit_cast(f16x8, ol[g]);
-            if (first && g == 0) cross = __builtin_amdgcn_mfma_f32_32x32x16_f16(wl, bh, zero, 0, 0, 0);
-            else cross = __builtin_amdgcn_mfma_f32_32x32x16_f16(wl, bh, cross, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh, bh, acc, 0, 0, 0);
-            cross = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh, bl, cross, 0, 0, 0);
-        }
-    }
-}
-
 template <bool QKV>
 __device__ __forceinline__ void coop_finish(const f32x16& acc, const f32x16& cross, f32x4 (&v)[4]) {
 #pragma unroll
@@ -68,14 +44,12 @@ __global__ __launch_bounds__(64 * LC_WAVES, NB <= 4 ? 2 : 1) void layer_h3_coop_
     const int lane = threadIdx.x & 63;
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int l31 = lane & 31, h = lane >> 5;
-    const int tpp = ceil_div_dev(a.N, 32);                          // tiles per pair
     const int gw = blockIdx.x;                                       // one workgroup = one tile
-    const int b = gw / tpp, tile = gw - b * tpp;
-    const int m0 = b * a.N + tile * 32;
-    const int valid = min(32, (a.nvalid ? a.nvalid[b] : a.N) - tile * 32);
-    if (valid <= 0) return;                                          // (ragged batches; uniform over the workgroup)
-    const bool live = l31 < valid;
-    const size_t row = (size_t)m0 + min(l31, valid - 1);
+    const TileDesc td = tile_desc(a, gw, l31);
+    if (td.valid <= 0) return;                                       // (ragged batches; uniform over the workgroup)
+    const int b = td.b, m0 = td.m0, valid = td.valid;
+    const bool live = td.live;
+    const size_t row = td.row;
     float* Vs = Vs_all[w];
     unsigned char* patch = reinterpret_cast<unsigned char*>(Vs);
     float rmax = 0.f;            // fp16 range sentinel (pdsc_common.h): largest |activation| this lane converts to an fp16 pair
@@ -115,7 +89,10 @@ __global__ __launch_bounds__(64 * LC_WAVES, NB <= 4 ? 2 : 1) void layer_h3_coop_
         u32x4 oh[4], ol[4];
 #pragma unroll
         for (int g = 0; g < 4; ++g) { oh[g] = ops.v[set][4 * c + g][0][lane]; ol[g] = ops.v[set][4 * c + g][1][lane]; }
-        coop_chunk<decltype(qkv_c)::value>(acc, cross, W[k % NB], oh, ol, first);
+        // the instruction order of layer_h3_kernel: bias step, then per k-step cross / main / cross (q|k|v: lo*hi, hi*lo, hi*hi)
+        if (first) acc = bias_step(W[k % NB]);
+        if constexpr (decltype(qkv_c)::value) mma_x3(acc, W[k % NB], oh, ol);
+        else mma_h3(acc, cross, W[k % NB], oh, ol, first);
         issue(std::integral_constant<int, k + NB>{});
     };
     using std::false_type; using std::true_type;
@@ -132,66 +109,35 @@ __global__ __launch_bounds__(64 * LC_WAVES, NB <= 4 ? 2 : 1) void layer_h3_coop_
 #pragma unroll
             for (int q = 0; q < 4; ++q) x0[q] = *reinterpret_cast<const f32x4*>(a.msg + row * VW + 8 * (4 * w + q) + 4 * h);
         } else {
-            // merge of the attention's key-split partials, the arithmetic of merge_partials_finish (merge_partials.h)
-            auto run = [&](auto ns_tag) {
+            with_split_count<MERGE_MAX_SPLIT_H3>(a.nsplit, [&](auto ns_tag) {
                 constexpr int NS = decltype(ns_tag)::value;
                 const size_t slot0 = (size_t)b * NS * a.Npad + (row - (size_t)b * a.N);
+                const MergeWeights<NS> mw = merge_row_weights<NS>(a.part_ml, slot0, (size_t)a.Npad);
+                // (own addresses: <T, H, PF, 4> keeps 253 registers with them, 254 through a shared address helper)
                 const bool pf = a.io_flags & PDSC_IO_PARTIALS_PF;
-                const size_t e0 = pf ? ((size_t)b * NS * a.Npad + (size_t)tile * 32) * VW + lane * 4 : slot0 * VW + 4 * h;
+                const size_t e0 = pf ? ((size_t)b * NS * a.Npad + (size_t)td.tile * 32) * VW + lane * 4 : slot0 * VW + 4 * h;
                 const int eq = pf ? 256 : 8;
                 // q per batch of loads: everything at once in the latency form; <= 32 registers of partials in flight in the
                 // two-workgroups-per-CU form (256 registers)
                 constexpr int GQ = NB > 4 ? 4 : NS <= 2 ? 4 : NS <= 4 ? 2 : 1;
-                float wsp[NS], ls[NS];
-#pragma unroll
-                for (int sp = 0; sp < NS; ++sp) {
-                    const float2 ml = *reinterpret_cast<const float2*>(a.part_ml + (slot0 + (size_t)sp * a.Npad) * 2);
-                    wsp[sp] = ml.x; ls[sp] = ml.y;
-                }
-                float mmax = wsp[0];
-#pragma unroll
-                for (int sp = 1; sp < NS; ++sp) mmax = fmaxf(mmax, wsp[sp]);
-                float den = 0.f;
-#pragma unroll
-                for (int sp = 0; sp < NS; ++sp) {
-                    wsp[sp] = __builtin_amdgcn_exp2f(wsp[sp] - mmax);
-                    den = fmaf(ls[sp], wsp[sp], den);
-                }
-                const float rden = 1.0f / den;
 #pragma unroll
                 for (int q0 = 0; q0 < 4; q0 += GQ) {
                     f32x4 pv[GQ][NS];
 #pragma unroll
                     for (int q = 0; q < GQ; ++q)
 #pragma unroll
-                        for (int sp = 0; sp < NS; ++sp)
-                            pv[q][sp] = *reinterpret_cast<const f32x4*>(a.part_o + e0 + (size_t)sp * a.Npad * VW + (size_t)eq * (4 * w + q0 + q));
+                        for (int sp = 0; sp < NS; ++sp) pv[q][sp] = *reinterpret_cast<const f32x4*>(a.part_o + e0 + (size_t)sp * a.Npad * VW + (size_t)eq * (4 * w + q0 + q));
 #pragma unroll
                     for (int q = 0; q < GQ; ++q) {
-                        f32x4 s = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                        for (int sp = 0; sp < NS; ++sp)
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) s[e] = fmaf(pv[q][sp][e], wsp[sp], s[e]);
 #pragma unroll
                         for (int e = 0; e < 4; ++e) {
-                            x0[q0 + q][e] = s[e] * rden;
+                            x0[q0 + q][e] = merge_apply<NS>(pv[q], mw, e);
                             if constexpr (GQ < 4) asm volatile("" : "+v"(x0[q0 + q][e]));    // materialise: the next batch's loads reuse the registers
                         }
                     }
                     if constexpr (GQ < 4) __builtin_amdgcn_sched_barrier(0);
                 }
-            };
-            switch (a.nsplit) {
-                case 1: run(std::integral_constant<int, 1>{}); break;
-                case 2: run(std::integral_constant<int, 2>{}); break;
-                case 3: run(std::integral_constant<int, 3>{}); break;
-                case 4: run(std::integral_constant<int, 4>{}); break;
-                case 5: run(std::integral_constant<int, 5>{}); break;
-                case 6: run(std::integral_constant<int, 6>{}); break;
-                case 7: run(std::integral_constant<int, 7>{}); break;
-                default: run(std::integral_constant<int, 8>{}); break;
-            }
+            });
         }
         if constexpr (F) {
             // relu(message + b') = fc2's operand (set 1, where fc1's output would go); the arithmetic of layer_h3_kernel's first_operand
@@ -213,6 +159,7 @@ __global__ __launch_bounds__(64 * LC_WAVES, NB <= 4 ? 2 : 1) void layer_h3_coop_
             make_kstep<true>(x0[2], x0[3], ph, pl, rmax); put(0, 2 * w + 1, ph, pl);
         }
         // residual rows of this wave's fc3 tile (needed three stages on: the loads fly under fc1 / fc2)
+        // (own addresses: 253 registers with them, 255 through a shared helper)
         {
             const bool pf = a.io_flags & PDSC_IO_RES_PF;
             const float* r0 = a.res + (pf ? (size_t)gw * PF_TILE_FLOATS + lane * 4 : row * PDSC_CHANNELS + 4 * h);
@@ -282,6 +229,8 @@ __global__ __launch_bounds__(64 * LC_WAVES, NB <= 4 ? 2 : 1) void layer_h3_coop_
         __syncthreads();
 
         // ---- pcn: 128 -> 128, output tile w; featB = relu -----------------------------------------------------------------
+        // (the featB, Q, K and V^T writers below are this kernel's own text: through the step helpers of layer_wave.h <T, H, PF, 4>
+        //  takes 255 registers instead of 253 (featB / Q / K) and <0, 1, 0, 4> 196 instead of 194 (V^T))
         run_chunk(std::integral_constant<int, 4>{}, 1, 0, true, false_type{});
         run_chunk(std::integral_constant<int, 5>{}, 1, 1, false, false_type{});
         coop_finish<false>(acc, cross, v);
@@ -386,20 +335,17 @@ __global__ __launch_bounds__(64 * LC_WAVES, NB <= 4 ? 2 : 1) void layer_h3_coop_
 
 int launch_layer_h3_coop(const LayerArgs& a, bool tail, bool head, hipStream_t st) {
     const dim3 grid(a.bs * ceil_div(a.N, 32)), block(64 * LC_WAVES);
-    const bool fb_pf = a.io_flags & PDSC_IO_FEATB_PF;
-    if (a.value_fold) {
-        if (tail && head && fb_pf) hipLaunchKernelGGL((layer_h3_coop_kernel<true, true, true, 4, true>), grid, block, 0, st, a);
-        else if (head && !tail && fb_pf) hipLaunchKernelGGL((layer_h3_coop_kernel<false, true, true, 4, true>), grid, block, 0, st, a);
-        else if (tail && !head) hipLaunchKernelGGL((layer_h3_coop_kernel<true, false, false, 4, true>), grid, block, 0, st, a);
-        else {
-            set_error("pdsc_layer_run(h3, four wavefronts per tile): the folded layer exists with point-fragment featB only");
-            return PDSC_ERR_ARG;
-        }
-    } else if (tail && head && fb_pf) hipLaunchKernelGGL((layer_h3_coop_kernel<true, true, true, 4>), grid, block, 0, st, a);
-    else if (head && !tail && fb_pf) hipLaunchKernelGGL((layer_h3_coop_kernel<false, true, true, 4>), grid, block, 0, st, a);
-    else if (tail && head) hipLaunchKernelGGL((layer_h3_coop_kernel<true, true, false, 4>), grid, block, 0, st, a);
-    else if (tail) hipLaunchKernelGGL((layer_h3_coop_kernel<true, false, false, 4>), grid, block, 0, st, a);
-    else hipLaunchKernelGGL((layer_h3_coop_kernel<false, true, false, 4>), grid, block, 0, st, a);
+    switch (layer_h3_form(a, tail, head)) {
+        case H3Form::FoldTailHeadPF: hipLaunchKernelGGL((layer_h3_coop_kernel<true, true, true, 4, true>), grid, block, 0, st, a); break;
+        case H3Form::FoldHeadPF: hipLaunchKernelGGL((layer_h3_coop_kernel<false, true, true, 4, true>), grid, block, 0, st, a); break;
+        case H3Form::FoldTail: hipLaunchKernelGGL((layer_h3_coop_kernel<true, false, false, 4, true>), grid, block, 0, st, a); break;
+        case H3Form::TailHeadPF: hipLaunchKernelGGL((layer_h3_coop_kernel<true, true, true, 4>), grid, block, 0, st, a); break;
+        case H3Form::HeadPF: hipLaunchKernelGGL((layer_h3_coop_kernel<false, true, true, 4>), grid, block, 0, st, a); break;
+        case H3Form::TailHead: hipLaunchKernelGGL((layer_h3_coop_kernel<true, true, false, 4>), grid, block, 0, st, a); break;
+        case H3Form::Tail: hipLaunchKernelGGL((layer_h3_coop_kernel<true, false, false, 4>), grid, block, 0, st, a); break;
+        case H3Form::Head: hipLaunchKernelGGL((layer_h3_coop_kernel<false, true, false, 4>), grid, block, 0, st, a); break;
+        case H3Form::Unserved: return PDSC_ERR_ARG;
+    }
     return check_launch("pdsc_layer_run(h3, four wavefronts per tile)");
 }
 

@@ -56,6 +56,8 @@ __global__ __launch_bounds__(64 * NWV, NBUF > 2 ? 1 : 2) void layer_h3_kernel(La
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int l31 = lane & 31, h = lane >> 5;
+    // (own prologue and own partial addresses instead of tile_desc and a shared address helper: the folded tail-only form
+    //  <1,0,..,1> has 206 registers with them, 210 through the helpers)
     const int tpp = ceil_div_dev(a.N, 32);                          // tiles per pair
     const int gw = blockIdx.x * NWV + wave;                         // one wave = one tile
     if (gw >= a.bs * tpp) return;                                    // (no workgroup barriers anywhere below)
@@ -85,7 +87,6 @@ __global__ __launch_bounds__(64 * NWV, NBUF > 2 ? 1 : 2) void layer_h3_kernel(La
     constexpr int NCH = num_chunks<T, H, F>();
     constexpr int VW = F ? LW_FOLD_VW : PDSC_CHANNELS;               // channels of the message / partials this launch merges
     constexpr int NQ = VW / 8;                                       // ... as 4-float pieces per lane
-    constexpr int SVL = F ? spl_v_lo<LW_FOLD_VW>() : SPL_VL;         // V^T lo plane of the tile image
     WChunk w[NBUF];
     static_for<0, NBUF - 1>([&](auto jc) {
         constexpr int j = decltype(jc)::value;
@@ -118,8 +119,7 @@ __global__ __launch_bounds__(64 * NWV, NBUF > 2 ? 1 : 2) void layer_h3_kernel(La
 #pragma unroll
             for (int kk = 0; kk < NQ / 2; ++kk) first_operand(kk);
         } else {
-            // merge of the attention's key-split partials, the arithmetic of merge_partials_finish (merge_partials.h)
-            auto run = [&](auto ns_tag) {
+            with_split_count<MERGE_MAX_SPLIT_H3>(a.nsplit, [&](auto ns_tag) {
                 constexpr int NS = decltype(ns_tag)::value;
                 constexpr int GQ = (NS <= 2 ? 16 : NS <= 4 ? 8 : 4) < NQ ? (NS <= 2 ? 16 : NS <= 4 ? 8 : 4) : NQ;   // pieces per batch of loads (<= 128 registers in flight)
                 const size_t slot0 = (size_t)b * NS * a.Npad + (row - (size_t)b * a.N);
@@ -127,22 +127,7 @@ __global__ __launch_bounds__(64 * NWV, NBUF > 2 ? 1 : 2) void layer_h3_kernel(La
                 const bool pf = a.io_flags & PDSC_IO_PARTIALS_PF;
                 const size_t e0 = pf ? ((size_t)b * NS * a.Npad + (size_t)tile * 32) * VW + lane * 4 : slot0 * VW + 4 * h;
                 const int eq = pf ? 256 : 8;
-                float wsp[NS], ls[NS];
-#pragma unroll
-                for (int sp = 0; sp < NS; ++sp) {
-                    const float2 ml = *reinterpret_cast<const float2*>(a.part_ml + (slot0 + (size_t)sp * a.Npad) * 2);
-                    wsp[sp] = ml.x; ls[sp] = ml.y;
-                }
-                float mmax = wsp[0];
-#pragma unroll
-                for (int sp = 1; sp < NS; ++sp) mmax = fmaxf(mmax, wsp[sp]);
-                float den = 0.f;
-#pragma unroll
-                for (int sp = 0; sp < NS; ++sp) {
-                    wsp[sp] = __builtin_amdgcn_exp2f(wsp[sp] - mmax);
-                    den = fmaf(ls[sp], wsp[sp], den);
-                }
-                const float rden = 1.0f / den;
+                const MergeWeights<NS> mw = merge_row_weights<NS>(a.part_ml, slot0, (size_t)a.Npad);
 #pragma unroll
                 for (int q0 = 0; q0 < NQ; q0 += GQ) {
                     f32x4 pv[GQ][NS];
@@ -154,14 +139,9 @@ __global__ __launch_bounds__(64 * NWV, NBUF > 2 ? 1 : 2) void layer_h3_kernel(La
                                                   : *reinterpret_cast<const f32x4*>(a.part_o + e0 + (size_t)sp * a.Npad * VW + eq * (q0 + q));
 #pragma unroll
                     for (int q = 0; q < GQ; ++q) {
-                        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                        for (int sp = 0; sp < NS; ++sp)
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) acc[e] = fmaf(pv[q][sp][e], wsp[sp], acc[e]);
 #pragma unroll
                         for (int e = 0; e < 4; ++e) {
-                            x0[q0 + q][e] = acc[e] * rden;
+                            x0[q0 + q][e] = merge_apply<NS>(pv[q], mw, e);
                             asm volatile("" : "+v"(x0[q0 + q][e]));     // materialise here (else the compiler sinks the arithmetic
                         }                                               // to the first MFMA and keeps every batch of loads live)
                     }
@@ -169,17 +149,7 @@ __global__ __launch_bounds__(64 * NWV, NBUF > 2 ? 1 : 2) void layer_h3_kernel(La
                     for (int kk = q0 / 2; kk < (q0 + GQ) / 2; ++kk) first_operand(kk);
                     __builtin_amdgcn_sched_barrier(0);               // keep the next batch's loads behind this batch's use
                 }
-            };
-            switch (a.nsplit) {
-                case 1: run(std::integral_constant<int, 1>{}); break;
-                case 2: run(std::integral_constant<int, 2>{}); break;
-                case 3: run(std::integral_constant<int, 3>{}); break;
-                case 4: run(std::integral_constant<int, 4>{}); break;
-                case 5: run(std::integral_constant<int, 5>{}); break;
-                case 6: run(std::integral_constant<int, 6>{}); break;
-                case 7: run(std::integral_constant<int, 7>{}); break;
-                default: run(std::integral_constant<int, 8>{}); break;
-            }
+            });
         }
     } else {
 #pragma unroll
@@ -228,19 +198,16 @@ __global__ __launch_bounds__(64 * NWV, NBUF > 2 ? 1 : 2) void layer_h3_kernel(La
                     // point-fragment order: this lane's registers are the next launch's residual registers (1 KiB per instruction)
                     if constexpr (!(EXP & (2 | 64))) *reinterpret_cast<f32x4*>(a.featB_out + (size_t)gw * PF_TILE_FLOATS + pf_offset_floats(4 * d.tile + s) + lane * 4) = v[s];
                 } else
-                    *reinterpret_cast<f32x4*>(patch + l31 * LW_PROW + 32 * s + 16 * h) = v[s];
+                    patch_put_featB(patch, lane, s, v[s]);
             }
             if constexpr (!FB_PF) {
                 if constexpr (s == 3) wave_lds_sync();
                 if constexpr (s >= 4) {           // 8 points x 128 B per store instruction
-                    const int pt = min(8 * (s - 4) + (lane >> 3), valid - 1), piece = lane & 7;     // (rows >= valid: copies of the last row)
-                    if constexpr (!(EXP & 2)) *reinterpret_cast<u32x4*>(a.featB_out + ((size_t)m0 + pt) * PDSC_CHANNELS + n0 + 4 * piece) = ev;
+                    const int pt = min(patch_line_row(lane, s - 4), valid - 1);     // (rows >= valid: copies of the last row)
+                    if constexpr (!(EXP & 2)) *reinterpret_cast<u32x4*>(featB_line(a.featB_out, (size_t)m0 + pt, n0, lane)) = ev;
                     else asm volatile("" :: "v"(ev));
                 }
-                if constexpr (s >= 3 && s < 7) {
-                    const int pt = 8 * (s - 3) + (lane >> 3), piece = lane & 7;
-                    ev = *reinterpret_cast<const u32x4*>(patch + pt * LW_PROW + 16 * piece);
-                }
+                if constexpr (s >= 3 && s < 7) ev = patch_line(patch, lane, s - 3);
             }
             if constexpr (s == 4 || s == 5)
                 make_kstep<false>(v[2 * (s - 4)], v[2 * (s - 4) + 1], xqh[2 * d.tile + (s - 4)], xql[2 * d.tile + (s - 4)], rmax);
@@ -249,20 +216,16 @@ __global__ __launch_bounds__(64 * NWV, NBUF > 2 ? 1 : 2) void layer_h3_kernel(La
             if constexpr (s < 4) range_note(rmax, v[s]);
             {
                 if constexpr (d.tile >= 4 && d.tile < 8) {
-                    // K image, chunk-major (split_layout.h): after the half swap lane (key l31, half h) holds chunk 4(t-4)+s of its
-                    // key for the hi (h = 0) / lo (h = 1) plane -- the 32 lanes of a half store 512 consecutive, aligned bytes
+                    // K image: chunk 4(t-4)+s of this lane's key, straight from registers
                     if constexpr (s < 4) {
-                        f32x4 z = v[s];
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) z[e] = live ? z[e] : 0.f;                    // keys beyond N are zero
-                        unsigned hi[2], lo[2];
-                        split4(z, hi, lo);
-                        const u32x4 ck = chunk_for_store(hi, lo);
-                        if constexpr (!(EXP & (2 | 16))) *reinterpret_cast<u32x4*>(img + (h ? SPL_KL : SPL_KH) + spl_k_offset(l31, 4 * (d.tile - 4) + s)) = ck;
+                        const u32x4 ck = k_chunk(v[s], live);
+                        if constexpr (!(EXP & (2 | 16))) k_chunk_store(img, lane, 4 * (d.tile - 4) + s, ck);
                         else asm volatile("" :: "v"(ck));
                     }
                 } else if constexpr (d.tile < 4) {
                     // Q rows (hi[128] | lo[128]) fp16 through the patch: row = (hi 64 B | lo 64 B) of this tile's 32 channels
+                    // (own put and row address: beside the own residual load the tail + head forms <1,1> have 240 registers with
+                    //  them, 244 through step helpers; the patch line read is the shared one)
                     if constexpr (s < 4) {
                         unsigned hi[2], lo[2];
                         split4(v[s], hi, lo);
@@ -275,34 +238,18 @@ __global__ __launch_bounds__(64 * NWV, NBUF > 2 ? 1 : 2) void layer_h3_kernel(La
                         if constexpr (!(EXP & (2 | 8))) *reinterpret_cast<u32x4*>(dst) = ev;
                         else asm volatile("" :: "v"(ev), "v"(dst));
                     }
-                    if constexpr (s >= 3 && s < 7) {
-                        const int pt = 8 * (s - 3) + (lane >> 3), piece = lane & 7;
-                        ev = *reinterpret_cast<const u32x4*>(patch + pt * LW_PROW + 16 * piece);
-                    }
+                    if constexpr (s >= 3 && s < 7) ev = patch_line(patch, lane, s - 3);
                 } else {
                     // V^T image: transpose 32 keys x 32 channels through the wave-private LDS patch
-                    if constexpr (s < 4) {
-                        f32x4 z = v[s];
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) z[e] = live ? z[e] : 0.f;
-                        *reinterpret_cast<f32x4*>(Vs + l31 * LW_VLD + 8 * s + 4 * h) = z;
-                    }
+                    if constexpr (s < 4) vt_put(Vs, lane, s, zero_unless(live, v[s]));
                     if constexpr (s == 3) wave_lds_sync();
-                    if constexpr (s == 4 || s == 6) {     // lane = (channel 16*it + lane/4, key chunk lane%4)
-                        const int cl = 16 * ((s - 4) >> 1) + (lane >> 2), jh = lane & 3;
-#pragma unroll
-                        for (int e = 0; e < 8; ++e) vt[e] = Vs[spl_v_key(jh, e) * LW_VLD + cl];
-                    }
-                    if constexpr (s == 5 || s == 7) {     // 256-byte runs: 16 channels of one key chunk
-                        const int cl = 16 * ((s - 5) >> 1) + (lane >> 2), jh = lane & 3;
-                        unsigned chi[4], clo[4];
-#pragma unroll
-                        for (int e = 0; e < 8; e += 2) split2(vt[e], vt[e + 1], chi[e / 2], clo[e / 2]);
-                        const int off = spl_v_offset_w<VW>(32 * (d.tile - 8) + cl, jh);
-                        if constexpr (!(EXP & (2 | 32))) {
-                            *reinterpret_cast<u32x4*>(img + SPL_VH + off) = u32x4{chi[0], chi[1], chi[2], chi[3]};
-                            *reinterpret_cast<u32x4*>(img + SVL + off) = u32x4{clo[0], clo[1], clo[2], clo[3]};
-                        } else asm volatile("" :: "v"(chi[0]), "v"(chi[1]), "v"(chi[2]), "v"(chi[3]), "v"(clo[0]), "v"(clo[1]), "v"(clo[2]), "v"(clo[3]), "v"(off));
+                    if constexpr (s == 4 || s == 6) vt_gather(Vs, lane, (s - 4) >> 1, vt);
+                    if constexpr (s == 5 || s == 7) {
+                        u32x4 ch, cl;
+                        vt_split(vt, ch, cl);
+                        const int off = vt_offset<VW>(lane, (s - 5) >> 1, 32 * (d.tile - 8));
+                        if constexpr (!(EXP & (2 | 32))) vt_store<VW>(img, off, ch, cl);
+                        else asm volatile("" :: "v"(ch), "v"(cl), "v"(off));
                     }
                 }
             }
@@ -315,6 +262,7 @@ __global__ __launch_bounds__(64 * NWV, NBUF > 2 ? 1 : 2) void layer_h3_kernel(La
         if constexpr (i + NBUF - 1 < NCH && !((EXP & 1) && i >= 1)) load_chunk<T, true, true, F>(w[(i + NBUF - 1) % NBUF], a, i + NBUF - 1, lane);
         if constexpr (T && d.stage == ST_FC2 && d.tile == 0 && !(EXP & 4)) {
             // residual rows for fc3's epilogue (the fc1 operand is dead, its registers are free): they come from HBM
+            // (own addresses: beside the own prologue the tail-only form <1,0> has 240 registers with them, 242 through a shared helper)
             const bool pf = a.io_flags & PDSC_IO_RES_PF;
             const float* r0 = a.res + (pf ? (size_t)gw * PF_TILE_FLOATS + lane * 4 : row * PDSC_CHANNELS + 4 * h);
             const int eq = pf ? 256 : 8;
@@ -322,12 +270,7 @@ __global__ __launch_bounds__(64 * NWV, NBUF > 2 ? 1 : 2) void layer_h3_kernel(La
             for (int q = 0; q < 16; ++q) y3[q] = *reinterpret_cast<const f32x4*>(r0 + eq * q);
         }
         const WChunk& wc = w[i % NBUF];
-        if constexpr (d.chunk == 0) {
-            // accumulator := bias, on the matrix pipe: one extra k-step whose A operand is the bias fragment (zero in the
-            // second k slot) and whose B operand is 1 -- no VALU work, and C = 0 is an inline constant
-            const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wc.bias, 1.0f, zero, 0, 0, 0);
-        }
+        if constexpr (d.chunk == 0) acc = bias_step(wc);
         // the previous output tile of the same stage left its epilogue pending: its 8 steps go between this tile's MFMA groups
         constexpr bool pending = d.tile > 0;
         using StageC = std::integral_constant<int, d.stage>;
@@ -393,6 +336,20 @@ bool launch_layer_h3_fits(const LayerArgs& a, bool tail, bool head) {
     return a.wf_tail || !tail;
 }
 
+H3Form layer_h3_form(const LayerArgs& a, bool tail, bool head) {
+    const bool fb_pf = a.io_flags & PDSC_IO_FEATB_PF;
+    if (a.value_fold) {
+        // the folded layer: the three forms of the point-fragment forward (head of layer 0, tail + head, tail of the last layer)
+        if (tail && head && fb_pf) return H3Form::FoldTailHeadPF;
+        if (head && !tail && fb_pf) return H3Form::FoldHeadPF;
+        if (tail && !head) return H3Form::FoldTail;
+        set_error("pdsc_layer_run(h3): the folded layer exists with point-fragment featB only");
+        return H3Form::Unserved;
+    }
+    if (head && fb_pf) return tail ? H3Form::TailHeadPF : H3Form::HeadPF;
+    return tail && head ? H3Form::TailHead : tail ? H3Form::Tail : H3Form::Head;
+}
+
 // launch shape (waves per workgroup, weight-ring depth), see the kernel's NWV / NBUF note
 static void h3_launch_shape(int tiles, int* nwv, int* nbuf) {
     *nwv = LW_WAVES; *nbuf = 2;
@@ -409,7 +366,8 @@ int launch_layer_h3(const LayerArgs& a, bool tail, bool head, hipStream_t st) {
     h3_launch_shape(waves, &nwv, &nbuf);
     if (a.value_fold) { nwv = LW_WAVES; nbuf = 2; }                // (the folded layer: product shape only)
     const dim3 grid(ceil_div(waves, nwv)), block(64 * nwv);
-    const bool fb_pf = a.io_flags & PDSC_IO_FEATB_PF;
+    const H3Form form = layer_h3_form(a, tail, head);
+    if (form == H3Form::Unserved) return PDSC_ERR_ARG;
     const bool timed = tail && head;
     int coop_tiles = PDSC_H3_COOP_TILES;
 #ifdef PDSC_EXPERIMENTS
@@ -439,42 +397,37 @@ int launch_layer_h3(const LayerArgs& a, bool tail, bool head, hipStream_t st) {
         PDSC_H3_LAUNCH_EXTRA(TT, HH, PF)                                                                                            \
         hipLaunchKernelGGL((layer_h3_kernel<TT, HH, false, 6, 0, PF>), grid, block, 0, st, a);                                       \
     } while (0)
-    if (a.value_fold) {
-        // the folded layer: the three forms of the point-fragment forward (head of layer 0, tail + head, tail of the last layer)
-        if (tail && head && fb_pf) hipLaunchKernelGGL((layer_h3_kernel<true, true, false, 6, 0, true, LW_WAVES, 2, true>), grid, block, 0, st, a);
-        else if (head && !tail && fb_pf) hipLaunchKernelGGL((layer_h3_kernel<false, true, false, 6, 0, true, LW_WAVES, 2, true>), grid, block, 0, st, a);
-        else if (tail && !head) hipLaunchKernelGGL((layer_h3_kernel<true, false, false, 6, 0, false, LW_WAVES, 2, true>), grid, block, 0, st, a);
-        else {
-            if (timed) profile_mark_end(PDSC_PROF_LAYER, st);
-            set_error("pdsc_layer_run(h3): the folded layer exists with point-fragment featB only");
-            return PDSC_ERR_ARG;
-        }
-    } else if (tail && head && fb_pf) {
+    switch (form) {
+        case H3Form::FoldTailHeadPF: hipLaunchKernelGGL((layer_h3_kernel<true, true, false, 6, 0, true, LW_WAVES, 2, true>), grid, block, 0, st, a); break;
+        case H3Form::FoldHeadPF: hipLaunchKernelGGL((layer_h3_kernel<false, true, false, 6, 0, true, LW_WAVES, 2, true>), grid, block, 0, st, a); break;
+        case H3Form::FoldTail: hipLaunchKernelGGL((layer_h3_kernel<true, false, false, 6, 0, false, LW_WAVES, 2, true>), grid, block, 0, st, a); break;
+        case H3Form::TailHeadPF: {
 #ifdef PDSC_LAYER_DIAG      // knock-out build (PDSC_HIPCC_EXTRA=-DPDSC_LAYER_DIAG python -m pointdsc_amd.build --force; tools/layer_bench.py)
-        const int ex = env_int("PDSC_LAYER_H3_EXP", 0);
-        if (ex == 1) hipLaunchKernelGGL((layer_h3_kernel<true, true, false, 6, 1, true>), grid, block, 0, st, a);
-        else if (ex == 2) hipLaunchKernelGGL((layer_h3_kernel<true, true, false, 6, 2, true>), grid, block, 0, st, a);
-        else if (ex == 4) hipLaunchKernelGGL((layer_h3_kernel<true, true, false, 6, 4, true>), grid, block, 0, st, a);
-        else if (ex == 7) hipLaunchKernelGGL((layer_h3_kernel<true, true, false, 6, 7, true>), grid, block, 0, st, a);
-        else if (ex == 8) hipLaunchKernelGGL((layer_h3_kernel<true, true, false, 6, 8, true>), grid, block, 0, st, a);
-        else if (ex == 16) hipLaunchKernelGGL((layer_h3_kernel<true, true, false, 6, 16, true>), grid, block, 0, st, a);
-        else if (ex == 32) hipLaunchKernelGGL((layer_h3_kernel<true, true, false, 6, 32, true>), grid, block, 0, st, a);
-        else if (ex == 64) hipLaunchKernelGGL((layer_h3_kernel<true, true, false, 6, 64, true>), grid, block, 0, st, a);
-        else
+            const int ex = env_int("PDSC_LAYER_H3_EXP", 0);
+            if (ex == 1) hipLaunchKernelGGL((layer_h3_kernel<true, true, false, 6, 1, true>), grid, block, 0, st, a);
+            else if (ex == 2) hipLaunchKernelGGL((layer_h3_kernel<true, true, false, 6, 2, true>), grid, block, 0, st, a);
+            else if (ex == 4) hipLaunchKernelGGL((layer_h3_kernel<true, true, false, 6, 4, true>), grid, block, 0, st, a);
+            else if (ex == 7) hipLaunchKernelGGL((layer_h3_kernel<true, true, false, 6, 7, true>), grid, block, 0, st, a);
+            else if (ex == 8) hipLaunchKernelGGL((layer_h3_kernel<true, true, false, 6, 8, true>), grid, block, 0, st, a);
+            else if (ex == 16) hipLaunchKernelGGL((layer_h3_kernel<true, true, false, 6, 16, true>), grid, block, 0, st, a);
+            else if (ex == 32) hipLaunchKernelGGL((layer_h3_kernel<true, true, false, 6, 32, true>), grid, block, 0, st, a);
+            else if (ex == 64) hipLaunchKernelGGL((layer_h3_kernel<true, true, false, 6, 64, true>), grid, block, 0, st, a);
+            else
 #endif
-        PDSC_H3_LAUNCH(true, true, true);
-    } else if (head && !tail && fb_pf) {
-        PDSC_H3_LAUNCH(false, true, true);
-    } else if (tail && head) {
+            PDSC_H3_LAUNCH(true, true, true);
+            break;
+        }
+        case H3Form::HeadPF: PDSC_H3_LAUNCH(false, true, true); break;
+        case H3Form::TailHead:
 #ifdef PDSC_EXPERIMENTS       // (the shader-clock trace form: experiments builds, tools/layer_trace.py)
-        if (a.trace) hipLaunchKernelGGL((layer_h3_kernel<true, true, true>), dim3(ceil_div(waves, LW_WAVES)), dim3(64 * LW_WAVES), 0, st, a);
-        else
+            if (a.trace) hipLaunchKernelGGL((layer_h3_kernel<true, true, true>), dim3(ceil_div(waves, LW_WAVES)), dim3(64 * LW_WAVES), 0, st, a);
+            else
 #endif
-        PDSC_H3_LAUNCH(true, true, false);
-    } else if (tail) {
-        PDSC_H3_LAUNCH(true, false, false);
-    } else {
-        PDSC_H3_LAUNCH(false, true, false);
+            PDSC_H3_LAUNCH(true, true, false);
+            break;
+        case H3Form::Tail: PDSC_H3_LAUNCH(true, false, false); break;
+        case H3Form::Head: PDSC_H3_LAUNCH(false, true, false); break;
+        case H3Form::Unserved: break;
     }
 #undef PDSC_H3_LAUNCH
 #undef PDSC_H3_LAUNCH_EXTRA

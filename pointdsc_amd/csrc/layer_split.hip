@@ -17,6 +17,7 @@
 #include "split_layout.h"
 #include "merge_partials.h"
 #include "layer_args.h"
+#include "layer_block.h"
 
 namespace pdsc {
 
@@ -105,85 +106,33 @@ __device__ __forceinline__ void store_tile(const f32x16& acc, const float* __res
     }
 }
 
-// 32x128 fp32 staging tile -> row-major global memory (ld floats per row), full 512-B rows
-__device__ __forceinline__ void tile_to_global(const float* F, float* __restrict__ dst, long long ld, int m0, int M, int t) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int f = t + 256 * i, row = f >> 5, c4 = f & 31;
-        if (m0 + row < M)
-            *reinterpret_cast<f32x4*>(dst + (size_t)(m0 + row) * ld + 4 * c4) = *reinterpret_cast<const f32x4*>(F + row * LX_FLD + 4 * c4);
-    }
-}
-
-// fp32 rows (already merged, or merged here from the attention's key-split partials) -> fp16 hi/lo activation tile
-__device__ __forceinline__ void rows_to_x(const LayerX3Args& a, const float* __restrict__ src, bool merge, int b, int m0, int M,
-                                          sp16* Xh, sp16* Xl, int t) {
+// fp32 rows (already merged, or, NS > 0, merged here from NS key-split partials of the attention) -> fp16 hi/lo activation tile
+template <int NS>
+__device__ __forceinline__ void rows_to_x(const LayerX3Args& a, const float* __restrict__ src, int b, int m0, int M, sp16* Xh, sp16* Xl, int t) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const int f = t + 256 * i, row = f >> 5, c4 = (f & 31) * 4;
         const int m = min(m0 + row, M - 1);
         f32x4 v;
-        if (!merge) {
+        if constexpr (NS == 0) {
             v = *reinterpret_cast<const f32x4*>(src + (size_t)m * PDSC_CHANNELS + c4);
         } else {
-            const size_t slot0 = (size_t)b * a.nsplit * a.Npad + (size_t)(m - b * a.N);
-            v = merge_partials_chunk(a.part_o, a.part_ml, slot0, (size_t)a.Npad, a.nsplit, c4);
+            const size_t slot0 = (size_t)b * NS * a.Npad + (size_t)(m - b * a.N);
+            const MergeWeights<NS> mw = merge_row_weights<NS>(a.part_ml, slot0, (size_t)a.Npad);
+            f32x4 pv[NS];
+#pragma unroll
+            for (int sp = 0; sp < NS; ++sp) pv[sp] = *reinterpret_cast<const f32x4*>(a.part_o + (slot0 + (size_t)sp * a.Npad) * PDSC_CHANNELS + c4);
+            v = merge_apply<NS>(pv, mw);
+            // the merged value as an fp32 number before it is split: without this the compiler folds the last multiply into the fp16
+            // conversion below (v_fma_mixlo_f16: one rounding instead of two), and hi differs from that of the merged msg on ties
+#pragma unroll
+            for (int e = 0; e < 4; ++e) asm volatile("" : "+v"(v[e]));
         }
         sp16x4 hi, lo;
 #pragma unroll
         for (int e = 0; e < 4; ++e) { sp16 x, y; split_sp16(v[e], x, y); hi[e] = x; lo[e] = y; }
         *reinterpret_cast<sp16x4*>(Xh + row * LX_XLD + c4) = hi;
         *reinterpret_cast<sp16x4*>(Xl + row * LX_XLD + c4) = lo;
-    }
-}
-
-// 32x128 fp32 staging tile (one of q / k / v for 32 points = one key tile) -> fp16 hi/lo streams (split_layout.h)
-template <int WHICH>
-__device__ __forceinline__ void stage_to_split(const float* F, sp16* __restrict__ qrows, unsigned char* __restrict__ img,
-                                               int valid, int t) {
-    if (WHICH == 0) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int f = t + 256 * i, row = f >> 5, c4 = (f & 31) * 4;
-            if (row < valid) {
-                const f32x4 v = *reinterpret_cast<const f32x4*>(F + row * LX_FLD + c4);
-                sp16x4 hi, lo;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) { sp16 x, y; split_sp16(v[e], x, y); hi[e] = x; lo[e] = y; }
-                sp16* dst = qrows + (size_t)row * SPL_Q_LD + c4;
-                *reinterpret_cast<sp16x4*>(dst) = hi;
-                *reinterpret_cast<sp16x4*>(dst + PDSC_CHANNELS) = lo;
-            }
-        }
-    } else if (WHICH == 1) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int f = t + 256 * i, key = f >> 4, chunk = f & 15;
-            const f32x4 v0 = *reinterpret_cast<const f32x4*>(F + key * LX_FLD + 8 * chunk);
-            const f32x4 v1 = *reinterpret_cast<const f32x4*>(F + key * LX_FLD + 8 * chunk + 4);
-            sp16x8 hi, lo;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const float v = key < valid ? (e < 4 ? v0[e & 3] : v1[e & 3]) : 0.f;
-                sp16 x, y; split_sp16(v, x, y); hi[e] = x; lo[e] = y;
-            }
-            *reinterpret_cast<sp16x8*>(img + SPL_KH + spl_k_offset(key, chunk)) = hi;
-            *reinterpret_cast<sp16x8*>(img + SPL_KL + spl_k_offset(key, chunk)) = lo;
-        }
-    } else {
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int f = t + 256 * i, ch = f & 127, jh = f >> 7;
-            sp16x8 hi, lo;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const int key = spl_v_key(jh, e);
-                const float v = key < valid ? F[key * LX_FLD + ch] : 0.f;
-                sp16 x, y; split_sp16(v, x, y); hi[e] = x; lo[e] = y;
-            }
-            *reinterpret_cast<sp16x8*>(img + SPL_VH + spl_v_offset(ch, jh)) = hi;
-            *reinterpret_cast<sp16x8*>(img + SPL_VL + spl_v_offset(ch, jh)) = lo;
-        }
     }
 }
 
@@ -205,7 +154,8 @@ __global__ __launch_bounds__(256, 3) void layer_x3_kernel(LayerX3Args a) {
         sp16x8 w1h[8], w1l[8], w2h[4], w2l[4], w3h[4], w3l[4];
         // ---- fc1: 128 -> 64 (+BN, ReLU): tiles {0,1} on waves {0,1} ----
         if (wave < 2) load_w<C>(a.w1, H, 32 * wave, l31, h, w1h, w1l);
-        rows_to_x(a, a.msg, a.msg == nullptr, b, m0, M, Xah, Xal, t);
+        if (a.msg) rows_to_x<0>(a, a.msg, b, m0, M, Xah, Xal, t);
+        else with_split_count<MERGE_MAX_SPLIT>(a.nsplit, [&](auto ns_tag) { rows_to_x<decltype(ns_tag)::value>(a, nullptr, b, m0, M, Xah, Xal, t); });
         __syncthreads();
         if (wave < 2) {
             load_w<H>(a.w2, H, 32 * wave, l31, h, w2h, w2l);                 // prefetch fc2 weights
@@ -231,11 +181,11 @@ __global__ __launch_bounds__(256, 3) void layer_x3_kernel(LayerX3Args a) {
         }
         __syncthreads();
         if (a.feat_out) {
-            tile_to_global(F, a.feat_out, C, m0, M, t);
+            tile_to_global<LX_FLD>(F, a.feat_out, C, m0, M, t);
             if (HAS_HEAD) __syncthreads();                                   // F is rewritten by the head
         }
     } else {
-        rows_to_x(a, a.feat_in, false, b, m0, M, Xbh, Xbl, t);
+        rows_to_x<0>(a, a.feat_in, b, m0, M, Xbh, Xbl, t);
         __syncthreads();
     }
 
@@ -249,7 +199,7 @@ __global__ __launch_bounds__(256, 3) void layer_x3_kernel(LayerX3Args a) {
             store_tile<true, false, true, true>(acc, a.bp, 32 * wave, 32 * wave, l31, h, nullptr, F, Xah, Xal);
         }
         __syncthreads();
-        tile_to_global(F, a.featB_out, C, m0, M, t);
+        tile_to_global<LX_FLD>(F, a.featB_out, C, m0, M, t);
         // ---- q|k|v: 128 -> 384 in three 128-column chunks staged through F ----
         unsigned char* img = a.kv ? a.kv + ((size_t)b * gridDim.x + blockIdx.x) * SPL_TILE_STRIDE : nullptr;
         const int valid = min(LX_ROWS, M - m0);
@@ -261,11 +211,11 @@ __global__ __launch_bounds__(256, 3) void layer_x3_kernel(LayerX3Args a) {
             __syncthreads();                                                 // previous readers of F are done
             store_tile<false, false, true, false>(acc, a.bq, n0, 32 * wave, l31, h, nullptr, F, nullptr, nullptr);
             __syncthreads();
-            if (a.qkv_out) tile_to_global(F, a.qkv_out + C * c, 3 * C, m0, M, t);
+            if (a.qkv_out) tile_to_global<LX_FLD>(F, a.qkv_out + C * c, 3 * C, m0, M, t);
             if (a.qs) {
-                if (c == 0) stage_to_split<0>(F, a.qs + (size_t)m0 * SPL_Q_LD, img, valid, t);
-                else if (c == 1) stage_to_split<1>(F, nullptr, img, valid, t);
-                else stage_to_split<2>(F, nullptr, img, valid, t);
+                if (c == 0) tile_to_split<0, LX_FLD>(F, a.qs + (size_t)m0 * SPL_Q_LD, img, valid, t);
+                else if (c == 1) tile_to_split<1, LX_FLD>(F, nullptr, img, valid, t);
+                else tile_to_split<2, LX_FLD>(F, nullptr, img, valid, t);
             }
         }
     }

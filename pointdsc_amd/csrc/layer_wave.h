@@ -131,17 +131,24 @@ __device__ __forceinline__ void mma_f32(f32x16& acc, const WChunk& w, const f32x
         for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(w.v[q][e], x[q][e], acc, 0, 0, 0);
 }
 
-__device__ __forceinline__ void mma_x3(f32x16& acc, const WChunk& w, const sp16x8* xh, const sp16x8* xl) {
+// accumulator := bias, on the matrix pipe: one extra k-step whose A operand is the bias fragment (zero in the second k slot) and
+// whose B operand is 1 -- no VALU work, and C = 0 is an inline constant
+__device__ __forceinline__ f32x16 bias_step(const WChunk& w) {
+    const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    return __builtin_amdgcn_mfma_f32_32x32x2f32(w.bias, 1.0f, zero, 0, 0, 0);
+}
+
+// one weight chunk (4 k-steps as (hi, lo) slot pairs) of the split q|k|v projection: small terms first, one accumulator
+__device__ __forceinline__ void mma_x3(f32x16& acc, const WChunk& w, const u32x4* xh, const u32x4* xl) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const sp16x8 wh = __builtin_bit_cast(sp16x8, w.v[2 * i]), wl = __builtin_bit_cast(sp16x8, w.v[2 * i + 1]);
-        acc = PDSC_MFMA_X3(wl, xh[i], acc, 0, 0, 0);
-        acc = PDSC_MFMA_X3(wh, xl[i], acc, 0, 0, 0);
-        acc = PDSC_MFMA_X3(wh, xh[i], acc, 0, 0, 0);
+        const sp16x8 bh = __builtin_bit_cast(sp16x8, xh[i]), bl = __builtin_bit_cast(sp16x8, xl[i]);
+        acc = PDSC_MFMA_X3(wl, bh, acc, 0, 0, 0);
+        acc = PDSC_MFMA_X3(wh, bl, acc, 0, 0, 0);
+        acc = PDSC_MFMA_X3(wh, bh, acc, 0, 0, 0);
     }
 }
-
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ unsigned pack2(sp16 a, sp16 b) {
     return (unsigned)__builtin_bit_cast(unsigned short, a) | ((unsigned)__builtin_bit_cast(unsigned short, b) << 16);
@@ -204,10 +211,7 @@ __device__ __forceinline__ u32x4 chunk_for_store(const unsigned (&hi)[2], const 
 // `b` = channels 16kk + 8 + 4h + e of its point; the k-step wants channels 16kk + 8h .. +7 in lane-half h.  F16 selects the
 // fp16 hi / scaled-lo split (H3) instead of the unscaled fp16 hi / lo split.
 template <bool F16>
-__device__ __forceinline__ void make_kstep(const f32x4& a_in, const f32x4& b_in, u32x4& oh, u32x4& ol, float& rmax) {
-    f32x4 a = a_in, b = b_in;
-    range_note(rmax, a);
-    range_note(rmax, b);
+__device__ __forceinline__ void make_kstep(const f32x4& a, const f32x4& b, u32x4& oh, u32x4& ol) {
     unsigned ha[2], la[2], hb[2], lb[2];
     if constexpr (F16) { split4h(a, ha, la); split4h(b, hb, lb); }
     else { split4(a, ha, la); split4(b, hb, lb); }
@@ -217,15 +221,13 @@ __device__ __forceinline__ void make_kstep(const f32x4& a_in, const f32x4& b_in,
     ol = u32x4{la[0], la[1], lb[0], lb[1]};
 }
 
+// ... with the values noted by the fp16 range sentinel (pdsc_common.h)
 template <bool F16>
-__device__ __forceinline__ void make_kstep(const f32x4& a, const f32x4& b, u32x4& oh, u32x4& ol) {
-    unsigned ha[2], la[2], hb[2], lb[2];
-    if constexpr (F16) { split4h(a, ha, la); split4h(b, hb, lb); }
-    else { split4(a, ha, la); split4(b, hb, lb); }
-    half_swap(ha[0], hb[0]); half_swap(ha[1], hb[1]);
-    half_swap(la[0], lb[0]); half_swap(la[1], lb[1]);
-    oh = u32x4{ha[0], ha[1], hb[0], hb[1]};
-    ol = u32x4{la[0], la[1], lb[0], lb[1]};
+__device__ __forceinline__ void make_kstep(const f32x4& a_in, const f32x4& b_in, u32x4& oh, u32x4& ol, float& rmax) {
+    f32x4 a = a_in, b = b_in;
+    range_note(rmax, a);
+    range_note(rmax, b);
+    make_kstep<F16>(a, b, oh, ol);
 }
 
 // one weight chunk (4 k-steps as (hi, lo') slot pairs) in the H3 arithmetic: main accumulator <- hi*hi, cross <- the two
@@ -253,6 +255,90 @@ __device__ __forceinline__ void wave_lds_sync() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// ---- the 32-point tile of a wavefront (layer_coop.hip: of a workgroup) -----------------------------------------------------
+// tile `gw` of the launch = tile `tile` of pair b, rows m0 .. m0 + valid - 1.  valid <= 0: nothing to do (past the launch's last
+// tile, or, in a ragged batch, past the pair's own rows).  Lane (l31, h) works on row `row`; lanes beyond the pair's last point
+// (!live) on a copy of its last row.
+struct TileDesc {
+    int b, tile, m0, valid;
+    bool live;
+    size_t row;
+};
+__device__ __forceinline__ TileDesc tile_desc(const LayerArgs& a, int gw, int l31) {
+    const int tpp = ceil_div_dev(a.N, 32);                          // tiles per pair
+    TileDesc t{};
+    if (gw >= a.bs * tpp) return t;
+    t.b = gw / tpp;
+    t.tile = gw - t.b * tpp;
+    t.m0 = t.b * a.N + t.tile * 32;
+    t.valid = min(32, (a.nvalid ? a.nvalid[t.b] : a.N) - t.tile * 32);
+    t.live = l31 < t.valid;
+    t.row = (size_t)t.m0 + min(l31, t.valid - 1);
+    return t;
+}
+
+// ---- writers of the attention's operand streams (split_layout.h) and of featB rows, one step each ------------------------------
+// v = piece g of an output tile: channels n0 + 8g + 4h + e of point l31 in lane (l31, h).  layer_h3_kernel issues the steps one at
+// a time between MFMA groups, the other kernels in loops.  Which rows a line store covers (predicated, or clamped to copies of the
+// last row) is the caller's: the stores take the row.
+
+// piece g of a featB tile into the patch: row l31 = the tile's 32 channels as fp32 (128 B)
+__device__ __forceinline__ void patch_put_featB(unsigned char* patch, int lane, int g, const f32x4& v) {
+    *reinterpret_cast<f32x4*>(patch + (lane & 31) * LW_PROW + 32 * g + 16 * (lane >> 5)) = v;
+}
+// pass `it` of 4 over the patch: lane = (row 8 it + lane / 8, 16-byte piece lane % 8), i.e. 8 rows x 128 B per instruction
+__device__ __forceinline__ int patch_line_row(int lane, int it) { return 8 * it + (lane >> 3); }
+__device__ __forceinline__ u32x4 patch_line(const unsigned char* patch, int lane, int it) {
+    return *reinterpret_cast<const u32x4*>(patch + patch_line_row(lane, it) * LW_PROW + 16 * (lane & 7));
+}
+// ... and its store as 128 B of row `m` of featB (channels n0 ..)
+__device__ __forceinline__ float* featB_line(float* featB, size_t m, int n0, int lane) { return featB + m * PDSC_CHANNELS + n0 + 4 * (lane & 7); }
+
+// keys beyond the pair's end are zero in the K and V^T images
+__device__ __forceinline__ f32x4 zero_unless(bool live, const f32x4& v) {
+    f32x4 z;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) z[e] = live ? v[e] : 0.f;
+    return z;
+}
+// K image, chunk-major: after the half swap lane (key l31, half h) holds chunk `chunk` of its key for the hi (h = 0) / lo (h = 1)
+// plane -- the 32 lanes of a half store 512 consecutive, aligned bytes
+__device__ __forceinline__ u32x4 k_chunk(const f32x4& v, bool live) {
+    unsigned hi[2], lo[2];
+    split4(zero_unless(live, v), hi, lo);
+    return chunk_for_store(hi, lo);
+}
+__device__ __forceinline__ void k_chunk_store(unsigned char* img, int lane, int chunk, const u32x4& ck) {
+    *reinterpret_cast<u32x4*>(img + ((lane >> 5) ? SPL_KL : SPL_KH) + spl_k_offset(lane & 31, chunk)) = ck;
+}
+
+// V^T image: 32 keys x 32 channels are transposed through the patch (as floats, LW_VLD per key row)
+__device__ __forceinline__ void vt_put(float* Vs, int lane, int g, const f32x4& z) {
+    *reinterpret_cast<f32x4*>(Vs + (lane & 31) * LW_VLD + 8 * g + 4 * (lane >> 5)) = z;
+}
+// pass `it` of 2: lane = (channel 16 it + lane / 4 of the tile, key chunk jh = lane % 4) gathers its chunk's 8 keys ...
+__device__ __forceinline__ int vt_channel(int lane, int it) { return 16 * it + (lane >> 2); }
+__device__ __forceinline__ void vt_gather(const float* Vs, int lane, int it, float (&vt)[8]) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) vt[e] = Vs[spl_v_key(lane & 3, e) * LW_VLD + vt_channel(lane, it)];
+}
+// ... splits them into the 16 bytes of the hi and of the lo plane ...
+__device__ __forceinline__ void vt_split(const float (&vt)[8], u32x4& ch, u32x4& cl) {
+    unsigned hi[4], lo[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) split2(vt[2 * e], vt[2 * e + 1], hi[e], lo[e]);
+    ch = u32x4{hi[0], hi[1], hi[2], hi[3]};
+    cl = u32x4{lo[0], lo[1], lo[2], lo[3]};
+}
+// ... and stores them at channel n0 + vt_channel of the image (VW channels per plane): 256-byte runs of 16 channels
+template <int VW>
+__device__ __forceinline__ int vt_offset(int lane, int it, int n0) { return spl_v_offset_w<VW>(n0 + vt_channel(lane, it), lane & 3); }
+template <int VW>
+__device__ __forceinline__ void vt_store(unsigned char* img, int off, const u32x4& ch, const u32x4& cl) {
+    *reinterpret_cast<u32x4*>(img + SPL_VH + off) = ch;
+    *reinterpret_cast<u32x4*>(img + spl_v_lo<VW>() + off) = cl;
 }
 
 }  // namespace pdsc

@@ -40,15 +40,12 @@ __global__ __launch_bounds__(64 * LW_WAVES, 2) void layer_wave_kernel(LayerArgs 
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int l31 = lane & 31, h = lane >> 5;
-    const int tpp = ceil_div_dev(a.N, 32);                          // tiles per pair
     const int gw = blockIdx.x * LW_WAVES + wave;                    // one wave = one tile
-    if (gw >= a.bs * tpp) return;                                    // (no workgroup barriers anywhere below)
-    const int b = gw / tpp, tile = gw - b * tpp;
-    const int m0 = b * a.N + tile * 32;
-    const int valid = min(32, (a.nvalid ? a.nvalid[b] : a.N) - tile * 32);
-    if (valid <= 0) return;                                          // (ragged batches: tile past the pair's own rows)
-    const bool live = l31 < valid;
-    const size_t row = (size_t)m0 + min(l31, valid - 1);
+    const TileDesc td = tile_desc(a, gw, l31);
+    if (td.valid <= 0) return;                                       // (no workgroup barriers anywhere below)
+    const int m0 = td.m0, valid = td.valid;
+    const bool live = td.live;
+    const size_t row = td.row;
     float* Vs = Vs_all[wave];
     unsigned char* patch = reinterpret_cast<unsigned char*>(Vs);     // the same 32 x 144 B patch, as bytes
 
@@ -64,7 +61,7 @@ __global__ __launch_bounds__(64 * LW_WAVES, 2) void layer_wave_kernel(LayerArgs 
     load_chunk<T, X3, FRAG>(w[0], a, 0, lane);
 
     f32x4 x0[16], x1[8], x2[8], y3[16], x4[16];
-    sp16x8 xh[8], xl[8];
+    u32x4 xh[8], xl[8];                                              // X3: B operands of q|k|v
     u32x4 a0h[8], a0l[8], a1h[4], a1l[4], a2h[4], a2l[4], ayh[8], ayl[8];     // HX: B operands of fc1 / fc2 / fc3 / PointCN
     if (T) {
         if (a.msg) {
@@ -75,46 +72,24 @@ __global__ __launch_bounds__(64 * LW_WAVES, 2) void layer_wave_kernel(LayerArgs 
                 for (int kk = 0; kk < 8; ++kk) make_kstep<true>(x0[2 * kk], x0[2 * kk + 1], a0h[kk], a0l[kk]);
             }
         } else {
-            // merge of the attention's key-split partials, the arithmetic of merge_partials_finish (merge_partials.h)
-            auto run = [&](auto ns_tag) {
+            with_split_count<MERGE_MAX_SPLIT>(a.nsplit, [&](auto ns_tag) {
                 constexpr int NS = decltype(ns_tag)::value;
-                constexpr int GQ = NS <= 2 ? 16 : 8;                 // k-steps per batch of loads (up to 128 registers in flight)
-                const size_t slot0 = (size_t)b * NS * a.Npad + (row - (size_t)b * a.N);
-                float wsp[NS], ls[NS];
-#pragma unroll
-                for (int sp = 0; sp < NS; ++sp) {
-                    const float2 ml = *reinterpret_cast<const float2*>(a.part_ml + (slot0 + (size_t)sp * a.Npad) * 2);
-                    wsp[sp] = ml.x; ls[sp] = ml.y;
-                }
-                float mmax = wsp[0];
-#pragma unroll
-                for (int sp = 1; sp < NS; ++sp) mmax = fmaxf(mmax, wsp[sp]);
-                float den = 0.f;
-#pragma unroll
-                for (int sp = 0; sp < NS; ++sp) {
-                    wsp[sp] = __builtin_amdgcn_exp2f(wsp[sp] - mmax);
-                    den = fmaf(ls[sp], wsp[sp], den);
-                }
-                const float rden = 1.0f / den;
+                constexpr int GQ = NS <= 2 ? 16 : 8;                 // pieces per batch of loads (up to 128 registers in flight)
+                const size_t slot0 = (size_t)td.b * NS * a.Npad + (row - (size_t)td.b * a.N);
+                const MergeWeights<NS> mw = merge_row_weights<NS>(a.part_ml, slot0, (size_t)a.Npad);
+                // (rows only, own addresses: <1,0,0,1,0,1> has 221 registers with them, 222 through a shared address helper)
 #pragma unroll
                 for (int q0 = 0; q0 < 16; q0 += GQ) {
                     f32x4 pv[GQ][NS];
 #pragma unroll
                     for (int q = 0; q < GQ; ++q)
 #pragma unroll
-                        for (int sp = 0; sp < NS; ++sp)
-                            pv[q][sp] = *reinterpret_cast<const f32x4*>(a.part_o + (slot0 + (size_t)sp * a.Npad) * PDSC_CHANNELS +
-                                                                        8 * (q0 + q) + 4 * h);
+                        for (int sp = 0; sp < NS; ++sp) pv[q][sp] = *reinterpret_cast<const f32x4*>(a.part_o + (slot0 + (size_t)sp * a.Npad) * PDSC_CHANNELS + 8 * (q0 + q) + 4 * h);
 #pragma unroll
                     for (int q = 0; q < GQ; ++q) {
-                        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                        for (int sp = 0; sp < NS; ++sp)
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) acc[e] = fmaf(pv[q][sp][e], wsp[sp], acc[e]);
 #pragma unroll
                         for (int e = 0; e < 4; ++e) {
-                            x0[q0 + q][e] = acc[e] * rden;
+                            x0[q0 + q][e] = merge_apply<NS>(pv[q], mw, e);
                             asm volatile("" : "+v"(x0[q0 + q][e]));     // materialise here (else the compiler sinks the arithmetic
                         }                                               // to the first MFMA and keeps every batch of loads live)
                     }
@@ -124,13 +99,7 @@ __global__ __launch_bounds__(64 * LW_WAVES, 2) void layer_wave_kernel(LayerArgs 
                     }
                     __builtin_amdgcn_sched_barrier(0);               // keep the next batch's loads behind this batch's use
                 }
-            };
-            switch (a.nsplit) {
-                case 1: run(std::integral_constant<int, 1>{}); break;
-                case 2: run(std::integral_constant<int, 2>{}); break;
-                case 3: run(std::integral_constant<int, 3>{}); break;
-                default: run(std::integral_constant<int, 4>{}); break;
-            }
+            });
         }
     } else {
 #pragma unroll
@@ -166,10 +135,7 @@ __global__ __launch_bounds__(64 * LW_WAVES, 2) void layer_wave_kernel(LayerArgs 
         }
         const WChunk& wc = w[buf_of(i)];
         if constexpr (d.chunk == 0) {
-            // accumulator := bias, on the matrix pipe: one extra k-step whose A operand is the bias fragment (zero in the
-            // second k slot) and whose B operand is 1 -- no VALU work, and C = 0 is an inline constant
-            const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wc.bias, 1.0f, zero, 0, 0, 0);
+            acc = bias_step(wc);
         }
         if constexpr (HX && d.stage == ST_FC1) mma_h3(acc, cross, wc, a0h + 4 * d.chunk, a0l + 4 * d.chunk, d.chunk == 0);
         else if constexpr (HX && d.stage == ST_FC2) mma_h3(acc, cross, wc, a1h, a1l, true);
@@ -221,31 +187,26 @@ __global__ __launch_bounds__(64 * LW_WAVES, 2) void layer_wave_kernel(LayerArgs 
                 for (int g = 0; g < 4; ++g) {
 #pragma unroll
                     for (int e = 0; e < 4; ++e) x4[4 * d.tile + g][e] = fmaxf(v[g][e], 0.f);
-                    *reinterpret_cast<f32x4*>(patch + l31 * LW_PROW + 32 * g + 16 * h) = x4[4 * d.tile + g];
+                    patch_put_featB(patch, lane, g, x4[4 * d.tile + g]);
                 }
                 wave_lds_sync();
 #pragma unroll
                 for (int it = 0; it < 4; ++it) {          // 8 points x 128 B (one full line each) per store instruction
-                    const int pt = 8 * it + (lane >> 3), piece = lane & 7;
-                    const f32x4 val = *reinterpret_cast<const f32x4*>(patch + pt * LW_PROW + 16 * piece);
-                    if (pt < valid) *reinterpret_cast<f32x4*>(a.featB_out + ((size_t)m0 + pt) * PDSC_CHANNELS + n0 + 4 * piece) = val;
+                    const int pt = patch_line_row(lane, it);
+                    const u32x4 val = patch_line(patch, lane, it);
+                    if (pt < valid) *reinterpret_cast<u32x4*>(featB_line(a.featB_out, (size_t)m0 + pt, n0, lane)) = val;
                 }
                 wave_lds_sync();
                 if constexpr (X3 && d.tile == 3) {
                     // featB -> fp16 hi / lo operands of the 16-wide k-steps: step kk, lane-half h <- channels 16kk+8h..+7
 #pragma unroll
-                    for (int kk = 0; kk < 8; ++kk) {
-                        unsigned ha[2], la[2], hb[2], lb[2];
-                        split4(x4[2 * kk], ha, la);              // channels 16kk + 4h + e
-                        split4(x4[2 * kk + 1], hb, lb);          // channels 16kk + 8 + 4h + e
-                        half_swap(ha[0], hb[0]); half_swap(ha[1], hb[1]);
-                        half_swap(la[0], lb[0]); half_swap(la[1], lb[1]);
-                        xh[kk] = __builtin_bit_cast(sp16x8, u32x4{ha[0], ha[1], hb[0], hb[1]});
-                        xl[kk] = __builtin_bit_cast(sp16x8, u32x4{la[0], la[1], lb[0], lb[1]});
-                    }
+                    for (int kk = 0; kk < 8; ++kk) make_kstep<false>(x4[2 * kk], x4[2 * kk + 1], xh[kk], xl[kk]);
                 }
             } else {
                 // q | k | v, output tile d.tile of 12: tiles 0..3 = q, 4..7 = k, 8..11 = v
+                // (the three writers below are this kernel's own text: <0,1,0,0,0,0> has 198 registers with it and 200 through the
+                //  step helpers of layer_wave.h, <*,1,1,1,0,0> 233 and 238; its K image goes through the patch and its row stores are
+                //  predicated, which the helpers' users do not do)
                 if (a.qkv_out && live) {
 #pragma unroll
                     for (int g = 0; g < 4; ++g)

@@ -1,8 +1,12 @@
-// Merge of the attention's key-split partials for one (query row, 4-channel chunk): the arithmetic of
-// attention_combine_kernel (attention.hip), used by the fused layer kernels so that the merge costs no launch and
-// msg makes no round trip through HBM.  All loads are issued before any is used (the split count is a run-time value:
-// a plain loop over it serialises 2 * nsplit dependent HBM round trips per chunk).
+// Merge of the attention's key-split partials for one query row: the arithmetic of attention_combine_kernel (attention.hip), used
+// by the fused layer kernels so that the merge costs no launch and msg makes no round trip through HBM.  Every layer kernel merges
+// with the pieces below -- the weights of a row, then one fused multiply-add chain per 4-channel piece -- so they agree bit for bit
+// by construction.  The split count is a compile-time constant at every site (with_split_count): registers for exactly that many
+// partials, and the loads of a batch of pieces can all be issued before any is used (a loop over a run-time count serialises
+// 2 * nsplit dependent HBM round trips per piece).  What stays with each kernel is how many pieces it loads per batch
+// and the addresses it loads them from (a shared address helper cost every wavefront kernel registers; the counts are at each site).
 #pragma once
+#include <type_traits>
 #include "pdsc_common.h"
 
 namespace pdsc {
@@ -12,78 +16,74 @@ constexpr int MERGE_MAX_SPLIT_BLOCK = 8;  // ... except in the workgroup-per-til
 constexpr int MERGE_MAX_SPLIT_H3 = 8;     // ... and in layer_h3.hip (r03: the per-GPU shares of the 8-GPU configurations -- 1-3 pairs of
                                           //     N = 5000 / 10000 -- are planned with 5-8 key splits: no combine launch, no msg round trip)
 
-__device__ __forceinline__ f32x4 merge_partials_chunk(const float* __restrict__ part_o, const float* __restrict__ part_ml,
-                                                      size_t slot0, size_t sp_stride, int ns, int c4) {
-    float mx[MERGE_MAX_SPLIT], ls[MERGE_MAX_SPLIT];
-    f32x4 pv[MERGE_MAX_SPLIT];
-#pragma unroll
-    for (int sp = 0; sp < MERGE_MAX_SPLIT; ++sp) {
-        const size_t slot = slot0 + (size_t)min(sp, ns - 1) * sp_stride;     // surplus slots repeat the last split
-        const float2 ml = *reinterpret_cast<const float2*>(part_ml + slot * 2);
-        mx[sp] = ml.x; ls[sp] = ml.y;
-        pv[sp] = *reinterpret_cast<const f32x4*>(part_o + slot * PDSC_CHANNELS + c4);
-    }
-    float mmax = mx[0];
-#pragma unroll
-    for (int sp = 1; sp < MERGE_MAX_SPLIT; ++sp) mmax = fmaxf(mmax, mx[sp]);   // repeats do not change the maximum
-    float L = 0.f;
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int sp = 0; sp < MERGE_MAX_SPLIT; ++sp) {
-        if (sp < ns) {                                                       // wave-uniform
-            const float w = __builtin_amdgcn_exp2f(mx[sp] - mmax);
-            L = fmaf(ls[sp], w, L);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) acc[e] = fmaf(pv[sp][e], w, acc[e]);
+// f(std::integral_constant<int, NS>{}) with NS = the run-time split count `ns` (wave-uniform); counts of MAX and above take MAX
+template <int MAX, class F>
+__device__ __forceinline__ void with_split_count(int ns, F&& f) {
+    static_assert(MAX == 4 || MAX == 8, "the layer kernels merge up to 4 or up to 8 splits");
+    using std::integral_constant;
+    if constexpr (MAX == 4) {
+        switch (ns) {
+            case 1: f(integral_constant<int, 1>{}); break;
+            case 2: f(integral_constant<int, 2>{}); break;
+            case 3: f(integral_constant<int, 3>{}); break;
+            default: f(integral_constant<int, 4>{}); break;
+        }
+    } else {
+        switch (ns) {
+            case 1: f(integral_constant<int, 1>{}); break;
+            case 2: f(integral_constant<int, 2>{}); break;
+            case 3: f(integral_constant<int, 3>{}); break;
+            case 4: f(integral_constant<int, 4>{}); break;
+            case 5: f(integral_constant<int, 5>{}); break;
+            case 6: f(integral_constant<int, 6>{}); break;
+            case 7: f(integral_constant<int, 7>{}); break;
+            default: f(integral_constant<int, 8>{}); break;
         }
     }
-    const float r = 1.0f / L;              // one correctly-rounded reciprocal per row, then multiplies (all merge sites agree)
-    f32x4 v;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] = acc[e] * r;
-    return v;
 }
 
-
-// Two-phase form for callers that merge several chunks per thread: issue the loads of ALL chunks first (one round trip
-// of latency instead of one per chunk), then do the arithmetic.  NS = compile-time split count (registers for exactly
-// NS splits, no duplicate loads).
+// weights of one row: w[sp] = exp2(m_sp - max m), rden = 1 / sum l_sp w[sp]
 template <int NS>
-struct MergeLoads {
-    float mx[NS], ls[NS];
-    f32x4 pv[NS];
+struct MergeWeights {
+    float w[NS], rden;
 };
 
+// slot0 = the row's slot in split 0 of its pair, sp_stride = slots per split (Npad)
 template <int NS>
-__device__ __forceinline__ void merge_partials_load(MergeLoads<NS>& L, const float* __restrict__ part_o,
-                                                    const float* __restrict__ part_ml, size_t slot0, size_t sp_stride, int c4) {
+__device__ __forceinline__ MergeWeights<NS> merge_row_weights(const float* __restrict__ part_ml, size_t slot0, size_t sp_stride) {
+    MergeWeights<NS> r;
+    float ls[NS];
 #pragma unroll
     for (int sp = 0; sp < NS; ++sp) {
-        const size_t slot = slot0 + (size_t)sp * sp_stride;
-        const float2 ml = *reinterpret_cast<const float2*>(part_ml + slot * 2);
-        L.mx[sp] = ml.x; L.ls[sp] = ml.y;
-        L.pv[sp] = *reinterpret_cast<const f32x4*>(part_o + slot * PDSC_CHANNELS + c4);
+        const float2 ml = *reinterpret_cast<const float2*>(part_ml + (slot0 + (size_t)sp * sp_stride) * 2);
+        r.w[sp] = ml.x; ls[sp] = ml.y;
     }
+    float mmax = r.w[0];
+#pragma unroll
+    for (int sp = 1; sp < NS; ++sp) mmax = fmaxf(mmax, r.w[sp]);
+    float den = 0.f;
+#pragma unroll
+    for (int sp = 0; sp < NS; ++sp) {
+        r.w[sp] = __builtin_amdgcn_exp2f(r.w[sp] - mmax);
+        den = fmaf(ls[sp], r.w[sp], den);
+    }
+    r.rden = 1.0f / den;                   // one correctly-rounded reciprocal per row, then multiplies
+    return r;
 }
 
+// one 4-channel piece from its NS loaded partials (and channel e of it alone, for callers that pin each value as it is made)
 template <int NS>
-__device__ __forceinline__ f32x4 merge_partials_finish(const MergeLoads<NS>& L) {
-    float mmax = L.mx[0];
+__device__ __forceinline__ float merge_apply(const f32x4 (&pv)[NS], const MergeWeights<NS>& mw, int e) {
+    float s = 0.f;
 #pragma unroll
-    for (int sp = 1; sp < NS; ++sp) mmax = fmaxf(mmax, L.mx[sp]);
-    float den = 0.f;
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int sp = 0; sp < NS; ++sp) {
-        const float w = __builtin_amdgcn_exp2f(L.mx[sp] - mmax);
-        den = fmaf(L.ls[sp], w, den);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) acc[e] = fmaf(L.pv[sp][e], w, acc[e]);
-    }
-    const float r = 1.0f / den;
+    for (int sp = 0; sp < NS; ++sp) s = fmaf(pv[sp][e], mw.w[sp], s);
+    return s * mw.rden;
+}
+template <int NS>
+__device__ __forceinline__ f32x4 merge_apply(const f32x4 (&pv)[NS], const MergeWeights<NS>& mw) {
     f32x4 v;
 #pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] = acc[e] * r;
+    for (int e = 0; e < 4; ++e) v[e] = merge_apply<NS>(pv, mw, e);
     return v;
 }
 

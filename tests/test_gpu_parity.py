@@ -655,11 +655,17 @@ def test_layer_h3_pipelined_kernel_is_bit_identical_to_the_generic_one(n, bs, ns
     assert torch.equal(fb2, fb_gen) and torch.equal(qs2, qs_gen) and torch.equal(kv2, kv_gen)
 
 
-@pytest.mark.parametrize("n,bs,nsplit", [(5000, 1, 6), (1000, 2, 8), (2053, 1, 5), (3001, 1, 7)])
+@pytest.mark.parametrize("n,bs,nsplit", [(5000, 1, 6), (1000, 2, 8), (2053, 1, 5), (3001, 1, 7)]
+                         + [(290, 1, k) for k in range(2, 9)] + [(290, 257, k) for k in range(2, 9)])
 def test_h3_layer_kernel_merges_up_to_eight_key_splits(n, bs, nsplit):
     """r03: layer_h3_kernel merges 5..8 key-split partials itself (the plans of 1-3 pairs of N = 5000 / 10000 per GPU: no
     attention_combine launch, no msg round trip).  Same arithmetic as the combine kernel: feeding the point-fragment partials
-    equals feeding the merged msg, bit for bit."""
+    equals feeding the merged msg, bit for bit.
+    N = 290 (10 tiles, the last with 2 valid rows, enough key tiles for 8 splits) reaches every split count of the shared
+    dispatcher (merge_partials.h) in both H3 kernels: one pair takes the four-wavefront kernel, 257 pairs (2570 tiles > 2560) the
+    one-wavefront-per-tile kernel.  The counts start at 2: sc_attention_split(..., merge=False) does not serve a single split
+    (the attention then writes msg itself and leaves no partials)."""
+    assert _lib.load().pdsc_layer_h3_uses_coop(bs, n) == (0 if bs == 257 else 1)      # the kernel each case is meant for
     gen = torch.Generator().manual_seed(800 + n)
     rnd = lambda *shape: torch.randn(*shape, generator=gen)  # noqa: E731
     m = bs * n
@@ -867,8 +873,11 @@ def test_layer_fused_frag_h3_small_and_large_magnitudes():
         assert e < 3e-6, (mag, e)
 
 
-@pytest.mark.parametrize("n,bs,nsplit", [(257, 1, 2), (1000, 2, 3), (5000, 2, 2)])
+@pytest.mark.parametrize("n,bs,nsplit", [(257, 1, 2), (1000, 2, 3), (5000, 2, 2), (290, 2, 3)])
 def test_layer_fused_frag_h3_merges_attention_partials(n, bs, nsplit):
+    """The generic wavefront-per-tile kernel (this output set: qkv_out) merges up to 4 key splits with the pieces of
+    merge_partials.h.  (290, 2, 3): a ragged last tile of 2 rows.  A single split cannot be fed here: sc_attention_split(...,
+    merge=False) does not serve nsplit = 1."""
     gen = torch.Generator().manual_seed(n + 2)
     rnd = lambda *shape: torch.randn(*shape, generator=gen)  # noqa: E731
     batch = synthetic.make_batch(bs, n, seed=6 + n)
