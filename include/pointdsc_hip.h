@@ -688,6 +688,54 @@ int pdsc_voxel_keys(const float* points, const int* n_per_cloud, double voxel_si
 int pdsc_voxel_means(const float* points, const long long* sorted_keys, const long long* perm, float* out, int* counts, int bs,
                      int N, void* stream);
 
+/* ---- FPFH descriptors ----------------------------------------------------------------------------
+ * replaces the open3d calls of misc/cal_fpfh.py:21-26 on an already down-sampled cloud (estimate_normals with
+ * KDTreeSearchParamHybrid(2 voxel, 30), compute_fpfh_feature with KDTreeSearchParamHybrid(5 voxel, 100)) and the normalisation of
+ * demo_registration.py:43, f / (|f|_2 + 1e-6).  fp64 arithmetic throughout; batched over bs clouds of up to N points:
+ * points [bs][N][3] fp32 (widened exactly), n_per_cloud [bs] int32 (DEVICE; NULL = N each; rows beyond a cloud's count are padding
+ * and never read).  Every entry only enqueues kernels on `stream`: no allocation, no host synchronisation, graph-capturable; a
+ * cloud's result does not depend on the batch it runs in.  Three named rules (open3d's own behaviour is an artefact there, or cannot
+ * be checked without it):
+ *   FLANN_RADIUS_RULE      a neighbour has fp64 d2 < float32(r * r), strict (as in pdsc_icp_refine);
+ *   COVARIANCE_ORDER_RULE  the nine cumulants of a normal are summed in ascending neighbour INDEX order, so that two points with
+ *                          the same neighbour set get bit-equal normals;
+ *   NORMAL_SIGN_RULE       a normal n of point p is kept when dot(n, viewpoint - p) >= 0 and negated otherwise (open3d 0.9 leaves
+ *                          the eigen-solver's arbitrary sign; orient_normals_towards_camera_location, default the origin).
+ *
+ * pdsc_hybrid_neighbours (KDTreeFlann::SearchHybrid): per point the at most max_nn (<= 128) nearest points of the same cloud under
+ *   FLANN_RADIUS_RULE, ascending by (d2, index); the point itself is included.  idx [bs][N][max_nn] int32 (entries beyond the count:
+ *   -1), d2 [bs][N][max_nn] double (optional; beyond the count: 0), count [bs][N] int32.  Padding rows have count 0; every row of a
+ *   cloud with a non-finite point has count -1, which the three entries below turn into NaN rows.  d2 = (dx dx + dy dy) + dz dz.
+ *   workspace: pdsc_hybrid_neighbours_workspace_bytes(bs, N) (the cell grid of icp_grid.h, built once per cloud per call).
+ * pdsc_estimate_normals (open3d 0.9 EstimateNormals): from such lists (count >= 3: cumulants = means of x, y, z, xx, xy, xz, yy,
+ *   yz, zz over the list under COVARIANCE_ORDER_RULE, C = E[p p^T] - E[p] E[p]^T, unit eigenvector of the smallest eigenvalue;
+ *   fewer than 3 neighbours: (0, 0, 1)), then NORMAL_SIGN_RULE.  viewpoint: 3 doubles on the HOST, read before the call returns
+ *   (NULL = the origin).  normals [bs][N][3] double; padding rows zero.
+ * pdsc_spfh (ComputeSPFHFeature): spfh [bs][N][33] double; for count > 1 the pair features of list entries 1 .. count-1
+ *   (ComputePairFeatures; a pair at distance 0 is binned as (0, 0, 0)) are counted into 3 x 11 bins and scaled by 100 / (count - 1).
+ * pdsc_fpfh_from_spfh (ComputeFPFHFeature): f[j] = sum over list entries k >= 1 with d2_k != 0 of spfh[idx_k][j] / d2_k (list order),
+ *   then f[j] = f[j] * (100 / sum of its block of 11, 0 when that sum is 0) + spfh[i][j].  fpfh_f64 [bs][N][33] double (optional),
+ *   desc_f32 [bs][N][33] fp32 = f / (|f|_2 + 1e-6) (optional; one of the two is required).  Padding rows zero.
+ * pdsc_fpfh chains the four: lists at normal_radius / normal_max_nn -> normals -> lists at feature_radius / feature_max_nn -> SPFH ->
+ *   FPFH.  normals_out [bs][N][3] double is optional.  workspace: pdsc_fpfh_workspace_bytes(bs, N, normal_max_nn, feature_max_nn).
+ * Bad arguments (null pointer, radius <= 0 or not finite, max_nn outside 1 .. 128, bs outside 1 .. 65535, N outside 1 .. 2^24,
+ * workspace too small) return PDSC_ERR_ARG with nothing enqueued. */
+#define PDSC_FPFH_DIM 33
+#define PDSC_FPFH_MAX_NN 128
+size_t pdsc_hybrid_neighbours_workspace_bytes(int bs, int N);
+int pdsc_hybrid_neighbours(const float* points, const int* n_per_cloud, double radius, int max_nn, int* idx, double* d2, int* count,
+                           void* workspace, size_t workspace_bytes, int bs, int N, void* stream);
+int pdsc_estimate_normals(const float* points, const int* n_per_cloud, const int* idx, const int* count, int max_nn,
+                          const double* viewpoint, double* normals, int bs, int N, void* stream);
+int pdsc_spfh(const float* points, const int* n_per_cloud, const double* normals, const int* idx, const int* count, int max_nn,
+              double* spfh, int bs, int N, void* stream);
+int pdsc_fpfh_from_spfh(const double* spfh, const int* n_per_cloud, const int* idx, const double* d2, const int* count, int max_nn,
+                        double* fpfh_f64, float* desc_f32, int bs, int N, void* stream);
+size_t pdsc_fpfh_workspace_bytes(int bs, int N, int normal_max_nn, int feature_max_nn);
+int pdsc_fpfh(const float* points, const int* n_per_cloud, double normal_radius, int normal_max_nn, double feature_radius,
+              int feature_max_nn, const double* viewpoint, double* fpfh_f64, float* desc_f32, double* normals_out, void* workspace,
+              size_t workspace_bytes, int bs, int N, void* stream);
+
 /* ---- range probe for layer_gemm = PDSC_LAYER_GEMM_H3 ----------------------------------------------------------------
  * The H3 arithmetic carries every operand of the fc_message / PointCN GEMMs as fp16 hi + lo, so every activation of the
  * 12-layer chain -- hidden ones included -- must stay below 65504.  This entry runs the ENCODER (compat, layer0, 12 x

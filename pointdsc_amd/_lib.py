@@ -131,6 +131,13 @@ SIGNATURES = {
     "pdsc_information_matrix": (_i, [_vp, _vp, _vp, _vp, _vp, C.c_double, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _vp]),
     "pdsc_voxel_keys": (_i, [_vp, _vp, C.c_double, _vp, _i, _i, _vp]),
     "pdsc_voxel_means": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
+    "pdsc_hybrid_neighbours_workspace_bytes": (_sz, [_i, _i]),
+    "pdsc_hybrid_neighbours": (_i, [_vp, _vp, C.c_double, _i, _vp, _vp, _vp, _vp, _sz, _i, _i, _vp]),
+    "pdsc_estimate_normals": (_i, [_vp, _vp, _vp, _vp, _i, C.POINTER(C.c_double), _vp, _i, _i, _vp]),
+    "pdsc_spfh": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _vp]),
+    "pdsc_fpfh_from_spfh": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _vp]),
+    "pdsc_fpfh_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "pdsc_fpfh": (_i, [_vp, _vp, C.c_double, _i, C.c_double, _i, C.POINTER(C.c_double), _vp, _vp, _vp, _vp, _sz, _i, _i, _vp]),
     "pdsc_encoder_range_probe": (_i, [_cfgp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
     "pdsc_forward_validation": (_i, [_cfgp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _ll, _vp, _sz, _vp]),
     "pdsc_feature_compat": (_i, [_vp, _vp, _vp, _ll, _i, _i, _vp]),

@@ -13,11 +13,12 @@ this module is host plumbing: PLY reading (binary little-endian float xyz, SURVE
 down-sampling in numpy, the pair loop, timers (``utils/timer.py`` semantics: wall clock, here with a device
 synchronisation so that model time is the GPU's).
 
-Descriptors: FPFH / FCGF extraction is upstream of the path and needs open3d / MinkowskiEngine (absent).  The
-harness takes descriptors as input; ``standin_descriptors`` provides seeded unit vectors that agree for points that
-coincide under the ground-truth motion (a stand-in with a controllable inlier ratio, NOT a feature extractor), so
-that the whole loop runs and produces meaningful rows on the demo clouds.  With real descriptors + the released
-weights the same loop is the Registration-Recall driver.
+Descriptors: FCGF extraction is upstream of the path and needs MinkowskiEngine and a checkpoint (absent).  FPFH runs on the
+device (``features.fpfh_descriptors``, f-7: the recipe of misc/cal_fpfh.py:21-26): ``demo_pairs`` / ``demo_views`` compute it with
+``descriptor="fpfh"``, so that cloud -> descriptors -> matching -> forward -> ICP runs on real geometry.  Their default,
+``standin_descriptors``, provides seeded unit vectors that agree for points that coincide under the ground-truth motion (a
+stand-in with a controllable inlier ratio, NOT a feature extractor).  With real descriptors + the released weights the same loop
+is the Registration-Recall driver.
 """
 from __future__ import annotations
 
@@ -30,6 +31,7 @@ import torch
 
 from . import ops
 from .correspondences import build_correspondences
+from .features import fpfh_descriptors
 from .icp import icp_refine
 from .multiway import local_refinement, loop_closure_edge
 
@@ -150,7 +152,7 @@ def eval_scene(model, pairs: Iterable[Dict[str, np.ndarray]], scene_ind: int = 0
     inside the model time as in the reference; the stats rows then use the refined poses."""
     rows: List[np.ndarray] = []
     dev = torch.device(device)
-    g = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
+    g = lambda a: a.to(dev) if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
 
     def flush(group):
         if not group:
@@ -210,12 +212,30 @@ def summarize(stats: np.ndarray) -> Dict[str, float]:
     }
 
 
+def _check_descriptor(descriptor: str) -> bool:
+    if descriptor not in ("standin", "fpfh"):
+        raise ValueError(f"descriptor must be 'standin' or 'fpfh', got {descriptor!r}")
+    return descriptor == "fpfh"
+
+
+def device_fpfh(points: np.ndarray, voxel: float, device: str = "cuda:0") -> torch.Tensor:
+    """FPFH descriptors [n,33] fp32 of a cloud down-sampled at `voxel`, computed and left on the device (f-7)."""
+    pts = torch.from_numpy(np.ascontiguousarray(points, dtype=np.float32)).to(torch.device(device))
+    return fpfh_descriptors(pts[None], voxel)[0]
+
+
 def demo_pairs(cloud: np.ndarray, num_pairs: int, dim: int = 33, cell: float = 0.05, corrupt: float = 0.6,
-               seed: int = 0) -> Iterable[Dict[str, np.ndarray]]:
-    """Pairs for the loop from ONE down-sampled cloud: view i = `second_view(cloud, seed + i)`, stand-in descriptors."""
+               seed: int = 0, descriptor: str = "standin", voxel: float = 0.05, device: str = "cuda:0") -> Iterable[Dict[str, np.ndarray]]:
+    """Pairs for the loop from ONE down-sampled cloud: view i = `second_view(cloud, seed + i)`; stand-in descriptors, or with
+    descriptor="fpfh" the device's FPFH of each view (cloud down-sampled at `voxel`; descriptors stay on `device`)."""
+    fpfh = _check_descriptor(descriptor)
+    src_desc = device_fpfh(cloud, voxel, device) if fpfh else None
     for i in range(num_pairs):
         rs = np.random.RandomState(10_000 + seed + i)
         tgt, T, tgt_in_src = second_view(cloud, seed + i)
+        if fpfh:
+            yield {"src_pts": cloud, "tgt_pts": tgt, "gt_trans": T, "src_desc": src_desc, "tgt_desc": device_fpfh(tgt, voxel, device)}
+            continue
         yield {"src_pts": cloud, "tgt_pts": tgt, "gt_trans": T,
                "src_desc": standin_descriptors(cloud, dim, cell, seed + i, corrupt, rs),
                "tgt_desc": standin_descriptors(tgt_in_src, dim, cell, seed + i, corrupt * 0.5, rs)}
@@ -225,17 +245,21 @@ def demo_pairs(cloud: np.ndarray, num_pairs: int, dim: int = 33, cell: float = 0
 # the multiway driver's pair loop (multiway/test_multi_ate.py:98-157)
 # ---------------------------------------------------------------------------------------------------------------
 def demo_views(cloud: np.ndarray, num_views: int, dim: int = 33, cell: float = 0.05, corrupt: float = 0.4, seed: int = 0,
-               odometry_deg: float = 2.0, odometry_cm: float = 5.0) -> List[Dict[str, np.ndarray]]:
+               odometry_deg: float = 2.0, odometry_cm: float = 5.0, descriptor: str = "standin", voxel: float = 0.05,
+               device: str = "cuda:0") -> List[Dict[str, np.ndarray]]:
     """Fragments for `multiway_edges` from ONE down-sampled cloud, built like `demo_pairs`: view i = `second_view(cloud, seed + i)`
-    in its own frame, with stand-in descriptors that agree between the views for points of the same cell of the cloud's frame.
+    in its own frame, with stand-in descriptors that agree between the views for points of the same cell of the cloud's frame
+    (descriptor="fpfh": the device's FPFH of each view, as in `demo_pairs`).
     `pose` [4,4]: p_view = pose p_cloud.  `odometry` [4,4] (all but the last view): the motion onto the next view disturbed by
     `odometry_deg` / `odometry_cm` -- the stand-in for the fragment odometry the driver starts its local refinement from
     (multiway/test_multi_ate.py:119-121)."""
+    fpfh = _check_descriptor(descriptor)
     views = []
     for i in range(num_views):
         rs = np.random.RandomState(20_000 + seed + i)
         pts, T, in_cloud = second_view(cloud, seed + i)
-        views.append({"pts": pts, "pose": T.astype(np.float64), "desc": standin_descriptors(in_cloud, dim, cell, seed, corrupt, rs)})
+        desc = device_fpfh(pts, voxel, device) if fpfh else standin_descriptors(in_cloud, dim, cell, seed, corrupt, rs)
+        views.append({"pts": pts, "pose": T.astype(np.float64), "desc": desc})
     for i in range(num_views - 1):
         rs = np.random.RandomState(30_000 + seed + i)
         axis = rs.standard_normal(3)
@@ -259,7 +283,7 @@ def multiway_edges(model, views: List[Dict[str, np.ndarray]], use_mutual: bool =
     Everything up to the gate stays on the device; the gates of all pairs are read back once, at the end.
     Returns the edges as the driver would append them: tuples (s, t, T [4,4] float64 numpy, info [6,6] float64 numpy, uncertain)."""
     dev = torch.device(device)
-    g = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)  # noqa: E731
+    g = lambda a: a.to(dev).float() if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)  # noqa: E731
     pts = [g(v["pts"]) for v in views]
     desc = [g(v["desc"]) for v in views]
     found = []

@@ -1,12 +1,16 @@
 #!/usr/bin/env python3
 """The reference's evaluation loop / demo around pointdsc_amd.PointDSC (pointdsc_amd/harness.py).
 
-    python tools/eval_harness.py [--pcd1 a.ply --pcd2 b.ply] [--num-pairs 8] [--snapshot model_best.pkl] [--kitti] [--use-icp]
-    python tools/eval_harness.py --multiway [--num-views 5]
+    python tools/eval_harness.py [--pcd1 a.ply] [--num-pairs 8] [--descriptor {standin,fpfh}] [--snapshot model_best.pkl] [--use-icp]
+    python tools/eval_harness.py --pcd1 a.ply --pcd2 b.ply --descriptor fpfh [--use-icp]
+    python tools/eval_harness.py --multiway [--num-views 5] [--descriptor {standin,fpfh}]
 
 Without --pcd1 the down-sampled demo cloud of tests/golden/demo_clouds_vox005.npz (reference demo_data/cloud_bin_0.ply at
 0.05 m) is used.  Every pair = the cloud against a seeded second view of it (partial overlap, noise, random rigid motion),
-stand-in descriptors with a known outlier share, GPU correspondence construction, forward, device-side stats row.
+stand-in descriptors with a known outlier share (--descriptor standin, the default) or the device's FPFH of each view
+(--descriptor fpfh: misc/cal_fpfh.py:21-26 on the GPU, pointdsc_amd.features), GPU correspondence construction, forward,
+device-side stats row.  --pcd2 registers the real second cloud instead (the demo's own pair, demo_registration.py:101-117, always
+with FPFH): there is no ground truth, so the pose and the inlier count are printed only.
 --multiway runs the multiway driver's pairwise loop instead (multiway/test_multi_ate.py:98-157, harness.multiway_edges): every pair
 of --num-views seeded views of the cloud; adjacent views through multi-scale ICP (certain edges), the others through the forward,
 the device-side information matrix and the overlap gate (uncertain edges); prints the edges a pose graph would receive.
@@ -27,7 +31,7 @@ from pointdsc_amd import PointDSC, harness, workloads  # noqa: E402
 
 
 def multiway(model, cloud, a):
-    views = harness.demo_views(cloud, a.num_views, corrupt=min(a.outlier_share, 0.4))
+    views = harness.demo_views(cloud, a.num_views, corrupt=min(a.outlier_share, 0.4), descriptor=a.descriptor, voxel=a.voxel)
     edges = harness.multiway_edges(model, views, use_mutual=a.mutual)
     if a.json:
         print(json.dumps({"edges": [{"source": s, "target": t, "transformation": T.tolist(), "information": info.tolist(),
@@ -43,9 +47,37 @@ def multiway(model, cloud, a):
               f"TE {np.linalg.norm(T[:3, 3] - gt[:3, 3]) * 100:7.3f} cm")
 
 
+def real_pair(model, cloud, a):
+    """demo_registration.py:101-117 on two real clouds: FPFH -> matching -> forward (-> ICP); no ground truth."""
+    from pointdsc_amd import icp_refine
+    from pointdsc_amd.correspondences import build_correspondences
+    cloud2 = harness.voxel_down_sample(harness.read_ply_xyz(a.pcd2), a.voxel)
+    dev = torch.device("cuda:0")
+    with torch.no_grad():
+        pts = [torch.from_numpy(c).to(dev) for c in (cloud, cloud2)]
+        desc = [harness.device_fpfh(c, a.voxel) for c in (cloud, cloud2)]
+        c = build_correspondences(desc[0], desc[1], pts[0], pts[1], use_mutual=a.mutual)
+        res = model({"corr_pos": c["corr_pos"], "src_keypts": c["src_keypts"], "tgt_keypts": c["tgt_keypts"], "testing": True})
+        trans = res["final_trans"]
+        if a.use_icp:
+            trans = icp_refine(c["src_keypts"], c["tgt_keypts"], trans, a.icp_distance)
+        T, inliers = trans[0].cpu().numpy(), int((res["final_labels"][0] > 0).sum())
+    if a.json:
+        print(json.dumps({"points": [len(cloud), len(cloud2)], "correspondences": int(c["corr_pos"].shape[1]), "inliers": inliers,
+                          "transformation": T.tolist()}))
+        return
+    print(f"{len(cloud)} / {len(cloud2)} points after {a.voxel} m voxel down-sampling; {c['corr_pos'].shape[1]} correspondences, "
+          f"{inliers} predicted inliers" + (" (ICP post-step)" if a.use_icp else ""))
+    print(np.array2string(T, precision=6, suppress_small=True))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--pcd1", default=None, help="PLY file (binary LE / ascii, float xyz); default: the demo fixture")
+    ap.add_argument("--pcd2", default=None, help="PLY file of the real second cloud: register --pcd1 onto it with FPFH descriptors "
+                    "(no ground truth: pose and inlier count only)")
+    ap.add_argument("--descriptor", choices=("standin", "fpfh"), default="standin",
+                    help="stand-in descriptors with a known outlier share, or FPFH on the device (misc/cal_fpfh.py:21-26)")
     ap.add_argument("--voxel", type=float, default=0.05, help="config.downsample of the 3DMatch snapshot")
     ap.add_argument("--num-pairs", type=int, default=8)
     ap.add_argument("--outlier-share", type=float, default=0.6, help="share of stand-in descriptors replaced by noise")
@@ -69,9 +101,14 @@ def main():
     else:
         model.load_state_dict(workloads.state_dict("n5000_b32", model.state_dict()))
     model = model.eval().cuda()
+    if a.pcd2:
+        if not a.pcd1:
+            ap.error("--pcd2 goes with --pcd1")
+        return real_pair(model, cloud, a)
     if a.multiway:
         return multiway(model, cloud, a)
-    stats = harness.eval_scene(model, harness.demo_pairs(cloud, a.num_pairs, corrupt=a.outlier_share), scene_ind=0,
+    pairs = harness.demo_pairs(cloud, a.num_pairs, corrupt=a.outlier_share, descriptor=a.descriptor, voxel=a.voxel)
+    stats = harness.eval_scene(model, pairs, scene_ind=0,
                                inlier_threshold=kw["inlier_threshold"], use_mutual=a.mutual, batch_size=a.batch_size,
                                use_icp=a.use_icp, icp_distance=a.icp_distance)
     summ = harness.summarize(stats)

@@ -6,7 +6,11 @@
 (.vgpr_count / .agpr_count / .sgpr_count / .private_segment_fixed_size = scratch bytes per lane / .group_segment_fixed_size = static
 LDS.)  What DESIGN.md's register and spill figures are read from, e.g. those of section 8 f-5 / f-6:
 
-    python tools/kernel_resources.py icp_kernel information_kernel voxel_keys_kernel voxel_means_kernel"""
+    python tools/kernel_resources.py icp_kernel information_kernel voxel_keys_kernel voxel_means_kernel
+
+and of section 8 f-7 (the FPFH path):
+
+    python tools/kernel_resources.py nb_grid_kernel nb_search_kernel normals_kernel spfh_kernel fpfh_kernel"""
 import re
 import subprocess
 import sys
