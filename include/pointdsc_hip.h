@@ -736,6 +736,67 @@ int pdsc_fpfh(const float* points, const int* n_per_cloud, double normal_radius,
               int feature_max_nn, const double* viewpoint, double* fpfh_f64, float* desc_f32, double* normals_out, void* workspace,
               size_t workspace_bytes, int bs, int N, void* stream);
 
+/* ---- pose-graph optimisation ---------------------------------------------------------------------
+ * pdsc_global_optimization replaces o3d.registration.global_optimization(pose_graph, GlobalOptimizationLevenbergMarquardt(),
+ * GlobalOptimizationConvergenceCriteria(), option) as multiway/test_multi_ate.py:166-174 and :217-224 call it, for a ragged batch
+ * of graphs, fp64 throughout.  open3d cannot be consulted here: this text (open3d 0.9's algorithm restated) is the contract.
+ *   graph: node poses [4][4] (fragment -> world); edges (s, t, X [4][4] source -> target, Lambda [6][6], uncertain).
+ *   residual of an edge: A = X^-1 pose_t^-1, e = lin6(A pose_s), lin6(M) = ((M21 - M12) / 2, (M02 - M20) / 2, (M10 - M01) / 2,
+ *     M03, M13, M23);  column k of Js = lin6(A G_k pose_s), G_k the generators (alpha: G12 = -1, G21 = 1; beta: G02 = 1,
+ *     G20 = -1; gamma: G01 = -1, G10 = 1; a, b, c: G03, G13, G23 = 1);  Jt = -Js.
+ *   line process: w = preference_loop_closure * max_correspondence_distance^2 * mean over the live edges of Lambda[5][5] (0 without
+ *     live edges); confidence of an uncertain edge = (w / (w + e^T Lambda e))^2, 1 before the first update; its weight l in the
+ *     system is the confidence, a certain edge's is 1.
+ *   objective: sum over uncertain edges of l e^T Lambda e + w (sqrt(l) - 1)^2, plus sum over certain edges of e^T Lambda e.
+ *   system: per live edge H[s][s] += l Js^T Lambda Js, H[s][t] += l Js^T Lambda Jt, H[t][s] += l Jt^T Lambda Js, H[t][t] += l Jt^T
+ *     Lambda Jt, b[s] -= l Js^T Lambda e, b[t] -= l Jt^T Lambda e; every entry is summed over its incident edges in ascending
+ *     edge index.
+ *   one pass: w; residuals; cur = objective; update the confidences; H, b; lambda = 1e-5 max diag H; nu = 2; stop = max b < 1e-6;
+ *     x = mat2vec of every pose; for (iter = 0; !stop; iter++) { lm = 0; do { delta = solve((H + lambda I) delta = b);
+ *     stop |= |delta| < 1e-6 (|x| + 1e-6); if (!stop) { pose'_i = vec2mat(delta_i) pose_i; new = objective of pose' (same
+ *     confidences); rho = (cur - new) / (delta . (lambda delta + b) + 1e-3); if (rho > 0) { stop |= cur - new < 1e-6 cur; if
+ *     (stop) break; lambda *= max(1/3, min(1 - (2 rho - 1)^3, 2/3)); nu = 2; accept pose', cur = new, x; update the confidences;
+ *     rebuild H, b; stop |= max b < 1e-6; if (stop) break; } else { lambda *= nu; nu *= 2; } } lm++; stop |= lm >= 20; } while
+ *     (!(rho > 0 || stop)); stop |= iter >= 100 || cur < 1e-6; }  finally every pose is multiplied from the left by
+ *     pose_ref(at the start of the pass) pose_ref(now)^-1 (open3d does not fix the reference node in the solve).
+ *     vec2mat(v): R = Rz(v2) Ry(v1) Rx(v0), t = v[3:6];  mat2vec(T) (used for |x| only): sy = hypot(R00, R10); sy not < 1e-6:
+ *     (atan2(R21, R22), atan2(-R20, sy), atan2(R10, R00)), otherwise (atan2(-R12, R11), atan2(-R20, sy), 0).
+ *   global optimisation: pass 1 on the live edges; an edge stays live when it is certain or its confidence > edge_prune_threshold;
+ *     pass 2 on the survivors from pass 1's poses and confidences (w over the survivors); prune again.  Pruning is a mask.
+ * Named rules:
+ *   INVERSE_RULE  the inverse of a pose is [R^-1, -R^-1 t; 0 0 0 1] with R^-1 = adj(R) / det(R), not R^T (the forward's fp32
+ *                 rotations are orthogonal to about 1e-7 only, and open3d takes the general inverse);
+ *   SOLVE_RULE    open3d solves with Eigen's ldlt(); here a blocked Cholesky with fused multiply-adds (H + lambda I is positive
+ *                 definite; any backward-stable factorisation agrees within the tolerance of tests/test_posegraph.py).
+ * Validity (this library's rule, not open3d's ValidatePoseGraph): a graph with a non-finite entry, an index outside [0, F) or
+ * s == t in a live edge, a non-finite node pose, reference_node >= F, or more nodes / edges than max_nodes / max_edges returns
+ * NaN poses, its input mask, confidences of 1 and status 1; nothing else in the batch is affected.  A graph without live edges
+ * returns its nodes unchanged with status 0.
+ * nodes [sum F][16], source / target [sum E] int32 (node index inside the edge's graph), X [sum E][16], info [sum E][36],
+ * uncertain [sum E] u8, live_in [sum E] u8 (NULL = all live), node_offset / edge_offset [num_graphs + 1] int32 (DEVICE; graph g owns
+ * nodes node_offset[g] .. node_offset[g + 1]), total_nodes / total_edges = the arrays' lengths (offsets beyond them: status 1,
+ * nothing else of that graph is written).  Outputs: nodes_out [sum F][16] (must not alias nodes), confidence [sum E] (1 for an
+ * edge that never was live or is certain), live_out [sum E] u8, record [num_graphs][PDSC_POSEGRAPH_RECORD] double: [0] status,
+ * [1..4] pass 1's outer iterations, solves, final objective and w, [5..8] pass 2's, [9..11] live edges at the start, after the first
+ * pruning, at the end; ticks [num_graphs][3] int64 (optional, NULL = not wanted; tools/posegraph_bench.py): the workgroup's time in
+ * residuals + assembly, in the solves and in the whole graph, in ticks of the constant 100 MHz device clock.  One launch of one persistent workgroup per graph; graphs exit independently; no allocation, no host
+ * synchronisation (graph-capturable); a graph's bits do not depend on its batch.  workspace: pdsc_posegraph_workspace_bytes.
+ * pdsc_posegraph_nodes: the driver's node chain (:129-130) per graph: node 0 = I, odometry = I; per live certain edge in order
+ *   odometry = X odometry, the next node = odometry^-1 (INVERSE_RULE); nodes the chain does not reach are NaN; a graph whose offsets
+ *   leave the arrays is not written at all.
+ * Bad arguments (null pointer, counts out of range, NaN option, workspace too small) return PDSC_ERR_ARG with nothing enqueued. */
+#define PDSC_POSEGRAPH_MAX_NODES 128
+#define PDSC_POSEGRAPH_RECORD 12
+size_t pdsc_posegraph_workspace_bytes(int num_graphs, int max_nodes, int max_edges);
+int pdsc_posegraph_nodes(const double* X, const unsigned char* uncertain, const unsigned char* live, const int* node_offset,
+                         const int* edge_offset, double* nodes, int num_graphs, int total_nodes, int total_edges, void* stream);
+int pdsc_global_optimization(const double* nodes, const int* source, const int* target, const double* X, const double* info,
+                             const unsigned char* uncertain, const unsigned char* live_in, const int* node_offset,
+                             const int* edge_offset, double max_correspondence_distance, double edge_prune_threshold,
+                             double preference_loop_closure, int reference_node, double* nodes_out, double* confidence,
+                             unsigned char* live_out, double* record, long long* ticks, void* workspace, size_t workspace_bytes,
+                             int num_graphs, int max_nodes, int max_edges, int total_nodes, int total_edges, void* stream);
+
 /* ---- range probe for layer_gemm = PDSC_LAYER_GEMM_H3 ----------------------------------------------------------------
  * The H3 arithmetic carries every operand of the fc_message / PointCN GEMMs as fp16 hi + lo, so every activation of the
  * 12-layer chain -- hidden ones included -- must stay below 65504.  This entry runs the ENCODER (compat, layer0, 12 x

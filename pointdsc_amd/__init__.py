@@ -8,16 +8,17 @@ Only what the path needs lives here:
   ops.py       stage-level tensor wrappers (``rigid_transform_3d``, ``knn`` ...) over the C-ABI
   icp.py       the evaluation's optional ICP post-step (``icp_refine``, ``registration_icp``) on the device
   features.py  FPFH descriptors of a down-sampled cloud (neighbour lists, normals, SPFH, FPFH) on the device
-  multiway.py  the multiway driver's edge step (information matrix + overlap gate, voxel down-sampling, multi-scale ICP) on the device
+  multiway.py  the multiway driver's edge step (information matrix + overlap gate, voxel down-sampling, multi-scale ICP) and its
+               pose-graph optimisation (node chain, LM with line process, edge pruning) on the device
   sharding.py  one-process-per-GPU sharding of pair batches + the single RCCL pose gather
   synthetic.py seeded synthetic correspondence sets / weights (tests + bench)
 """
 from .features import compute_fpfh_feature, estimate_normals, fpfh_descriptors, hybrid_neighbours  # noqa: F401
 from .icp import icp_refine, registration_icp  # noqa: F401
 from .model import PointDSC  # noqa: F401
-from .multiway import (align, information_matrix, local_refinement, loop_closure_edge, multi_scale_icp,  # noqa: F401
-                       voxel_down_sample)
+from .multiway import (align, global_optimization, information_matrix, local_refinement, loop_closure_edge,  # noqa: F401
+                       multi_scale_icp, pose_graph_nodes, voxel_down_sample)
 
 __all__ = ["PointDSC", "icp_refine", "registration_icp", "information_matrix", "voxel_down_sample", "loop_closure_edge",
            "multi_scale_icp", "local_refinement", "align", "hybrid_neighbours", "estimate_normals", "compute_fpfh_feature",
-           "fpfh_descriptors"]
+           "fpfh_descriptors", "pose_graph_nodes", "global_optimization"]

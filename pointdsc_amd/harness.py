@@ -8,7 +8,8 @@ Replicates, without open3d / easydict (absent here):
   * ``demo_registration.py:37-44,101-117``  cloud -> voxel down-sampling -> descriptors -> nearest-neighbour matching
     -> ``corr_pos`` -> ``model(data)``.
 The arithmetic on the path runs in libpointdsc_hip.so (correspondence construction f-2, forward a-*, stats row f-4, the
-optional ICP post-step f-5, the multiway driver's edge step f-6: ``multiway_edges``);
+optional ICP post-step f-5, the multiway driver's edge step f-6: ``multiway_edges``, its pose-graph optimisation and ATE f-8:
+``multiway_trajectory``);
 this module is host plumbing: PLY reading (binary little-endian float xyz), open3d-style voxel
 down-sampling in numpy, the pair loop, timers (``utils/timer.py`` semantics: wall clock, here with a device
 synchronisation so that model time is the GPU's).
@@ -283,6 +284,15 @@ def multiway_edges(model, views: List[Dict[str, np.ndarray]], use_mutual: bool =
     Everything up to the gate stays on the device; the gates of all pairs are read back once, at the end.
     Returns the edges as the driver would append them: tuples (s, t, T [4,4] float64 numpy, info [6,6] float64 numpy, uncertain)."""
     dev = torch.device(device)
+    found, _ = _pairwise_registration(model, views, use_mutual, dev)
+    keep = torch.stack([f[4] if f[4] is not None else torch.ones((), dtype=torch.bool, device=dev) for f in found]).cpu().numpy()
+    return [(s, t, T.double().cpu().numpy(), info.cpu().numpy(), gate is not None)
+            for (s, t, T, info, gate), k in zip(found, keep) if k]
+
+
+def _pairwise_registration(model, views, use_mutual: bool, dev):
+    """The pair loop of `multiway_edges`, everything left on the device: -> ([(s, t, T [4,4] fp32, info [6,6] fp64, gate or None)] in
+    the driver's order -- gate: the overlap gate's 0-d bool tensor of a loop closure, None for an odometry edge --, the views' points)."""
     g = lambda a: a.to(dev).float() if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)  # noqa: E731
     pts = [g(v["pts"]) for v in views]
     desc = [g(v["desc"]) for v in views]
@@ -298,6 +308,50 @@ def multiway_edges(model, views: List[Dict[str, np.ndarray]], use_mutual: bool =
                     res = model({"corr_pos": c["corr_pos"], "src_keypts": c["src_keypts"], "tgt_keypts": c["tgt_keypts"], "testing": True})
                     edge = loop_closure_edge(c["src_keypts"], c["tgt_keypts"], res["final_trans"])
                     found.append((s, t, res["final_trans"][0], edge["information"][0], edge["keep"][0]))
-    keep = torch.stack([f[4] if f[4] is not None else torch.ones((), dtype=torch.bool, device=dev) for f in found]).cpu().numpy()
-    return [(s, t, T.double().cpu().numpy(), info.cpu().numpy(), gate is not None)
-            for (s, t, T, info, gate), k in zip(found, keep) if k]
+    return found, pts
+
+
+def multiway_trajectory(model, views: List[Dict[str, np.ndarray]], use_icp: bool = False, use_mutual: bool = False,
+                        device: str = "cuda:0", return_graph: bool = False) -> Dict[str, object]:
+    """The driver's `eval_redwood_scene` plus its ATE (multiway/test_multi_ate.py:86-227, :262-270) over `views` (as `multiway_edges`
+    takes them; `pose` [4,4] is the ground truth: p_view = pose p_scene):
+      1. the edges of `multiway_edges`, with the overlap gates kept on the device and handed to the optimiser as its edge mask;
+      2. the node chain over the odometry edges (:129-130);
+      3. `global_optimization` (:166-174);
+      4. use_icp (:188-224): `multi_scale_icp` of every edge from its transformation on the full clouds (the pruned ones too: which
+         edges survived is known on the device only; they stay masked out), the node chain again, a second `global_optimization`;
+      5. `align` of the node origins onto the views' true origins and sqrt(mean(err^2)).
+    Nothing is read on the host before the final ATE.  Returns ate_cm, errors_cm [F] (device), nodes_before / nodes_after,
+    edges_before / edges_after (as the driver prints them), nodes [F,4,4], keep [E], confidence [E], record [12] (device tensors; with
+    use_icp those of the second optimisation, plus first_record); return_graph adds graph = the inputs of the last optimisation
+    (nodes, edges, edge_mask)."""
+    from .multiway import align, global_optimization, multi_scale_icp, pose_graph_nodes
+    dev = torch.device(device)
+    F = len(views)
+    found, pts = _pairwise_registration(model, views, use_mutual, dev)
+    with torch.no_grad():
+        edges = {"source": torch.tensor([f[0] for f in found], dtype=torch.int32).to(dev),
+                 "target": torch.tensor([f[1] for f in found], dtype=torch.int32).to(dev),
+                 "transformation": torch.stack([f[2] for f in found]), "information": torch.stack([f[3] for f in found]),
+                 "uncertain": torch.tensor([f[4] is not None for f in found]).to(dev)}
+        mask = torch.stack([f[4] if f[4] is not None else torch.ones((), dtype=torch.bool, device=dev) for f in found])
+        nodes = pose_graph_nodes(edges, F, edge_mask=mask)
+        res = global_optimization(nodes, edges, edge_mask=mask)
+        out = {}
+        if use_icp:
+            out["first_record"] = res["record"]
+            refined = [multi_scale_icp(pts[s][None], pts[t][None], trans=T[None]) for s, t, T, _, _ in found]
+            edges = dict(edges, transformation=torch.cat([r["transformation_f64"] for r in refined]),
+                         information=torch.cat([r["information"] for r in refined]))
+            mask = res["keep"]
+            nodes = pose_graph_nodes(edges, F, edge_mask=mask)
+            res = global_optimization(nodes, edges, edge_mask=mask)
+        truth = np.stack([np.linalg.inv(np.asarray(v["pose"], dtype=np.float64))[:3, 3] for v in views], axis=1)
+        _, err = align(res["nodes"][:, :3, 3].T.contiguous(), torch.from_numpy(truth).to(dev))
+        ate = torch.sqrt((err.double() ** 2).mean())
+        record = res["record"].cpu().numpy()                   # the one read-back: record and ATE
+    out.update(ate_cm=float(ate), errors_cm=err, nodes_before=F, nodes_after=F, edges_before=int(record[9]), edges_after=int(record[11]),
+               nodes=res["nodes"], keep=res["keep"], confidence=res["confidence"], record=res["record"])
+    if return_graph:
+        out["graph"] = {"nodes": nodes, "edges": edges, "edge_mask": mask}
+    return out

@@ -4,6 +4,7 @@
     python tools/eval_harness.py [--pcd1 a.ply] [--num-pairs 8] [--descriptor {standin,fpfh}] [--snapshot model_best.pkl] [--use-icp]
     python tools/eval_harness.py --pcd1 a.ply --pcd2 b.ply --descriptor fpfh [--use-icp]
     python tools/eval_harness.py --multiway [--num-views 5] [--descriptor {standin,fpfh}]
+    python tools/eval_harness.py --multiway --posegraph [--use-icp] [--num-views 5]
 
 Without --pcd1 the down-sampled demo cloud of tests/golden/demo_clouds_vox005.npz (reference demo_data/cloud_bin_0.ply at
 0.05 m) is used.  Every pair = the cloud against a seeded second view of it (partial overlap, noise, random rigid motion),
@@ -14,6 +15,9 @@ with FPFH): there is no ground truth, so the pose and the inlier count are print
 --multiway runs the multiway driver's pairwise loop instead (multiway/test_multi_ate.py:98-157, harness.multiway_edges): every pair
 of --num-views seeded views of the cloud; adjacent views through multi-scale ICP (certain edges), the others through the forward,
 the device-side information matrix and the overlap gate (uncertain edges); prints the edges a pose graph would receive.
+--multiway --posegraph goes on as the driver does (:159-227, harness.multiway_trajectory): node chain, pose-graph optimisation on the
+device (with --use-icp: multi-scale ICP of every edge and a second optimisation), and the driver's lines -- "Before optimization ...
+nodes ... edges", "After optimization ...", "Mean Absolute Trajectory Error: ... cm" against the views' true poses.
 Registration Recall on 3DMatch-FCGF itself needs the released weights and the dataset (both absent here): pass
 --snapshot / real descriptors when they exist; the loop is the same.
 """
@@ -32,6 +36,8 @@ from pointdsc_amd import PointDSC, harness, workloads  # noqa: E402
 
 def multiway(model, cloud, a):
     views = harness.demo_views(cloud, a.num_views, corrupt=min(a.outlier_share, 0.4), descriptor=a.descriptor, voxel=a.voxel)
+    if a.posegraph:
+        return posegraph(model, views, a)
     edges = harness.multiway_edges(model, views, use_mutual=a.mutual)
     if a.json:
         print(json.dumps({"edges": [{"source": s, "target": t, "transformation": T.tolist(), "information": info.tolist(),
@@ -45,6 +51,26 @@ def multiway(model, cloud, a):
         re = np.degrees(np.arccos(np.clip((np.trace(d[:3, :3]) - 1) / 2, -1, 1)))
         print(f"{s:3d} -> {t:3d}  {'uncertain' if u else 'certain  '}  correspondences {info[5, 5]:7.0f}  RE {re:7.3f} deg  "
               f"TE {np.linalg.norm(T[:3, 3] - gt[:3, 3]) * 100:7.3f} cm")
+
+
+def posegraph(model, views, a):
+    """multiway/test_multi_ate.py:164, :175 (:215, :225 with --use-icp) and :268."""
+    res = harness.multiway_trajectory(model, views, use_icp=a.use_icp, use_mutual=a.mutual)
+    records = [res["first_record"].cpu().numpy()] if a.use_icp else []
+    records.append(res["record"].cpu().numpy())
+    if a.json:
+        print(json.dumps({"ate_cm": res["ate_cm"], "errors_cm": res["errors_cm"].cpu().tolist(), "nodes": res["nodes"].cpu().tolist(),
+                          "keep": res["keep"].cpu().tolist(), "records": [r.tolist() for r in records]}))
+        return
+    for i, r in enumerate(records):
+        if i:
+            print("Refine each edge with ICP ...")
+        print(f"Before optimization {len(views)} nodes {int(r[9])} edges")
+        print("Optimizing PoseGraph ...")
+        print(f"  pass 1: {int(r[1])} iterations, {int(r[2])} solves, objective {r[3]:.6g}; pass 2: {int(r[5])} iterations, {int(r[6])} solves, "
+              f"objective {r[7]:.6g}" + ("  (INVALID GRAPH)" if r[0] else ""))
+        print(f"After optimization {len(views)} nodes {int(r[11])} edges")
+    print(f"Mean Absolute Trajectory Error: {res['ate_cm']:.2f} cm")
 
 
 def real_pair(model, cloud, a):
@@ -88,6 +114,8 @@ def main():
     ap.add_argument("--icp-distance", type=float, default=0.10, help="max_correspondence_distance of the ICP post-step")
     ap.add_argument("--multiway", action="store_true", help="the multiway driver's edge loop over --num-views views (test_multi_ate.py:98-157)")
     ap.add_argument("--num-views", type=int, default=5)
+    ap.add_argument("--posegraph", action="store_true", help="with --multiway: node chain, pose-graph optimisation on the device and the ATE "
+                    "(test_multi_ate.py:159-227, :268); --use-icp adds the ICP refinement of the edges and the second optimisation")
     ap.add_argument("--json", action="store_true")
     a = ap.parse_args()
     if a.pcd1:
@@ -105,6 +133,8 @@ def main():
         if not a.pcd1:
             ap.error("--pcd2 goes with --pcd1")
         return real_pair(model, cloud, a)
+    if a.posegraph and not a.multiway:
+        ap.error("--posegraph goes with --multiway")
     if a.multiway:
         return multiway(model, cloud, a)
     pairs = harness.demo_pairs(cloud, a.num_pairs, corrupt=a.outlier_share, descriptor=a.descriptor, voxel=a.voxel)

@@ -10,7 +10,11 @@ LDS.)  What DESIGN.md's register and spill figures are read from, e.g. those of 
 
 and of section 8 f-7 (the FPFH path):
 
-    python tools/kernel_resources.py nb_grid_kernel nb_search_kernel normals_kernel spfh_kernel fpfh_kernel"""
+    python tools/kernel_resources.py nb_grid_kernel nb_search_kernel normals_kernel spfh_kernel fpfh_kernel
+
+and of section 8 f-8 (pose-graph optimisation):
+
+    python tools/kernel_resources.py posegraph"""
 import re
 import subprocess
 import sys
