@@ -12,7 +12,7 @@
  *     pdsc_forward_validation; the weight packers pdsc_wpack_floats / _offset, pdsc_wsplit_bytes / _offset / _build; the workspace
  *     queries pdsc_workspace_bytes / _offset; pdsc_encoder_range_probe; pdsc_version / pdsc_last_error; and, for the callers either
  *     side of the path (SURVEY.md section 8 f-2 .. f-4), pdsc_match_* / pdsc_select_correspondences / pdsc_build_corr_pos,
- *     pdsc_sm_baseline*, pdsc_cal_confidence, pdsc_eval_stats, pdsc_icp_*, pdsc_information_*, pdsc_voxel_*.
+ *     pdsc_sm_baseline*, pdsc_cal_confidence, pdsc_eval_stats, pdsc_icp_*, pdsc_information_*, pdsc_voxel_*, pdsc_cloud_*.
  *   STAGE LEVEL -- one entry point per reference stage (sections a-1 .. a-11 below), the plan / size queries that go with them,
  *     pdsc_selftest_* and the diagnostic hooks.  The forward does not go through them (it calls the same launchers directly); they
  *     exist so that every stage can be parity-checked on its own (tests/test_gpu_parity.py), for the tools, and for a maintainer
@@ -735,6 +735,54 @@ size_t pdsc_fpfh_workspace_bytes(int bs, int N, int normal_max_nn, int feature_m
 int pdsc_fpfh(const float* points, const int* n_per_cloud, double normal_radius, int normal_max_nn, double feature_radius,
               int feature_max_nn, const double* viewpoint, double* fpfh_f64, float* desc_f32, double* normals_out, void* workspace,
               size_t workspace_bytes, int bs, int N, void* stream);
+
+/* ---- FPFH from raw clouds ------------------------------------------------------------------------
+ * The demo's recipe (demo_registration.py:37-44, --descriptor fpfh) for clouds of any size up to 2^24 points: estimate_normals on the
+ * RAW cloud (pdsc_cloud_neighbours at (2 voxel, 30) + pdsc_estimate_normals), voxel_down_sample(voxel) that also averages the normals
+ * of each voxel (pdsc_cloud_voxel_keys, the caller's stable sort, pdsc_cloud_voxel_means), compute_fpfh_feature on the down-sampled
+ * cloud with those normals (pdsc_hybrid_neighbours + pdsc_spfh + pdsc_fpfh_from_spfh).  The three pdsc_cloud_* entries take a
+ * `path` selector, as pdsc_sm_baseline_form takes `form`:
+ *   PDSC_PATH_AUTO (0)           PDSC_PATH_MANY from N >= PDSC_CLOUD_AUTO_MANY rows per cloud on, PDSC_PATH_ONE_WORKGROUP below;
+ *                                PDSC_CLOUD_AUTO_MANY is 2^30, above every admissible N: no time of a raw cloud has been measured
+ *                                yet, so auto is PDSC_PATH_ONE_WORKGROUP for every shape and PDSC_PATH_MANY is OPT-IN (DESIGN.md
+ *                                f-9); the threshold moves down (never below 32768) once a measurement shows where path 2 wins;
+ *   PDSC_PATH_ONE_WORKGROUP (1)  the kernels of f-6 / f-7: one 512-thread workgroup per cloud;
+ *   PDSC_PATH_MANY (2)           chains of ordinary kernels with one workgroup per 1024 points (512 sorted keys for the means):
+ *                                chunk boxes -> reduce -> keys; run heads per tile -> scan -> means; chunk boxes -> grid -> bucket
+ *                                histogram -> scan -> scatter.  No kernel waits for another workgroup.
+ * Both paths give bit-identical results: min / max are order-free, a key depends on its point and the box alone, a run of equal keys
+ * is summed by one thread in input order either way, and the neighbour search ranks its candidates by (d2, index), whatever their
+ * order inside a hash bucket.  pdsc_hybrid_neighbours and pdsc_fpfh behave as PDSC_PATH_AUTO (their workspace holds the chunk boxes);
+ * pdsc_voxel_keys / pdsc_voxel_means have no workspace and stay on one workgroup per cloud.
+ * Two named rules:
+ *   VOXEL_NORMAL_RULE  the normal of a voxel is sum(n_i) / count over its points (fp64, summed in input order), NOT renormalised.
+ *                      This restates open3d 0.9's AccumulatedPoint::GetAverageNormal from memory: open3d is not available where this
+ *                      was written, so the text here is the contract.  Later open3d versions normalise the average, hence the flag:
+ *                      renormalize = 1 gives n / |n| (|n| = sqrt((x x + y y) + z z)), and a zero mean stays (0, 0, 0).  The pair
+ *                      features of pdsc_spfh use whatever comes out, as open3d's do.
+ *   CAPACITY_RULE      out_capacity = output rows per cloud.  A cloud with more occupied voxels than out_capacity gets count -1 and
+ *                      out_capacity zero rows; nothing is ever written beyond out_capacity rows.  (pdsc_hybrid_neighbours, pdsc_spfh,
+ *                      ... read a negative n_per_cloud entry as an empty cloud.)
+ * pdsc_cloud_voxel_keys : pdsc_voxel_keys with a path.
+ * pdsc_cloud_voxel_means: pdsc_voxel_means (same keys, same stable-sort contract, same output order, bit-equal mean points) that also
+ *   averages normals [bs][N][3] double -> out_points [bs][out_capacity][3] fp32, out_normals [bs][out_capacity][3] double (rows beyond
+ *   the count: zero), counts [bs] int32.
+ * pdsc_cloud_neighbours : pdsc_hybrid_neighbours with a path; workspace: pdsc_hybrid_neighbours_workspace_bytes(bs, N).
+ * workspace of the two voxel entries: pdsc_cloud_voxel_workspace_bytes(bs, N) (chunk boxes and head counts; required on every path).
+ * Enqueue-only, graph-capturable.  Bad arguments (null pointer, bs outside 1 .. 65535, N outside 1 .. 2^24, out_capacity < 1,
+ * renormalize not 0 / 1, path outside 0 .. 2, workspace too small) return PDSC_ERR_ARG with nothing enqueued. */
+#define PDSC_PATH_AUTO 0
+#define PDSC_PATH_ONE_WORKGROUP 1
+#define PDSC_PATH_MANY 2
+#define PDSC_CLOUD_AUTO_MANY 1073741824
+size_t pdsc_cloud_voxel_workspace_bytes(int bs, int N);
+int pdsc_cloud_voxel_keys(const float* points, const int* n_per_cloud, double voxel_size, long long* keys, void* workspace,
+                          size_t workspace_bytes, int bs, int N, int path, void* stream);
+int pdsc_cloud_voxel_means(const float* points, const double* normals, const long long* sorted_keys, const long long* perm,
+                           float* out_points, double* out_normals, int* counts, int out_capacity, int renormalize, void* workspace,
+                           size_t workspace_bytes, int bs, int N, int path, void* stream);
+int pdsc_cloud_neighbours(const float* points, const int* n_per_cloud, double radius, int max_nn, int* idx, double* d2, int* count,
+                          void* workspace, size_t workspace_bytes, int bs, int N, int path, void* stream);
 
 /* ---- pose-graph optimisation ---------------------------------------------------------------------
  * pdsc_global_optimization replaces o3d.registration.global_optimization(pose_graph, GlobalOptimizationLevenbergMarquardt(),

@@ -13,7 +13,8 @@ Only what the path needs lives here:
   sharding.py  one-process-per-GPU sharding of pair batches + the single RCCL pose gather
   synthetic.py seeded synthetic correspondence sets / weights (tests + bench)
 """
-from .features import compute_fpfh_feature, estimate_normals, fpfh_descriptors, hybrid_neighbours  # noqa: F401
+from .features import (compute_fpfh_feature, estimate_normals, extract_fpfh_features, fpfh_descriptors,  # noqa: F401
+                       hybrid_neighbours, voxel_down_sample_with_normals)
 from .icp import icp_refine, registration_icp  # noqa: F401
 from .model import PointDSC  # noqa: F401
 from .multiway import (align, global_optimization, information_matrix, local_refinement, loop_closure_edge,  # noqa: F401
@@ -21,4 +22,4 @@ from .multiway import (align, global_optimization, information_matrix, local_ref
 
 __all__ = ["PointDSC", "icp_refine", "registration_icp", "information_matrix", "voxel_down_sample", "loop_closure_edge",
            "multi_scale_icp", "local_refinement", "align", "hybrid_neighbours", "estimate_normals", "compute_fpfh_feature",
-           "fpfh_descriptors", "pose_graph_nodes", "global_optimization"]
+           "fpfh_descriptors", "voxel_down_sample_with_normals", "extract_fpfh_features", "pose_graph_nodes", "global_optimization"]

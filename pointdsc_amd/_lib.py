@@ -138,6 +138,10 @@ SIGNATURES = {
     "pdsc_fpfh_from_spfh": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _vp]),
     "pdsc_fpfh_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "pdsc_fpfh": (_i, [_vp, _vp, C.c_double, _i, C.c_double, _i, C.POINTER(C.c_double), _vp, _vp, _vp, _vp, _sz, _i, _i, _vp]),
+    "pdsc_cloud_voxel_workspace_bytes": (_sz, [_i, _i]),
+    "pdsc_cloud_voxel_keys": (_i, [_vp, _vp, C.c_double, _vp, _vp, _sz, _i, _i, _i, _vp]),
+    "pdsc_cloud_voxel_means": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _sz, _i, _i, _i, _vp]),
+    "pdsc_cloud_neighbours": (_i, [_vp, _vp, C.c_double, _i, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _vp]),
     "pdsc_posegraph_workspace_bytes": (_sz, [_i, _i, _i]),
     "pdsc_posegraph_nodes": (_i, [_vp] * 6 + [_i, _i, _i, _vp]),
     "pdsc_global_optimization": (_i, [_vp] * 9 + [C.c_double, C.c_double, C.c_double, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i,

@@ -4,6 +4,10 @@
 // and in include/pointdsc_hip.h.  Kernels:
 //   nb_grid_kernel    one 512-thread workgroup per cloud counting-sorts the cloud into the hashed cell grid of icp_grid.h
 //                     (cells of width r (1 + 1e-3): the 27-cell lookup equals brute force exactly, margin argument there);
+//                     f-9, for raw clouds (path many of cloud_many.h): the same grid and the same buckets from a chain of
+//                     many-workgroup kernels, cloud_box_kernel (chunk boxes; clears the bucket counts) -> nb_header_kernel (box,
+//                     grid) -> nb_hist_kernel -> nb_scan_kernel -> nb_scatter_kernel; only the order inside a bucket differs,
+//                     which nb_search_kernel does not see (it ranks by (d2, index));
 //   nb_search_kernel  one wavefront per query: lanes over the candidates of the 27 buckets, accepted candidates are appended to an
 //                     LDS buffer, and whenever it fills (and once at the end) a rank count by (d2, index) keeps the max_nn
 //                     smallest in order; the max_nn-th key then tightens the acceptance test (the cut is the common case:
@@ -16,7 +20,7 @@
 // The build compiles with -ffp-contract=off, so every expression below is evaluated as written: the squared distances and the
 // covariance are bit-equal to an fp64 restatement with the same operation order.  Bound: latency / LDS (small per-point problems);
 // reported as time only.
-#include "icp_grid.h"
+#include "cloud_many.h"
 
 namespace pdsc {
 namespace {
@@ -33,7 +37,7 @@ struct NbHeader {
 };
 
 struct NbLayout {
-    size_t tsort, cells, cursor, header, cloud_bytes;
+    size_t tsort, cells, cursor, header, parts, cloud_bytes;
 };
 
 inline NbLayout nb_layout(int N) {
@@ -44,13 +48,9 @@ inline NbLayout nb_layout(int N) {
     L.cells = o;  o += (size_t)round_up((long long)(hmax + 1) * 4, 256);     // bucket counts, then bucket starts
     L.cursor = o; o += (size_t)round_up((long long)hmax * 4, 256);           // scatter cursors
     L.header = o; o += (size_t)round_up((long long)sizeof(NbHeader), 256);
+    L.parts = o;  o += (size_t)round_up((long long)cloud_chunks(N) * (long long)sizeof(CloudBox), 256);   // chunk boxes (path many)
     L.cloud_bytes = o;
     return L;
-}
-
-__device__ __forceinline__ int cloud_count(const int* __restrict__ n_per_cloud, int b, int N) {
-    const int n = n_per_cloud ? n_per_cloud[b] : N;
-    return n < 0 ? 0 : (n > N ? N : n);
 }
 
 // ---- a. neighbour lists ----------------------------------------------------------------------------------------------------
@@ -79,6 +79,74 @@ __global__ __launch_bounds__(ICP_NT) void nb_grid_kernel(const float* __restrict
     if (t == 0) {
         hdr->g = g;
         hdr->bad = 0;
+    }
+}
+
+// ---- a'. the same grid from many workgroups per cloud (f-9) -------------------------------------------------------------------
+// one workgroup per cloud: the chunks' boxes -> the header (the grid of icp_make_grid over the same box)
+__global__ __launch_bounds__(ICP_NT) void nb_header_kernel(const int* __restrict__ n_per_cloud, double rdist,
+                                                           unsigned char* __restrict__ workspace, NbLayout L, int N) {
+    __shared__ float bb[ICP_NW * 6];
+    __shared__ IcpGrid grid_s;
+    const int b = blockIdx.x, t = threadIdx.x;
+    const int n = cloud_count(n_per_cloud, b, N);
+    unsigned char* wb = workspace + (size_t)b * L.cloud_bytes;
+    NbHeader* hdr = reinterpret_cast<NbHeader*>(wb + L.header);
+    float mn[3], mx[3];
+    const bool bad = cloud_box_share(reinterpret_cast<const CloudBox*>(wb + L.parts), cloud_chunks(N), mn, mx);
+    if (__syncthreads_or(bad)) {
+        if (t == 0) hdr->bad = 1;
+        return;
+    }
+    icp_make_grid(mn, mx, n, rdist, bb, &grid_s);
+    __syncthreads();
+    if (t == 0) {
+        hdr->g = grid_s;
+        hdr->bad = 0;
+    }
+}
+
+// grid (nchunk, bs): bucket counts (cleared by cloud_box_kernel)
+__global__ __launch_bounds__(ICP_NT) void nb_hist_kernel(const float* __restrict__ points, const int* __restrict__ n_per_cloud,
+                                                         unsigned char* __restrict__ workspace, NbLayout L, int N) {
+    const int c = blockIdx.x, b = blockIdx.y, t = threadIdx.x;
+    const int n = cloud_count(n_per_cloud, b, N);
+    const float* pb = points + (size_t)b * N * 3;
+    unsigned char* wb = workspace + (size_t)b * L.cloud_bytes;
+    const NbHeader* hdr = reinterpret_cast<const NbHeader*>(wb + L.header);
+    if (hdr->bad) return;
+    const IcpGrid g = hdr->g;
+    int* cells = reinterpret_cast<int*>(wb + L.cells);
+    const int i1 = min((c + 1) * CLOUD_CHUNK, n);
+    for (int i = c * CLOUD_CHUNK + t; i < i1; i += ICP_NT) atomicAdd(&cells[icp_target_bucket(pb[i * 3], pb[i * 3 + 1], pb[i * 3 + 2], g)], 1);
+}
+
+// one workgroup per cloud: bucket counts -> bucket starts and scatter cursors
+__global__ __launch_bounds__(ICP_NT) void nb_scan_kernel(unsigned char* __restrict__ workspace, NbLayout L) {
+    __shared__ int scan[ICP_NT];
+    unsigned char* wb = workspace + (size_t)blockIdx.x * L.cloud_bytes;
+    const NbHeader* hdr = reinterpret_cast<const NbHeader*>(wb + L.header);
+    if (hdr->bad) return;
+    icp_scan_cells(reinterpret_cast<int*>(wb + L.cells), reinterpret_cast<int*>(wb + L.cursor), hdr->g.hmask + 1, scan);
+}
+
+// grid (nchunk, bs)
+__global__ __launch_bounds__(ICP_NT) void nb_scatter_kernel(const float* __restrict__ points, const int* __restrict__ n_per_cloud,
+                                                            unsigned char* __restrict__ workspace, NbLayout L, int N) {
+    const int c = blockIdx.x, b = blockIdx.y, t = threadIdx.x;
+    const int n = cloud_count(n_per_cloud, b, N);
+    const float* pb = points + (size_t)b * N * 3;
+    unsigned char* wb = workspace + (size_t)b * L.cloud_bytes;
+    const NbHeader* hdr = reinterpret_cast<const NbHeader*>(wb + L.header);
+    if (hdr->bad) return;
+    const IcpGrid g = hdr->g;
+    int* cursor = reinterpret_cast<int*>(wb + L.cursor);
+    float4* tsort = reinterpret_cast<float4*>(wb + L.tsort);
+    const int i1 = min((c + 1) * CLOUD_CHUNK, n);
+    for (int i = c * CLOUD_CHUNK + t; i < i1; i += ICP_NT) {
+        const float x = pb[i * 3], y = pb[i * 3 + 1], z = pb[i * 3 + 2];
+        const int pos = atomicAdd(&cursor[icp_target_bucket(x, y, z, g)], 1);
+        tsort[pos] = make_float4(x, y, z, __int_as_float(i));          // order inside a bucket is free: the search ranks by (d2, index)
     }
 }
 
@@ -455,15 +523,37 @@ inline bool shape_ok(int bs, int N) { return bs > 0 && bs <= 65535 && N > 0 && N
 inline bool nn_ok(int max_nn) { return max_nn >= 1 && max_nn <= FPFH_MAX_NN; }
 inline bool radius_ok(double r) { return r > 0.0 && isfinite(r); }
 
-// the two launches of a neighbour search; arguments checked by the caller
+// the launches of a neighbour search (the grid: one kernel, or the five of path many; then the search); arguments checked by the caller
 int enqueue_neighbours(const float* points, const int* n_per_cloud, double radius, int max_nn, int* idx, double* d2, int* count,
-                       void* workspace, int bs, int N, hipStream_t st, const char* what) {
+                       void* workspace, int bs, int N, int path, hipStream_t st, const char* what) {
     const NbLayout L = nb_layout(N);
     // FLANN's radius search takes the squared radius as float: float(r * r), compared with '<' against the fp64 distance
     const double r2 = (double)(float)(radius * radius);
-    hipLaunchKernelGGL(nb_grid_kernel, dim3(bs), dim3(ICP_NT), 0, st, points, n_per_cloud, radius, (unsigned char*)workspace, L, N);
-    const int rc = check_launch(what);
-    if (rc != PDSC_OK) return rc;
+    unsigned char* ws = (unsigned char*)workspace;
+    int rc;
+    if (!path_many(path, N)) {
+        hipLaunchKernelGGL(nb_grid_kernel, dim3(bs), dim3(ICP_NT), 0, st, points, n_per_cloud, radius, ws, L, N);
+        rc = check_launch(what);
+        if (rc != PDSC_OK) return rc;
+    } else {
+        const int nchunk = cloud_chunks(N);
+        hipLaunchKernelGGL(cloud_box_kernel, dim3(nchunk, bs), dim3(ICP_NT), 0, st, points, n_per_cloud, ws + L.parts, L.cloud_bytes,
+                           ws + L.cells, L.cloud_bytes, icp_hash_size(N) + 1, N);
+        rc = check_launch(what);
+        if (rc != PDSC_OK) return rc;
+        hipLaunchKernelGGL(nb_header_kernel, dim3(bs), dim3(ICP_NT), 0, st, n_per_cloud, radius, ws, L, N);
+        rc = check_launch(what);
+        if (rc != PDSC_OK) return rc;
+        hipLaunchKernelGGL(nb_hist_kernel, dim3(nchunk, bs), dim3(ICP_NT), 0, st, points, n_per_cloud, ws, L, N);
+        rc = check_launch(what);
+        if (rc != PDSC_OK) return rc;
+        hipLaunchKernelGGL(nb_scan_kernel, dim3(bs), dim3(ICP_NT), 0, st, ws, L);
+        rc = check_launch(what);
+        if (rc != PDSC_OK) return rc;
+        hipLaunchKernelGGL(nb_scatter_kernel, dim3(nchunk, bs), dim3(ICP_NT), 0, st, points, n_per_cloud, ws, L, N);
+        rc = check_launch(what);
+        if (rc != PDSC_OK) return rc;
+    }
     hipLaunchKernelGGL(nb_search_kernel, dim3(N, bs), dim3(FPFH_WAVE), 0, st, points, n_per_cloud, r2, max_nn, idx, d2, count,
                        (const unsigned char*)workspace, L, N);
     return check_launch(what);
@@ -482,14 +572,15 @@ size_t fpfh_workspace_bytes(int bs, int N, int nn_n, int nn_f) {
 }
 
 int launch_hybrid_neighbours(const float* points, const int* n_per_cloud, double radius, int max_nn, int* idx, double* d2, int* count,
-                             void* workspace, size_t workspace_bytes, int bs, int N, hipStream_t st) {
+                             void* workspace, size_t workspace_bytes, int bs, int N, int path, hipStream_t st) {
     PDSC_REQUIRE(points && idx && count && workspace, "pdsc_hybrid_neighbours: null pointer");
     PDSC_REQUIRE(shape_ok(bs, N), "pdsc_hybrid_neighbours: bs=%d N=%d", bs, N);
     PDSC_REQUIRE(radius_ok(radius), "pdsc_hybrid_neighbours: radius %g must be positive and finite", radius);
     PDSC_REQUIRE(nn_ok(max_nn), "pdsc_hybrid_neighbours: max_nn=%d outside 1 .. %d", max_nn, FPFH_MAX_NN);
+    PDSC_REQUIRE(path_ok(path), "pdsc_hybrid_neighbours: path=%d outside 0 .. 2", path);
     const size_t need = hybrid_neighbours_workspace_bytes(bs, N);
     PDSC_REQUIRE(workspace_bytes >= need, "pdsc_hybrid_neighbours: workspace %zu bytes < %zu", workspace_bytes, need);
-    return enqueue_neighbours(points, n_per_cloud, radius, max_nn, idx, d2, count, workspace, bs, N, st, "pdsc_hybrid_neighbours");
+    return enqueue_neighbours(points, n_per_cloud, radius, max_nn, idx, d2, count, workspace, bs, N, path, st, "pdsc_hybrid_neighbours");
 }
 
 int launch_estimate_normals(const float* points, const int* n_per_cloud, const int* idx, const int* count, int max_nn,
@@ -545,12 +636,14 @@ int launch_fpfh(const float* points, const int* n_per_cloud, double normal_radiu
     int* count_f = reinterpret_cast<int*>(ws + L.count_f);
     double* normals = normals_out ? normals_out : reinterpret_cast<double*>(ws + L.normals);
     double* spfh = reinterpret_cast<double*>(ws + L.spfh);
-    int rc = enqueue_neighbours(points, n_per_cloud, normal_radius, normal_max_nn, idx_n, nullptr, count_n, ws + L.nb, bs, N, st,
+    int rc = enqueue_neighbours(points, n_per_cloud, normal_radius, normal_max_nn, idx_n, nullptr, count_n, ws + L.nb, bs, N,
+                                PDSC_PATH_AUTO, st,
                                 "pdsc_fpfh");
     if (rc != PDSC_OK) return rc;
     rc = launch_estimate_normals(points, n_per_cloud, idx_n, count_n, normal_max_nn, viewpoint, normals, bs, N, st);
     if (rc != PDSC_OK) return rc;
-    rc = enqueue_neighbours(points, n_per_cloud, feature_radius, feature_max_nn, idx_f, d2_f, count_f, ws + L.nb, bs, N, st, "pdsc_fpfh");
+    rc = enqueue_neighbours(points, n_per_cloud, feature_radius, feature_max_nn, idx_f, d2_f, count_f, ws + L.nb, bs, N, PDSC_PATH_AUTO, st,
+                            "pdsc_fpfh");
     if (rc != PDSC_OK) return rc;
     rc = launch_spfh(points, n_per_cloud, normals, idx_f, count_f, feature_max_nn, spfh, bs, N, st);
     if (rc != PDSC_OK) return rc;
@@ -564,6 +657,12 @@ extern "C" size_t pdsc_hybrid_neighbours_workspace_bytes(int bs, int N) { return
 extern "C" int pdsc_hybrid_neighbours(const float* points, const int* n_per_cloud, double radius, int max_nn, int* idx, double* d2,
                                       int* count, void* workspace, size_t workspace_bytes, int bs, int N, void* stream) {
     return pdsc::launch_hybrid_neighbours(points, n_per_cloud, radius, max_nn, idx, d2, count, workspace, workspace_bytes, bs, N,
+                                          PDSC_PATH_AUTO, (hipStream_t)stream);
+}
+
+extern "C" int pdsc_cloud_neighbours(const float* points, const int* n_per_cloud, double radius, int max_nn, int* idx, double* d2,
+                                     int* count, void* workspace, size_t workspace_bytes, int bs, int N, int path, void* stream) {
+    return pdsc::launch_hybrid_neighbours(points, n_per_cloud, radius, max_nn, idx, d2, count, workspace, workspace_bytes, bs, N, path,
                                           (hipStream_t)stream);
 }
 

@@ -178,6 +178,41 @@ __device__ __forceinline__ void icp_make_grid(float (&mn)[3], float (&mx)[3], in
     }
 }
 
+// the bucket of a target point (its cell is clamped into the grid: never taken, the same expression as nx; kept as a guard)
+__device__ __forceinline__ int icp_target_bucket(float x, float y, float z, const IcpGrid& g) {
+    int cx = (int)icp_cell(x, g.xmin, g.w), cy = (int)icp_cell(y, g.ymin, g.w), cz = (int)icp_cell(z, g.zmin, g.w);
+    cx = cx < 0 ? 0 : (cx >= g.nx ? g.nx - 1 : cx);
+    cy = cy < 0 ? 0 : (cy >= g.ny ? g.ny - 1 : cy);
+    cz = cz < 0 ? 0 : (cz >= g.nz ? g.nz - 1 : cz);
+    return icp_bucket(cx, cy, cz, g.hmask);
+}
+
+// One workgroup: bucket counts cells[0, hsize) -> their exclusive scan in cells and cursor, cells[hsize] = the total: `per`
+// consecutive buckets per thread, Hillis-Steele over the thread totals.  scan: ICP_NT ints of LDS.
+__device__ __forceinline__ void icp_scan_cells(int* cells, int* cursor, int hsize, int* scan) {
+    const int t = threadIdx.x;
+    const int per = (hsize + ICP_NT - 1) / ICP_NT;
+    const int h0 = t * per, h1 = min(h0 + per, hsize);
+    int local = 0;
+    for (int h = h0; h < h1; ++h) local += cells[h];
+    scan[t] = local;
+    __syncthreads();
+    for (int off = 1; off < ICP_NT; off <<= 1) {
+        const int v = scan[t] + (t >= off ? scan[t - off] : 0);
+        __syncthreads();
+        scan[t] = v;
+        __syncthreads();
+    }
+    int run = scan[t] - local;
+    for (int h = h0; h < h1; ++h) {
+        const int c = cells[h];
+        cells[h] = run;
+        cursor[h] = run;
+        run += c;
+    }
+    if (t == ICP_NT - 1) cells[hsize] = scan[t];                       // == nt
+}
+
 // Counting sort of the target into the grid's hsize = hmask + 1 buckets: cells[h] .. cells[h + 1] bound bucket h in tsort
 // (float4 {x, y, z, original index}).  cells: hsize + 1 ints, cursor: hsize ints (global), scan: ICP_NT ints of LDS.  The caller
 // synchronises before the first search.
@@ -187,41 +222,13 @@ __device__ __forceinline__ void icp_sort_target(const float* __restrict__ tgtb, 
     const int hsize = g.hmask + 1;
     for (int h = t; h <= hsize; h += ICP_NT) cells[h] = 0;
     __syncthreads();
-    auto target_bucket = [&](float x, float y, float z) {
-        int cx = (int)icp_cell(x, g.xmin, g.w), cy = (int)icp_cell(y, g.ymin, g.w), cz = (int)icp_cell(z, g.zmin, g.w);
-        cx = cx < 0 ? 0 : (cx >= g.nx ? g.nx - 1 : cx);               // never taken (same expression as nx), kept as a guard
-        cy = cy < 0 ? 0 : (cy >= g.ny ? g.ny - 1 : cy);
-        cz = cz < 0 ? 0 : (cz >= g.nz ? g.nz - 1 : cz);
-        return icp_bucket(cx, cy, cz, g.hmask);
-    };
-    for (int i = t; i < nt; i += ICP_NT) atomicAdd(&cells[target_bucket(tgtb[i * 3], tgtb[i * 3 + 1], tgtb[i * 3 + 2])], 1);
+    for (int i = t; i < nt; i += ICP_NT) atomicAdd(&cells[icp_target_bucket(tgtb[i * 3], tgtb[i * 3 + 1], tgtb[i * 3 + 2], g)], 1);
     __syncthreads();
-    {   // exclusive scan of cells[0, hsize): `per` consecutive buckets per thread, Hillis-Steele over the thread totals
-        const int per = (hsize + ICP_NT - 1) / ICP_NT;
-        const int h0 = t * per, h1 = min(h0 + per, hsize);
-        int local = 0;
-        for (int h = h0; h < h1; ++h) local += cells[h];
-        scan[t] = local;
-        __syncthreads();
-        for (int off = 1; off < ICP_NT; off <<= 1) {
-            const int v = scan[t] + (t >= off ? scan[t - off] : 0);
-            __syncthreads();
-            scan[t] = v;
-            __syncthreads();
-        }
-        int run = scan[t] - local;
-        for (int h = h0; h < h1; ++h) {
-            const int c = cells[h];
-            cells[h] = run;
-            cursor[h] = run;
-            run += c;
-        }
-        if (t == ICP_NT - 1) cells[hsize] = scan[t];                   // == nt
-    }
+    icp_scan_cells(cells, cursor, hsize, scan);
     __syncthreads();
     for (int i = t; i < nt; i += ICP_NT) {
         const float x = tgtb[i * 3], y = tgtb[i * 3 + 1], z = tgtb[i * 3 + 2];
-        const int pos = atomicAdd(&cursor[target_bucket(x, y, z)], 1);
+        const int pos = atomicAdd(&cursor[icp_target_bucket(x, y, z, g)], 1);
         tsort[pos] = make_float4(x, y, z, __int_as_float(i));          // order inside a bucket is free: the search is order-independent
     }
 }

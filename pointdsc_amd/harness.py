@@ -32,7 +32,7 @@ import torch
 
 from . import ops
 from .correspondences import build_correspondences
-from .features import fpfh_descriptors
+from .features import extract_fpfh_features, fpfh_descriptors
 from .icp import icp_refine
 from .multiway import local_refinement, loop_closure_edge
 
@@ -223,6 +223,16 @@ def device_fpfh(points: np.ndarray, voxel: float, device: str = "cuda:0") -> tor
     """FPFH descriptors [n,33] fp32 of a cloud down-sampled at `voxel`, computed and left on the device (f-7)."""
     pts = torch.from_numpy(np.ascontiguousarray(points, dtype=np.float32)).to(torch.device(device))
     return fpfh_descriptors(pts[None], voxel)[0]
+
+
+def device_demo_fpfh(raw_points: np.ndarray, voxel: float, device: str = "cuda:0") -> Tuple[torch.Tensor, torch.Tensor]:
+    """The demo's ``extract_fpfh_features`` (demo_registration.py:37-44) on a RAW cloud (f-9): the vertices go to the device as they
+    are, normals are estimated on them, the cloud is down-sampled at `voxel` with averaged normals, and FPFH is computed on the
+    result.  Nothing is down-sampled on the host.  Returns (points [n,3] fp32, desc [n,33] fp32), both left on the device."""
+    pts = torch.from_numpy(np.ascontiguousarray(raw_points, dtype=np.float32)).to(torch.device(device))
+    res = extract_fpfh_features(pts[None], voxel)
+    n = max(0, int(res["counts"][0].item()))
+    return res["points"][0, :n], res["desc"][0, :n]
 
 
 def demo_pairs(cloud: np.ndarray, num_pairs: int, dim: int = 33, cell: float = 0.05, corrupt: float = 0.6,

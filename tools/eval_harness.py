@@ -77,11 +77,16 @@ def real_pair(model, cloud, a):
     """demo_registration.py:101-117 on two real clouds: FPFH -> matching -> forward (-> ICP); no ground truth."""
     from pointdsc_amd import icp_refine
     from pointdsc_amd.correspondences import build_correspondences
-    cloud2 = harness.voxel_down_sample(harness.read_ply_xyz(a.pcd2), a.voxel)
     dev = torch.device("cuda:0")
     with torch.no_grad():
-        pts = [torch.from_numpy(c).to(dev) for c in (cloud, cloud2)]
-        desc = [harness.device_fpfh(c, a.voxel) for c in (cloud, cloud2)]
+        if a.fpfh_recipe == "demo":             # demo_registration.py:37-44: the raw vertices go to the device, nothing is down-sampled here
+            cloud2 = harness.read_ply_xyz(a.pcd2)
+            pts, desc = zip(*(harness.device_demo_fpfh(c, a.voxel) for c in (cloud, cloud2)))
+            cloud, cloud2 = pts
+        else:
+            cloud2 = harness.voxel_down_sample(harness.read_ply_xyz(a.pcd2), a.voxel)
+            pts = [torch.from_numpy(c).to(dev) for c in (cloud, cloud2)]
+            desc = [harness.device_fpfh(c, a.voxel) for c in (cloud, cloud2)]
         c = build_correspondences(desc[0], desc[1], pts[0], pts[1], use_mutual=a.mutual)
         res = model({"corr_pos": c["corr_pos"], "src_keypts": c["src_keypts"], "tgt_keypts": c["tgt_keypts"], "testing": True})
         trans = res["final_trans"]
@@ -104,6 +109,10 @@ def main():
                     "(no ground truth: pose and inlier count only)")
     ap.add_argument("--descriptor", choices=("standin", "fpfh"), default="standin",
                     help="stand-in descriptors with a known outlier share, or FPFH on the device (misc/cal_fpfh.py:21-26)")
+    ap.add_argument("--fpfh-recipe", choices=("cal_fpfh", "demo"), default="cal_fpfh",
+                    help="with --pcd1 / --pcd2: cal_fpfh = down-sample on the host, then normals and FPFH on the device (misc/cal_fpfh.py); "
+                    "demo = demo_registration.py:37-44 on the device from the raw vertices (normals on the raw cloud, voxel step that "
+                    "averages them, FPFH)")
     ap.add_argument("--voxel", type=float, default=0.05, help="config.downsample of the 3DMatch snapshot")
     ap.add_argument("--num-pairs", type=int, default=8)
     ap.add_argument("--outlier-share", type=float, default=0.6, help="share of stand-in descriptors replaced by noise")
@@ -118,7 +127,11 @@ def main():
                     "(test_multi_ate.py:159-227, :268); --use-icp adds the ICP refinement of the edges and the second optimisation")
     ap.add_argument("--json", action="store_true")
     a = ap.parse_args()
-    if a.pcd1:
+    if a.fpfh_recipe == "demo" and not (a.pcd1 and a.pcd2):
+        ap.error("--fpfh-recipe demo goes with --pcd1 and --pcd2")
+    if a.pcd1 and a.fpfh_recipe == "demo":
+        cloud = harness.read_ply_xyz(a.pcd1)              # raw: real_pair sends it to the device as it is
+    elif a.pcd1:
         cloud = harness.voxel_down_sample(harness.read_ply_xyz(a.pcd1), a.voxel)
     else:
         cloud = np.load(ROOT / "tests" / "golden" / "demo_clouds_vox005.npz")["cloud_bin_0"]

@@ -12,6 +12,11 @@ and of section 8 f-7 (the FPFH path):
 
     python tools/kernel_resources.py nb_grid_kernel nb_search_kernel normals_kernel spfh_kernel fpfh_kernel
 
+and of section 8 f-9 (the raw-cloud path: the many-workgroups chains in front of the descriptor):
+
+    python tools/kernel_resources.py cloud_box_kernel voxel_box_kernel voxel_keys_many_kernel voxel_heads_kernel voxel_scan_kernel \
+        voxel_means nb_header_kernel nb_hist_kernel nb_scan_kernel nb_scatter_kernel
+
 and of section 8 f-8 (pose-graph optimisation):
 
     python tools/kernel_resources.py posegraph"""
