@@ -12,7 +12,7 @@
  *     pdsc_forward_validation; the weight packers pdsc_wpack_floats / _offset, pdsc_wsplit_bytes / _offset / _build; the workspace
  *     queries pdsc_workspace_bytes / _offset; pdsc_encoder_range_probe; pdsc_version / pdsc_last_error; and, for the callers either
  *     side of the path (SURVEY.md section 8 f-2 .. f-4), pdsc_match_* / pdsc_select_correspondences / pdsc_build_corr_pos,
- *     pdsc_sm_baseline*, pdsc_cal_confidence, pdsc_eval_stats, pdsc_icp_*, pdsc_information_*, pdsc_voxel_*, pdsc_cloud_*.
+ *     pdsc_sm_baseline*, pdsc_pmc_*, pdsc_cal_confidence, pdsc_eval_stats, pdsc_icp_*, pdsc_information_*, pdsc_voxel_*, pdsc_cloud_*.
  *   STAGE LEVEL -- one entry point per reference stage (sections a-1 .. a-11 below), the plan / size queries that go with them,
  *     pdsc_selftest_* and the diagnostic hooks.  The forward does not go through them (it calls the same launchers directly); they
  *     exist so that every stage can be parity-checked on its own (tests/test_gpu_parity.py), for the tools, and for a maintainer
@@ -608,6 +608,53 @@ int pdsc_sm_baseline(const float* corr_pos, const float* src_keypts, const float
 int pdsc_sm_baseline_form(const float* corr_pos, const float* src_keypts, const float* tgt_keypts, float inlier_threshold,
                           int num_top, int num_iterations, float* pred_trans, float* pred_labels, float* leading_eig,
                           void* workspace, size_t workspace_bytes, int bs, int N, int form, void* stream);
+
+/* ---- PMC baseline: exact maximum clique of the compatibility graph ----------------------------
+ * replaces PMC() of baseline_scripts/baseline_3DMatch.py:56-77.  Vertices = correspondences; i and j are joined iff
+ *   | ((dx*dx + dy*dy) + dz*dz)  -  ((ex*ex + ey*ey) + ez*ez) | < inlier_threshold,   d = c_i[0:3] - c_j[0:3], e = c_i[3:6] - c_j[3:6]
+ * in fp32 in exactly this order (SQUARED distances, as the reference writes it; c = corr_pos, the centred coordinates the reference
+ * passes as `corr`): the edge set is numpy's bit for bit.  pred_labels = 1 on a maximum clique, pred_trans =
+ * rigid_transform_3d(src_keypts, tgt_keypts, pred_labels).
+ *
+ * pdsc_pmc_adjacency: bits [bs][N][ld_words] 64-bit words, bit (j & 63) of word (j >> 6) of row i = edge (i, j); zero diagonal,
+ *   symmetric, the bits of columns >= N and the words beyond ceil(N / 64) zero.  ld_words >= ceil(N / 64).  N <= 16384.
+ *
+ * pdsc_pmc_baseline: adjacency, degrees, the order (degree descending, index ascending), a greedy clique from every vertex (its
+ *   largest = the lower bound), branch and bound with a greedy-colouring bound, labels, Procrustes -- ten launches, no host
+ *   synchronisation, nothing allocated.  The ROOT of a clique is its last member in the order; root r's subproblem (r + its neighbours
+ *   earlier in the order, renumbered into a bitset of their own) is searched by one single-wave workgroup whose incumbent is private
+ *   and starts at the lower bound, so nothing depends on the order in which workgroups finish: the same inputs give the same bits in
+ *   every output, for a pair alone or inside a batch, with proven = 0 as well.
+ *   max_nodes (1 .. 2^30, mandatory): the number of NODES one workgroup (= one root's search, but see LIMITS) may expand per launch; a node = one branching step (one vertex joins
+ *     the current clique and the child's candidate set is formed).  A root that runs out keeps its best find; the call returns normally.
+ *   clique_size [bs] int: size of the labelled clique.  proven [bs] int: 1 = every root was exhausted or cut by its bound, the size
+ *     is the maximum; 0 = some root ran out of max_nodes (or could not be served, below) and the clique is the best one found.
+ *   TIE RULE: the largest clique wins; a root's clique replaces the greedy one only when strictly larger; among roots with equally
+ *     large cliques the root earliest in the order wins; inside a root the first clique of that size met by the depth-first search
+ *     (branching on the later-ordered candidate first) stays; among greedy cliques of equal size the start vertex earliest in the order.
+ *     A graph without edges (and N = 1) therefore labels vertex 0 alone: clique_size 1, proven 1.
+ *   LIMITS: N <= 16384.  A root's candidate bitsets and their n x ceil(n / 64)-word adjacency live in 48 KiB of LDS when
+ *     8 (n ceil(n / 64) + 2 ceil(n / 64) (colours of the root + 1)) bytes fit (n up to ~ 500 - 600 candidates), else in a slab of the
+ *     workspace, which serves n <= 4096 candidates and 1024 stack levels; a root beyond that is not searched and makes proven 0.
+ *     The slab pass has 64 workgroups per pair; workgroup g serves the roots g, g + 64, ... that did not fit, in ascending order,
+ *     with ONE budget of max_nodes for all of them, a node there being charged 8 (its matrix is behind the L2, not in LDS).
+ *   The workspace's first bs x 4 int64 hold, per pair, after the call: nodes expanded, roots searched, roots not exhausted, the greedy bound.
+ * Bad arguments (null pointer, N < 1 or > 16384, max_nodes out of range) return PDSC_ERR_ARG, a short workspace PDSC_ERR_WORKSPACE,
+ * with nothing enqueued. */
+int pdsc_pmc_adjacency(const float* corr_pos, float inlier_threshold, unsigned long long* bits, long long ld_words, int bs, int N,
+                       void* stream);
+size_t pdsc_pmc_workspace_bytes(int bs, int N);
+int pdsc_pmc_baseline(const float* corr_pos, const float* src_keypts, const float* tgt_keypts, float inlier_threshold, int max_nodes,
+                      float* pred_trans, float* pred_labels, int* clique_size, int* proven, void* workspace, size_t workspace_bytes,
+                      int bs, int N, void* stream);
+/* The same call with two options for tools and tests.  lds_words: 0, or the number of 8-byte words (1 .. 6144) of the LDS pool the
+ * first search pass may use -- a small value sends every root through the slab pass (same results where the budget allows: the
+ * two passes run the same code).  stage_ms (HOST, 4 floats, or NULL): the call is bracketed by events on the stream and returns
+ * the milliseconds of adjacency | ordering, greedy cliques and bound | search | labels and Procrustes; asking for them
+ * synchronises the host on the last event (tools/pmc_bench.py). */
+int pdsc_pmc_baseline_ex(const float* corr_pos, const float* src_keypts, const float* tgt_keypts, float inlier_threshold, int max_nodes,
+                         float* pred_trans, float* pred_labels, int* clique_size, int* proven, void* workspace, size_t workspace_bytes,
+                         int bs, int N, int lds_words, float* stage_ms, void* stream);
 
 /* cal_confidence (models/PointDSC.py:366-401): confidence of a spectral-matching solution from its compatibility matrix
  * M [bs][N][ld] (ld >= N, multiple of 4) and leading eigenvector [bs][N]:

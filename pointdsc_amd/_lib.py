@@ -121,6 +121,10 @@ SIGNATURES = {
     "pdsc_sm_workspace_bytes": (_sz, [_i, _i]),
     "pdsc_sm_baseline": (_i, [_vp, _vp, _vp, _f, _i, _i, _vp, _vp, _vp, _vp, _sz, _i, _i, _vp]),
     "pdsc_sm_baseline_form": (_i, [_vp, _vp, _vp, _f, _i, _i, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _vp]),
+    "pdsc_pmc_adjacency": (_i, [_vp, _f, _vp, _ll, _i, _i, _vp]),
+    "pdsc_pmc_workspace_bytes": (_sz, [_i, _i]),
+    "pdsc_pmc_baseline": (_i, [_vp, _vp, _vp, _f, _i, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _vp]),
+    "pdsc_pmc_baseline_ex": (_i, [_vp, _vp, _vp, _f, _i, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, C.POINTER(C.c_float), _vp]),
     "pdsc_cal_confidence_workspace_bytes": (_sz, [_i, _i]),
     "pdsc_cal_confidence": (_i, [_vp, _ll, _vp, _i, _i, _vp, _vp, _sz, _i, _i, _vp]),
     "pdsc_eval_stats": (_i, [_vp, _vp, _vp, _vp, _f, _f, _vp, _i, _i, _vp]),

@@ -140,6 +140,28 @@ def gt_labels_from_trans(src_keypts: torch.Tensor, tgt_keypts: torch.Tensor, gt_
     return ((warped - tgt_keypts).norm(dim=-1) < thr).float()
 
 
+class BaselineModel:
+    """A classical baseline of baseline_scripts/baseline_3DMatch.py (``--method SM`` / ``PMC``) behind the model's calling
+    convention, so that eval_scene runs it in place of the network: data dict with corr_pos / src_keypts / tgt_keypts ([1,N,.]
+    tensors, or lists of per-pair [N,.] tensors) -> {"final_trans": [B,4,4], "final_labels": per-pair [N] rows}."""
+    METHODS = ("SM", "PMC")
+
+    def __init__(self, method: str, inlier_threshold: float = 0.10):
+        if method not in self.METHODS:
+            raise ValueError(f"baseline must be one of {self.METHODS}, got {method!r}")
+        self.method, self.inlier_threshold = method, float(inlier_threshold)
+
+    def __call__(self, data):
+        from . import baselines
+        fn = baselines.SM if self.method == "SM" else baselines.PMC
+        c, s, t = data["corr_pos"], data["src_keypts"], data["tgt_keypts"]
+        if torch.is_tensor(c):
+            trans, labels = fn(c, s, t, self.inlier_threshold)
+            return {"final_trans": trans, "final_labels": labels}
+        out = [fn(ci[None], si[None], ti[None], self.inlier_threshold) for ci, si, ti in zip(c, s, t)]      # every pair has its own N
+        return {"final_trans": torch.cat([o[0] for o in out]), "final_labels": [o[1][0] for o in out]}
+
+
 def eval_scene(model, pairs: Iterable[Dict[str, np.ndarray]], scene_ind: int = 0, re_thre: float = 15.0, te_thre: float = 30.0,
                inlier_threshold: float = 0.10, use_mutual: bool = False, device: str = "cuda:0", batch_size: int = 1,
                use_icp: bool = False, icp_distance: float = 0.10) -> np.ndarray:

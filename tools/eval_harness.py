@@ -5,6 +5,7 @@
     python tools/eval_harness.py --pcd1 a.ply --pcd2 b.ply --descriptor fpfh [--use-icp]
     python tools/eval_harness.py --multiway [--num-views 5] [--descriptor {standin,fpfh}]
     python tools/eval_harness.py --multiway --posegraph [--use-icp] [--num-views 5]
+    python tools/eval_harness.py --baseline {SM,PMC} [--num-pairs 8]
 
 Without --pcd1 the down-sampled demo cloud of tests/golden/demo_clouds_vox005.npz (reference demo_data/cloud_bin_0.ply at
 0.05 m) is used.  Every pair = the cloud against a seeded second view of it (partial overlap, noise, random rigid motion),
@@ -18,6 +19,8 @@ the device-side information matrix and the overlap gate (uncertain edges); print
 --multiway --posegraph goes on as the driver does (:159-227, harness.multiway_trajectory): node chain, pose-graph optimisation on the
 device (with --use-icp: multi-scale ICP of every edge and a second optimisation), and the driver's lines -- "Before optimization ...
 nodes ... edges", "After optimization ...", "Mean Absolute Trajectory Error: ... cm" against the views' true poses.
+--baseline runs a classical baseline of baseline_scripts/baseline_3DMatch.py (--method SM / PMC: pointdsc_amd.baselines) in place of
+the model on the same pairs and prints the same stats rows.
 Registration Recall on 3DMatch-FCGF itself needs the released weights and the dataset (both absent here): pass
 --snapshot / real descriptors when they exist; the loop is the same.
 """
@@ -125,8 +128,12 @@ def main():
     ap.add_argument("--num-views", type=int, default=5)
     ap.add_argument("--posegraph", action="store_true", help="with --multiway: node chain, pose-graph optimisation on the device and the ATE "
                     "(test_multi_ate.py:159-227, :268); --use-icp adds the ICP refinement of the edges and the second optimisation")
+    ap.add_argument("--baseline", choices=harness.BaselineModel.METHODS, default=None,
+                    help="run this baseline of baseline_3DMatch.py in place of the model (pair loop only)")
     ap.add_argument("--json", action="store_true")
     a = ap.parse_args()
+    if a.baseline and (a.pcd2 or a.multiway or a.posegraph or a.snapshot):
+        ap.error("--baseline replaces the model in the pair loop: not with --pcd2, --multiway, --posegraph or --snapshot")
     if a.fpfh_recipe == "demo" and not (a.pcd1 and a.pcd2):
         ap.error("--fpfh-recipe demo goes with --pcd1 and --pcd2")
     if a.pcd1 and a.fpfh_recipe == "demo":
@@ -136,12 +143,15 @@ def main():
     else:
         cloud = np.load(ROOT / "tests" / "golden" / "demo_clouds_vox005.npz")["cloud_bin_0"]
     kw = dict(workloads.BASE_MODEL)                       # evaluation/test_3DMatch.py:215-224 with the snapshot's config.json
-    model = PointDSC(**kw)
-    if a.snapshot:
-        print(model.load_state_dict(torch.load(a.snapshot, map_location="cpu"), strict=False))      # test_3DMatch.py:225-226
+    if a.baseline:
+        model = harness.BaselineModel(a.baseline, kw["inlier_threshold"])
     else:
-        model.load_state_dict(workloads.state_dict("n5000_b32", model.state_dict()))
-    model = model.eval().cuda()
+        model = PointDSC(**kw)
+        if a.snapshot:
+            print(model.load_state_dict(torch.load(a.snapshot, map_location="cpu"), strict=False))      # test_3DMatch.py:225-226
+        else:
+            model.load_state_dict(workloads.state_dict("n5000_b32", model.state_dict()))
+        model = model.eval().cuda()
     if a.pcd2:
         if not a.pcd1:
             ap.error("--pcd2 goes with --pcd1")
@@ -158,7 +168,8 @@ def main():
     if a.json:
         print(json.dumps({"stats_columns": harness.STATS_NAMES, "stats": stats.tolist(), "summary": summ}))
         return
-    print(f"{len(cloud)} points after {a.voxel} m voxel down-sampling; {a.num_pairs} pairs" + (" (ICP post-step)" if a.use_icp else ""))
+    print(f"{len(cloud)} points after {a.voxel} m voxel down-sampling; {a.num_pairs} pairs" + (" (ICP post-step)" if a.use_icp else "") +
+          (f" (baseline {a.baseline})" if a.baseline else ""))
     print(" ".join(f"{n[:10]:>10s}" for n in harness.STATS_NAMES))
     for row in stats:
         print(" ".join(f"{v:10.4f}" for v in row))
