@@ -12,7 +12,7 @@
  *     pdsc_forward_validation; the weight packers pdsc_wpack_floats / _offset, pdsc_wsplit_bytes / _offset / _build; the workspace
  *     queries pdsc_workspace_bytes / _offset; pdsc_encoder_range_probe; pdsc_version / pdsc_last_error; and, for the callers either
  *     side of the path (SURVEY.md section 8 f-2 .. f-4), pdsc_match_* / pdsc_select_correspondences / pdsc_build_corr_pos,
- *     pdsc_sm_baseline*, pdsc_pmc_*, pdsc_cal_confidence, pdsc_eval_stats, pdsc_icp_*, pdsc_information_*, pdsc_voxel_*, pdsc_cloud_*.
+ *     pdsc_sm_baseline*, pdsc_pmc_*, pdsc_cal_confidence, pdsc_eval_stats, pdsc_*_loss*, pdsc_icp_*, pdsc_information_*, pdsc_voxel_*, pdsc_cloud_*.
  *   STAGE LEVEL -- one entry point per reference stage (sections a-1 .. a-11 below), the plan / size queries that go with them,
  *     pdsc_selftest_* and the diagnostic hooks.  The forward does not go through them (it calls the same launchers directly); they
  *     exist so that every stage can be parity-checked on its own (tests/test_gpu_parity.py), for the tools, and for a maintainer
@@ -922,6 +922,54 @@ int pdsc_profile_reset(void);
  * kernels around it; bench.py samples one attention / layer launch per forward: the launches of a kind do identical work) */
 int pdsc_profile_set_stride(int kind, int stride);
 int pdsc_profile_read(int kind, double* total_ms, int* launches);
+
+/* ---- the losses of libs/loss.py on the device, with their gradients ---------------------------
+ * What the reference's validation and training loops (libs/trainer.py:95-107,186-194) apply to the outputs of the validation
+ * forward.  Every call is asynchronous on `stream`, allocates nothing, does not synchronise and can be captured in a graph.
+ * Every call is deterministic: no floating-point atomics; workgroups write fp64 partials into `ws` and a one-workgroup finishing
+ * launch adds them in a fixed order.  Labels `gt` are 0 / 1 floats.  The per-element arithmetic and every sum are fp64 (computed
+ * from the fp32 inputs), except where pdsc_sm_loss_features says otherwise; the gradients of the fp64 losses (dpred, dM) are
+ * fp64 arrays.  All calls may share one workspace of pdsc_loss_workspace_bytes(bs, N) bytes (calls on one stream are ordered). */
+size_t pdsc_loss_workspace_bytes(int bs, int N);
+
+/* ClassificationLoss.forward (libs/loss.py:85-102).  pred, gt, weight [bs][N].
+ *   num_pos = relu(sum gt - 1) + 1, num_neg = relu(sum (1 - gt) - 1) + 1 over the whole batch;
+ *   weight != NULL: loss = mean(bce * weight); else balanced == 0: mean(bce); else mean(bce with pos_weight = num_neg / num_pos);
+ *   bce = (1 - y) x + (1 + (pos_weight - 1) y) (log1p(exp(-|x|)) + max(-x, 0)).
+ *   stats[0..7] = loss, precision, recall, F1 (pair 0 only, `pred > 0`, 0 where sklearn's zero_division applies), mean logit of the
+ *   inliers, mean logit of the outliers (whole batch, denominators max(1, count)), num_pos, num_neg.
+ *   dpred [bs][N] (fp64, or NULL) = d loss / d pred (the weights depend on gt only). */
+int pdsc_classification_loss(const float* pred, const float* gt, const float* weight, int balanced, double* stats, double* dpred,
+                             void* ws, size_t ws_bytes, int bs, int N, void* stream);
+
+/* SpectralMatchingLoss.forward (libs/loss.py:129-138) on a given M [bs][N][ld >= N], read once.
+ *   gt_M[i][j] = gt_i gt_j for i != j, 0 on the diagonal (never stored); with k = the pair's number of inliers the class sizes are
+ *   P = relu(k (k - 1) - 1) + 1 and Q = relu(N^2 - k (k - 1) - 1) + 1 (the diagonal counts as negative, as in the reference).
+ *   per pair l_b = balanced ? 0.5 sum_pos (M - 1)^2 / P + 0.5 sum_neg M^2 / Q : sum (M - gt_M)^2 / N^2;   loss[0] = mean_b l_b.
+ *   The fp64 values l_b are left in the first bs doubles of `ws`.
+ *   dM [bs][N][ld] (fp64, or NULL) = d loss / d M; only columns 0 .. N-1 of a row are written, the pad columns (ld > N) are left
+ *   as they were. */
+int pdsc_sm_loss_matrix(const float* M, long long ld, const float* gt, int balanced, double* loss, double* dM, void* ws,
+                        size_t ws_bytes, int bs, int N, void* stream);
+
+/* The same loss of M = clamp(1 - (1 - F F^T) / sigma^2, 0, 1) with a zero diagonal (models/PointDSC.py:160-163), taken from
+ * normed = F [bs*N][128] without M ever being stored.  The Gram tiles run on v_mfma_f32_32x32x2_f32 in the k order of
+ * pdsc_feature_compat and the clamp expression is the same fp32 expression, so loss[0] (and the l_b in `ws`) equal
+ * pdsc_sm_loss_matrix on the matrix pdsc_feature_compat writes, bit for bit.
+ *   dnormed [bs*N][128] (fp32, or NULL) = d loss / d F with g_ij = c_ij 2 (M_ij - gt_M_ij) [0 <= raw_ij <= 1] [i != j]
+ *   (inclusive mask: torch.clamp's backward), c_ij the loss weight: dF_i = (2 / sigma^2) sum_j g_ij F_j, a second fp32 MFMA product.
+ *   dsigma [1] (fp64, or NULL) = sum_ij g_ij 2 (1 - s_ij) / sigma^3.   Either gradient pointer may be NULL on its own. */
+int pdsc_sm_loss_features(const float* normed, const float* sigma, const float* gt, int balanced, double* loss, float* dnormed,
+                          double* dsigma, void* ws, size_t ws_bytes, int bs, int N, void* stream);
+
+/* TransformationLoss.forward (libs/loss.py:34-63), forward only.  trans, gt_trans [bs][16]; src, tgt [bs][N][3]; probs [bs][N].
+ *   out[0..4] = loss, recall [%], RE [deg], TE [cm], RMSE, each the mean over the bs pairs.
+ *   RE = acos(clamp((trace(R^T gR) - 1) / 2, -1, 1)) in degrees, TE in cm, a pair counts for the recall if TE < te_thre && RE < re_thre.
+ *   THE REFERENCE'S BROADCAST IS MIRRORED: `warp_src_keypts - tgt_keypts` subtracts pair i's warped [N][3] from the whole
+ *   [bs][N][3] target, so pair i's RMSE and squared loss are means over all bs * N rows (row (j, n): R_i src[i][n] + t_i - tgt[j][n]).
+ *   That is the definition for bs > 1; for bs == 1 it is the intended per-pair mean.  A pair with no probs > 0 adds 0 to the loss. */
+int pdsc_transformation_loss(const float* trans, const float* gt_trans, const float* src, const float* tgt, const float* probs,
+                             float re_thre, float te_thre, double* out, void* ws, size_t ws_bytes, int bs, int N, void* stream);
 
 #ifdef __cplusplus
 }

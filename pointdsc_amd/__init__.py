@@ -8,6 +8,8 @@ Only what the path needs lives here:
   ops.py       stage-level tensor wrappers (``rigid_transform_3d``, ``knn`` ...) over the C-ABI
   icp.py       the evaluation's optional ICP post-step (``icp_refine``, ``registration_icp``) on the device
   features.py  FPFH descriptors of a down-sampled cloud (neighbour lists, normals, SPFH, FPFH) on the device
+  losses.py   the reference's training / validation losses (classification, spectral matching, transformation) on the device,
+               the first two with their gradients
   multiway.py  the multiway driver's edge step (information matrix + overlap gate, voxel down-sampling, multi-scale ICP) and its
                pose-graph optimisation (node chain, LM with line process, edge pruning) on the device
   sharding.py  one-process-per-GPU sharding of pair batches + the single RCCL pose gather
@@ -16,10 +18,12 @@ Only what the path needs lives here:
 from .features import (compute_fpfh_feature, estimate_normals, extract_fpfh_features, fpfh_descriptors,  # noqa: F401
                        hybrid_neighbours, voxel_down_sample_with_normals)
 from .icp import icp_refine, registration_icp  # noqa: F401
+from .losses import ClassificationLoss, SpectralMatchingLoss, TransformationLoss  # noqa: F401
 from .model import PointDSC  # noqa: F401
 from .multiway import (align, global_optimization, information_matrix, local_refinement, loop_closure_edge,  # noqa: F401
                        multi_scale_icp, pose_graph_nodes, voxel_down_sample)
 
 __all__ = ["PointDSC", "icp_refine", "registration_icp", "information_matrix", "voxel_down_sample", "loop_closure_edge",
            "multi_scale_icp", "local_refinement", "align", "hybrid_neighbours", "estimate_normals", "compute_fpfh_feature",
-           "fpfh_descriptors", "voxel_down_sample_with_normals", "extract_fpfh_features", "pose_graph_nodes", "global_optimization"]
+           "fpfh_descriptors", "voxel_down_sample_with_normals", "extract_fpfh_features", "pose_graph_nodes", "global_optimization",
+           "ClassificationLoss", "SpectralMatchingLoss", "TransformationLoss"]

@@ -128,6 +128,11 @@ SIGNATURES = {
     "pdsc_cal_confidence_workspace_bytes": (_sz, [_i, _i]),
     "pdsc_cal_confidence": (_i, [_vp, _ll, _vp, _i, _i, _vp, _vp, _sz, _i, _i, _vp]),
     "pdsc_eval_stats": (_i, [_vp, _vp, _vp, _vp, _f, _f, _vp, _i, _i, _vp]),
+    "pdsc_loss_workspace_bytes": (_sz, [_i, _i]),
+    "pdsc_classification_loss": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _sz, _i, _i, _vp]),
+    "pdsc_sm_loss_matrix": (_i, [_vp, _ll, _vp, _i, _vp, _vp, _vp, _sz, _i, _i, _vp]),
+    "pdsc_sm_loss_features": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _sz, _i, _i, _vp]),
+    "pdsc_transformation_loss": (_i, [_vp, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp, _sz, _i, _i, _vp]),
     "pdsc_icp_workspace_bytes": (_sz, [_i, _i, _i]),
     "pdsc_icp_refine": (_i, [_vp, _vp, _vp, _vp, _vp, C.c_double, C.c_double, C.c_double, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                              _sz, _i, _i, _i, _vp]),

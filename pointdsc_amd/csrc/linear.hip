@@ -8,6 +8,7 @@
 // convention used throughout this library: k-slot (step t = 4q+e, half h = lane>>5) <-> channel 8q+4h+e,
 // so one ds_read_b128 per lane feeds 4 MFMA steps for both A and B.
 #include "pdsc_common.h"
+#include "gram_tile.h"
 #include "ragged.h"
 
 namespace pdsc {
@@ -336,16 +337,7 @@ __global__ __launch_bounds__(256, 2) void gram_rows_kernel(GramArgs a) {
         if (tile + 1 < t1) load_tile(tile + 1);                     // in flight under the MFMAs
 #pragma unroll
         for (int sub = 0; sub < GR_COLS / 32; ++sub) {
-            f32x16 acc;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-            const float* brow = cur + (32 * sub + l31) * GR_LD + 4 * h;
-#pragma unroll
-            for (int q = 0; q < 16; ++q) {
-                const f32x4 bf = *reinterpret_cast<const f32x4*>(brow + 8 * q);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(af[q][e], bf[e], acc, 0, 0, 0);
-            }
+            const f32x16 acc = gram_tile_k128<true>(af, cur + (32 * sub + l31) * GR_LD + 4 * h);      // gram_tile.h: the one k order
             const int col = tile * GR_COLS + 32 * sub + l31;
             if (col < a.N) {
 #pragma unroll
@@ -355,7 +347,7 @@ __global__ __launch_bounds__(256, 2) void gram_rows_kernel(GramArgs a) {
                         float v;
                         if (MODE == 1) v = 2.0f - 2.0f * acc[r];      // == reference `2 - 2*matmul` (one rounding)
                         else {
-                            v = fminf(fmaxf(1.0f - (1.0f - acc[r]) / sig2, 0.0f), 1.0f);
+                            v = feature_compat_clamp(feature_compat_raw(acc[r], sig2));
                             if (row == col) v = 0.0f;
                         }
                         Yb[(size_t)row * a.ldy + col] = v;

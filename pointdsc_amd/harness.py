@@ -387,3 +387,42 @@ def multiway_trajectory(model, views: List[Dict[str, np.ndarray]], use_icp: bool
     if return_graph:
         out["graph"] = {"nodes": nodes, "edges": edges, "edge_mask": mask}
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the validation loop (libs/trainer.py:158-222)
+# ---------------------------------------------------------------------------------------------------------------------------
+VALIDATE_NAMES = ("class_loss", "trans_loss", "sm_loss", "reg_recall", "re", "te", "precision", "recall", "f1")
+
+
+def validate(model, batches: Iterable[Dict[str, torch.Tensor]], balanced: bool = False, re_thre: float = 15.0,
+             te_thre: float = 30.0) -> Dict[str, float]:
+    """``Trainer.evaluate`` (libs/trainer.py:158-222) on the device: for every batch (dict with corr_pos [bs,N,in_dim], src_keypts,
+    tgt_keypts [bs,N,3], gt_trans [bs,4,4], gt_labels [bs,N]) the validation forward of `model` (eval() mode) and the three losses
+    of pointdsc_amd.losses on its outputs.  The nine meters of the reference are running means kept on the device (fp64; a NaN
+    value is skipped, as the reference's `if not np.isnan(...)` does); ONE device -> host copy at the end returns them all.
+    The spectral-matching loss is also taken straight from the forward's normalised features (workspace entry "normed") without
+    reading M; that value is returned as "sm_loss_features" and equals "sm_loss" bit for bit.
+    The reference logs ``te`` as ``float(re)`` (libs/trainer.py:203); the REAL translation error is returned here."""
+    from .losses import classification_loss_raw, sm_loss_features_raw, sm_loss_matrix_raw, transformation_loss_raw
+    dev = next(model.parameters()).device
+    names = VALIDATE_NAMES + ("sm_loss_features",)
+    sums = torch.zeros(len(names), device=dev, dtype=torch.float64)
+    counts = torch.zeros(len(names), device=dev, dtype=torch.float64)
+    with torch.no_grad():
+        for batch in batches:
+            d = {k: v.to(dev) for k, v in batch.items() if torch.is_tensor(v)}
+            res = model({k: d[k] for k in ("corr_pos", "src_keypts", "tgt_keypts")})
+            logits, gt = res["final_labels"], d["gt_labels"]
+            bs, n = logits.shape
+            cls = classification_loss_raw(logits, gt, None, balanced)[0]
+            sm = sm_loss_matrix_raw(res["M"], gt, balanced)[0]
+            normed = model.workspace_view("normed", bs, n)[: bs * n * 128].view(bs * n, 128)
+            smf = sm_loss_features_raw(normed, model.sigma, gt, balanced)[0]
+            tr = transformation_loss_raw(res["final_trans"], d["gt_trans"], d["src_keypts"], d["tgt_keypts"], logits, re_thre, te_thre)
+            vals = torch.stack([cls[0], tr[0], sm[0], tr[1], tr[2], tr[3], cls[1], cls[2], cls[3], smf[0]])
+            ok = ~torch.isnan(vals)
+            sums += torch.where(ok, vals, torch.zeros_like(vals))
+            counts += ok.to(torch.float64)
+        means = (sums / counts).cpu().tolist()          # the one read-back (a meter that never got a value is NaN)
+    return dict(zip(names, means))

@@ -105,6 +105,25 @@ def real_pair(model, cloud, a):
     print(np.array2string(T, precision=6, suppress_small=True))
 
 
+def validate(a):
+    from pointdsc_amd import synthetic
+    kw = dict(workloads.BASE_MODEL)
+    model = PointDSC(**kw)
+    if a.snapshot:
+        print(model.load_state_dict(torch.load(a.snapshot, map_location="cpu"), strict=False))
+    else:
+        model.load_state_dict(workloads.state_dict("n5000_b32", model.state_dict()))
+    model = model.eval().cuda()
+    batches = [synthetic.make_batch(16, 1000, seed=100 + 16 * i, inlier_ratio=0.3) for i in range(a.num_batches)]
+    means = harness.validate(model, batches)
+    if a.json:
+        print(json.dumps(means))
+        return
+    print(f"{a.num_batches} synthetic batches of 16 pairs x 1000 correspondences")
+    for k, v in means.items():
+        print(f"{k}: {v:.6f}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--pcd1", default=None, help="PLY file (binary LE / ascii, float xyz); default: the demo fixture")
@@ -130,8 +149,15 @@ def main():
                     "(test_multi_ate.py:159-227, :268); --use-icp adds the ICP refinement of the edges and the second optimisation")
     ap.add_argument("--baseline", choices=harness.BaselineModel.METHODS, default=None,
                     help="run this baseline of baseline_3DMatch.py in place of the model (pair loop only)")
+    ap.add_argument("--validate", action="store_true", help="the validation loop of libs/trainer.py:158-222 on the device "
+                    "(harness.validate: validation forward + the three losses) over --num-batches synthetic batches (bs 16, N 1000)")
+    ap.add_argument("--num-batches", type=int, default=4, help="with --validate: batches of 16 pairs")
     ap.add_argument("--json", action="store_true")
     a = ap.parse_args()
+    if a.validate:
+        if a.baseline or a.pcd1 or a.pcd2 or a.multiway or a.posegraph:
+            ap.error("--validate runs the model on synthetic batches: not with --baseline, --pcd1, --pcd2, --multiway or --posegraph")
+        return validate(a)
     if a.baseline and (a.pcd2 or a.multiway or a.posegraph or a.snapshot):
         ap.error("--baseline replaces the model in the pair loop: not with --pcd2, --multiway, --posegraph or --snapshot")
     if a.fpfh_recipe == "demo" and not (a.pcd1 and a.pcd2):
