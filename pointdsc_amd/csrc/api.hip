@@ -1,7 +1,8 @@
-// Host side of libpointdsc_hip.so: error plumbing, packed-weight layout, workspace layout and the
-// whole-path orchestrator pdsc_forward_testing (reference PointDSC.forward in testing mode,
-// models/PointDSC.py:128-197).  Pure HIP runtime -- no torch types cross this boundary.  Every stage is
-// enqueued on the caller's stream with no host synchronisation, so one forward is hipGraph-capturable.
+// Host side of libpointdsc_hip.so: error plumbing, packed-weight layout, workspace layout (entries by WsId) and the whole-path
+// orchestrator run_forward behind pdsc_forward_testing* / pdsc_forward_validation / pdsc_encoder_range_probe: one ForwardCall,
+// an explicit ForwardMode, one function per stage (reference PointDSC.forward, models/PointDSC.py:128-197).  Pure HIP runtime --
+// no torch types cross this boundary.  Every stage is enqueued on the caller's stream with no host synchronisation, so one
+// forward is hipGraph-capturable.
 #include <stdarg.h>
 #include <stdlib.h>
 #include <string.h>
@@ -200,72 +201,78 @@ static long long wpack_offset(const pdsc_config* c, int section, int layer) {
 }
 
 // ---- workspace layout --------------------------------------------------------------------------
-struct WsEntry { const char* name; size_t bytes; size_t offset; };
+// One id per entry, in layout order; ws_names[id] is the name pdsc_workspace_offset serves.
+enum WsId {
+    WS_COMPAT, WS_FEATA, WS_FEATB, WS_FEATC, WS_QKV, WS_MSG, WS_T64A, WS_T64B, WS_ATT_SCRATCH, WS_Q_SPLIT, WS_KV_TILES, WS_NORMED,
+    WS_NORMED_PF, WS_H1, WS_H2, WS_CONF, WS_KEYS, WS_NMS_WS, WS_SEEDS, WS_KNN_DIST, WS_KNN_IDX, WS_EIG_ITERS, WS_CONV_MASK,
+    WS_SEED_TRANS, WS_SEED_W, WS_COUNTS, WS_BEST, WS_INITIAL_TRANS, WS_SOLVES, WS_RANGE_FLAG, WS_REFINE_TRACE,
+#ifdef PDSC_EXPERIMENTS
+    WS_SCORE_DBG,
+#endif
+    WS_NUM
+};
+static const char* const ws_names[] = {
+    "compat", "featA", "featB", "featC", "qkv", "msg", "t64a", "t64b", "att_scratch", "q_split", "kv_tiles", "normed",
+    "normed_pf", "h1", "h2", "conf", "keys", "nms_ws", "seeds", "knn_dist", "knn_idx", "eig_iters", "conv_mask",
+    "seed_trans", "seed_w", "counts", "best", "initial_trans", "solves", "range_flag", "refine_trace",
+#ifdef PDSC_EXPERIMENTS
+    "score_dbg",
+#endif
+};
+static_assert(sizeof(ws_names) / sizeof(ws_names[0]) == WS_NUM, "ws_names must name every WsId, in order");
+
 struct WsLayout {
-    WsEntry e[40];
-    int n = 0;
-    size_t total = 0;
-    void add(const char* name, size_t bytes) {
-        e[n].name = name; e[n].bytes = bytes; e[n].offset = total;
-        total += (size_t)round_up((long long)bytes, 256);
-        ++n;
-    }
-    long long find(const char* name) const {
-        for (int i = 0; i < n; ++i) if (strcmp(e[i].name, name) == 0) return (long long)e[i].offset;
-        return -1;
-    }
-    size_t bytes_of(const char* name) const {
-        for (int i = 0; i < n; ++i) if (strcmp(e[i].name, name) == 0) return e[i].bytes;
-        return 0;
-    }
+    size_t offset[WS_NUM], bytes[WS_NUM], total;
+    template <class T> T* at(void* ws, WsId id) const { return (T*)((char*)ws + offset[id]); }
 };
 
 static WsLayout make_layout(const pdsc_config* c, int bs, int N, int S) {
-    WsLayout L;
+    WsLayout L{};
+    size_t* B = L.bytes;
     const size_t M = (size_t)bs * N, C = PDSC_CHANNELS, f = sizeof(float);
     const size_t ld = (size_t)pdsc_compat_ld(N);
     const int k = c->k < N - 1 ? c->k : N - 1;
     const int iters = c->num_iterations > 0 ? c->num_iterations : 1;
     const bool compat16 = c->attention_precision != PDSC_ATT_FP32 && c->compat_format == PDSC_COMPAT_U16;
-    L.add("compat", (size_t)bs * N * ld * (compat16 ? sizeof(unsigned short) : f));
-    L.add("featA", M * C * f);
+    B[WS_COMPAT] = (size_t)bs * N * ld * (compat16 ? sizeof(unsigned short) : f);
+    B[WS_FEATA] = M * C * f;
     const size_t Mpf = (size_t)bs * round_up(N, 32);          // featB / featC may be kept in point-fragment order: whole 32-row tiles per pair
-    L.add("featB", Mpf * C * f);
-    L.add("featC", Mpf * C * f);
-    L.add("qkv", M * 3 * C * f);
-    L.add("msg", M * C * f);
-    L.add("t64a", M * (C / 2) * f);
-    L.add("t64b", M * (C / 2) * f);
+    B[WS_FEATB] = B[WS_FEATC] = Mpf * C * f;
+    B[WS_QKV] = M * 3 * C * f;
+    B[WS_MSG] = M * C * f;
+    B[WS_T64A] = B[WS_T64B] = M * (C / 2) * f;
     {
         const size_t a32 = pdsc_attention_scratch_bytes(bs, N, 0), a16 = pdsc_attention_split_scratch_bytes(bs, N, 0);
         const size_t amg = c->att_leaves >= PDSC_LEAVES_CANONICAL ? pdsc_attention_leaf_scratch_bytes(bs, N, c->att_leaves) : 0;
-        L.add("att_scratch", c->attention_precision == PDSC_ATT_FP32 ? a32 : (a16 > amg ? a16 : amg));
+        B[WS_ATT_SCRATCH] = c->attention_precision == PDSC_ATT_FP32 ? a32 : (a16 > amg ? a16 : amg);
     }
-    L.add("q_split", c->attention_precision != PDSC_ATT_FP32 ? pdsc_split_q_bytes(bs, N) : 0);
-    L.add("kv_tiles", c->attention_precision != PDSC_ATT_FP32 ? pdsc_split_kv_bytes(bs, N) : 0);
-    L.add("normed", M * C * f);
-    L.add("normed_pf", knn_seeds_uses_fused(bs, N, S, k) ? Mpf * C * f : 0);      // the fused kNN's B operand (point-fragment order)
-    L.add("h1", M * 32 * f);
-    L.add("h2", M * 32 * f);
-    L.add("conf", M * f);
-    L.add("keys", M * f);
-    L.add("nms_ws", pdsc_nms_workspace_bytes(bs, N));
-    L.add("seeds", (size_t)bs * S * sizeof(int));
-    L.add("knn_dist", (size_t)bs * S * ld * f);
-    L.add("knn_idx", (size_t)bs * S * (k > 0 ? k : 1) * sizeof(int));
-    L.add("eig_iters", (size_t)bs * S * iters * PDSC_MAX_K * f);
-    L.add("conv_mask", (size_t)bs * sizeof(unsigned int));
-    L.add("seed_trans", (size_t)bs * S * 16 * f);
-    L.add("seed_w", (size_t)bs * S * (k > 0 ? k : 1) * f);
-    L.add("counts", (size_t)bs * S * sizeof(int));
-    L.add("best", (size_t)bs * sizeof(int));
-    L.add("initial_trans", (size_t)bs * 16 * f);
-    L.add("solves", (size_t)bs * sizeof(int));
-    L.add("range_flag", (size_t)bs * sizeof(unsigned int));      // fp16 range sentinel (pdsc_common.h): != 0 = pair b left the fp16 range
-    L.add("refine_trace", (size_t)bs * PDSC_REFINE_TRACE * sizeof(int));      // inlier count per refinement iteration, -1 padded (parity census)
+    B[WS_Q_SPLIT] = c->attention_precision != PDSC_ATT_FP32 ? pdsc_split_q_bytes(bs, N) : 0;
+    B[WS_KV_TILES] = c->attention_precision != PDSC_ATT_FP32 ? pdsc_split_kv_bytes(bs, N) : 0;
+    B[WS_NORMED] = M * C * f;
+    B[WS_NORMED_PF] = knn_seeds_uses_fused(bs, N, S, k) ? Mpf * C * f : 0;      // the fused kNN's B operand (point-fragment order)
+    B[WS_H1] = B[WS_H2] = M * 32 * f;
+    B[WS_CONF] = B[WS_KEYS] = M * f;
+    B[WS_NMS_WS] = pdsc_nms_workspace_bytes(bs, N);
+    B[WS_SEEDS] = (size_t)bs * S * sizeof(int);
+    B[WS_KNN_DIST] = (size_t)bs * S * ld * f;
+    B[WS_KNN_IDX] = (size_t)bs * S * (k > 0 ? k : 1) * sizeof(int);
+    B[WS_EIG_ITERS] = (size_t)bs * S * iters * PDSC_MAX_K * f;
+    B[WS_CONV_MASK] = (size_t)bs * sizeof(unsigned int);
+    B[WS_SEED_TRANS] = (size_t)bs * S * 16 * f;
+    B[WS_SEED_W] = (size_t)bs * S * (k > 0 ? k : 1) * f;
+    B[WS_COUNTS] = (size_t)bs * S * sizeof(int);
+    B[WS_BEST] = (size_t)bs * sizeof(int);
+    B[WS_INITIAL_TRANS] = (size_t)bs * 16 * f;
+    B[WS_SOLVES] = (size_t)bs * sizeof(int);
+    B[WS_RANGE_FLAG] = (size_t)bs * sizeof(unsigned int);      // fp16 range sentinel (pdsc_common.h): != 0 = pair b left the fp16 range
+    B[WS_REFINE_TRACE] = (size_t)bs * PDSC_REFINE_TRACE * sizeof(int);      // inlier count per refinement iteration, -1 padded (parity census)
 #ifdef PDSC_EXPERIMENTS
-    L.add("score_dbg", (size_t)bs * S * 16 * f);        // diagnostics of the scoring kernel (score.hip, DBG)
+    B[WS_SCORE_DBG] = (size_t)bs * S * 16 * f;        // diagnostics of the scoring kernel (score.hip, DBG)
 #endif
+    for (int i = 0; i < WS_NUM; ++i) {        // entries follow one another in id order, each rounded up to 256 bytes
+        L.offset[i] = L.total;
+        L.total += (size_t)round_up((long long)B[i], 256);
+    }
     return L;
 }
 
@@ -313,7 +320,10 @@ extern "C" size_t pdsc_workspace_bytes(const pdsc_config* cfg, int bs, int N, in
 }
 extern "C" long long pdsc_workspace_offset(const pdsc_config* cfg, int bs, int N, int num_seeds, const char* name) {
     if (!config_ok(cfg) || bs <= 0 || N <= 1 || num_seeds <= 0 || !name) return -1;
-    return make_layout(cfg, bs, N, num_seeds).find(name);
+    const WsLayout L = make_layout(cfg, bs, N, num_seeds);
+    for (int i = 0; i < WS_NUM; ++i)
+        if (strcmp(ws_names[i], name) == 0) return (long long)L.offset[i];
+    return -1;
 }
 
 extern "C" int pdsc_profile_enable(int max_records) {
@@ -404,7 +414,7 @@ static int plan_encoder(const pdsc_config* cfg, int bs, int N, const int* nvalid
         return force_block || (!force_wave && pdsc_layer_prefers_block(pairs, rows)) ? LayerKernel::Block : LayerKernel::Wave;
     };
     if (!p.fused || !p.split) {
-        // exact fp32 sees the batch as ONE run of bs * N independent rows (see run_forward)
+        // exact fp32 sees the batch as ONE run of bs * N independent rows (see run_fused_layer)
         p.kernel = by_size(1, bs * N);
         return PDSC_OK;
     }
@@ -449,249 +459,346 @@ static int plan_encoder(const pdsc_config* cfg, int bs, int N, const int* nvalid
     return PDSC_OK;
 }
 
-// mode 0 = testing forward; mode 1 = validation forward (no 'testing' key, module in eval mode): feature similarity
-// matrix M, seeds = top-S by confidence (no NMS), batch-wide power-iteration exit, no refinement, labels = logits
-// nvalid / svalid (device, [bs]) != NULL: ragged batch (ragged.h) -- N and num_seeds are then those of the longest pair,
-// n_min the shortest pair's count (host copy: the attention's key split must leave every pair at least one tile per split).
-static int run_forward(int mode, const pdsc_config* cfg, const float* wpack, const void* wsplit, const float* corr_pos,
-                       const float* src, const float* tgt, int bs, int N, int num_seeds,
-                       float* final_trans, float* final_labels, float* Mout, long long ldM, void* workspace,
-                       size_t workspace_bytes, void* stream, const int* nvalid = nullptr, const int* svalid = nullptr, int n_min = 0,
-                       void* tail_stream = nullptr, void* ev_fork = nullptr, void* ev_join = nullptr, unsigned int* probe = nullptr) {
-    if (!config_ok(cfg)) return PDSC_ERR_ARG;
-    PDSC_REQUIRE(!tail_stream || (ev_fork && ev_join && tail_stream != stream),
+// Testing = the reference's testing forward.  Validation (no 'testing' key, module in eval mode): feature similarity matrix M,
+// seeds = top-S by confidence (no NMS), batch-wide power-iteration exit, no refinement, labels = logits.  Probe
+// (pdsc_encoder_range_probe): the encoder alone, one launch per conv, |max| of each activation kind; no pose, no labels.
+enum class ForwardMode { Testing, Validation, Probe };
+
+// One whole-path call, as the extern "C" entry points fill it in (zero / NULL = absent).
+struct ForwardCall {
+    ForwardMode mode;
+    const pdsc_config* cfg;
+    const float* wpack;
+    const void* wsplit;
+    const float *corr_pos, *src, *tgt;
+    int bs, N, num_seeds;
+    float *final_trans, *final_labels, *Mout;      // Mout [bs][N][ldM]: Validation only; the probe writes none of the three
+    long long ldM;
+    void* workspace;
+    size_t workspace_bytes;
+    void* stream;
+    // ragged batch (ragged.h): device [bs] counts -- N and num_seeds are then those of the longest pair, n_min the shortest pair's
+    // count (host copy: the attention's key split must leave every pair at least one tile per split)
+    const int *nvalid, *svalid;
+    int n_min;
+    void *tail_stream, *ev_fork, *ev_join;      // pdsc_forward_testing_streams
+    unsigned int* probe;                        // Probe: [PDSC_RANGE_NUM_KINDS] |max| bit patterns (device)
+};
+
+// The call plus what is derived from it once: encoder plan, workspace layout, the buffers more than one stage uses, a few scalars.
+struct ForwardCtx {
+    const ForwardCall& c;
+    EncoderPlan plan;
+    WsLayout L;
+    hipStream_t st;      // where the next launch goes: the caller's stream, after fork_tail the tail stream
+    int M, S, k, cfmt;   // cfmt: enum pdsc_compat_format of the compat buffer
+    long long ld;
+    bool split;
+    float *compat, *featA, *featB, *featC, *qkv, *msg, *normed, *normed_pf, *conf, *keys, *seed_trans;
+    int *seeds, *knn_idx, *counts;
+    unsigned int *conv_mask, *range_flag;
+    void *att_scratch, *q_split, *kv_tiles;
+    const float* W(int section, int layer) const { return c.wpack + wpack_offset(c.cfg, section, layer); }
+    const void* WS(int section, int layer) const { return (const unsigned short*)c.wsplit + pdsc_wsplit_offset(c.cfg, section, layer); }
+};
+
+static int validate_call(const ForwardCall& c) {
+    if (!config_ok(c.cfg)) return PDSC_ERR_ARG;
+    PDSC_REQUIRE(!c.tail_stream || (c.ev_fork && c.ev_join && c.tail_stream != c.stream),
                  "pdsc_forward_testing_streams: a tail stream (different from the main stream) needs the fork and join events");
-    hipStream_t hst = (hipStream_t)stream;
-    if (nvalid) {
-        PDSC_REQUIRE(mode == 0 && svalid, "pdsc_forward_testing_ragged: testing forward only, both count arrays needed");
+    const int N = c.N, n_min = c.n_min, k = c.cfg->k < N - 1 ? c.cfg->k : N - 1;
+    if (c.nvalid) {
+        PDSC_REQUIRE(c.mode == ForwardMode::Testing && c.svalid, "pdsc_forward_testing_ragged: testing forward only, both count arrays needed");
         PDSC_REQUIRE(n_min >= 2 && n_min <= N, "pdsc_forward_testing_ragged: n_min=%d (N=%d)", n_min, N);
         // one launch has one neighbour count k = min(cfg->k, N - 1); the reference clamps per pair, k_b = min(k, num_corr_b - 1)
         // (models/PointDSC.py:250): a pair with fewer than k + 1 correspondences must be its own call
-        PDSC_REQUIRE(n_min > (cfg->k < N - 1 ? cfg->k : N - 1), "pdsc_forward_testing_ragged: the shortest pair (%d correspondences) has no "
-                     "more than k=%d: the reference clamps k per pair (k = min(k, num_corr - 1)); run such a pair in its own call",
-                     n_min, cfg->k < N - 1 ? cfg->k : N - 1);
+        PDSC_REQUIRE(n_min > k, "pdsc_forward_testing_ragged: the shortest pair (%d correspondences) has no "
+                     "more than k=%d: the reference clamps k per pair (k = min(k, num_corr - 1)); run such a pair in its own call", n_min, k);
     }
-    PDSC_REQUIRE(wpack && corr_pos && src && tgt && final_trans && final_labels && workspace,
-                 "pdsc_forward_testing: null pointer");
-    PDSC_REQUIRE(bs > 0 && N > 1, "pdsc_forward_testing: bs=%d N=%d", bs, N);
-    PDSC_REQUIRE(num_seeds >= 1 && num_seeds <= N,
-                 "pdsc_forward_testing: num_seeds=%d (int(N*ratio) must be >= 1; the reference fails on an empty seed set)",
-                 num_seeds);
-    EncoderPlan plan;
-    PDSC_TRY(plan_encoder(cfg, bs, N, nvalid, n_min, &plan));
-    const WsLayout L = make_layout(cfg, bs, N, num_seeds);
-    if (workspace_bytes < L.total) {
-        set_error("pdsc_forward_testing: workspace %zu < %zu bytes", workspace_bytes, L.total);
+    const bool outputs = c.mode == ForwardMode::Probe || (c.final_trans && c.final_labels);
+    PDSC_REQUIRE(c.wpack && c.corr_pos && c.src && c.tgt && outputs && c.workspace, "pdsc_forward_testing: null pointer");
+    PDSC_REQUIRE(c.bs > 0 && N > 1, "pdsc_forward_testing: bs=%d N=%d", c.bs, N);
+    PDSC_REQUIRE(c.num_seeds >= 1 && c.num_seeds <= N,
+                 "pdsc_forward_testing: num_seeds=%d (int(N*ratio) must be >= 1; the reference fails on an empty seed set)", c.num_seeds);
+    return PDSC_OK;
+}
+
+// layout, workspace size check, shared buffers and derived scalars (x.c and x.plan are set)
+static int bind_workspace(ForwardCtx& x) {
+    const ForwardCall& c = x.c;
+    const WsLayout& L = x.L = make_layout(c.cfg, c.bs, c.N, c.num_seeds);
+    if (c.workspace_bytes < L.total) {
+        set_error("pdsc_forward_testing: workspace %zu < %zu bytes", c.workspace_bytes, L.total);
         return PDSC_ERR_WORKSPACE;
     }
-    char* ws = (char*)workspace;
-    auto F = [&](const char* n) { return (float*)(ws + L.find(n)); };
-    auto I = [&](const char* n) { return (int*)(ws + L.find(n)); };
-    auto W = [&](int section, int layer) { return wpack + wpack_offset(cfg, section, layer); };
-
-    const int C = PDSC_CHANNELS, M = bs * N, S = num_seeds;
-    const int k = cfg->k < N - 1 ? cfg->k : N - 1;
-    const long long ld = pdsc_compat_ld(N);
-    float *compat = F("compat"), *featA = F("featA"), *featB = F("featB"), *featC = F("featC"), *qkv = F("qkv"), *msg = F("msg");
-    float *t64a = F("t64a"), *t64b = F("t64b"), *normed = F("normed"), *h1 = F("h1"), *h2 = F("h2");
-    float *conf = F("conf"), *keys = F("keys"), *knn_dist = F("knn_dist"), *eig = F("eig_iters");
-    float *seed_trans = F("seed_trans"), *seed_w = F("seed_w"), *initial = F("initial_trans");
-    int *seeds = I("seeds"), *knn_idx = I("knn_idx"), *counts = I("counts"), *best = I("best"), *solves = I("solves");
-    unsigned int* conv_mask = (unsigned int*)(ws + L.find("conv_mask"));
-    void* att_scratch = ws + L.find("att_scratch");
-    const bool split = plan.split;
-    PDSC_REQUIRE(!split || wsplit, "pdsc_forward_testing: the split-precision modes need the split-weight buffer (pdsc_wsplit_build)");
-    auto WS = [&](int section, int layer) { return (const void*)((const unsigned short*)wsplit + pdsc_wsplit_offset(cfg, section, layer)); };
-    const size_t att_bytes = L.bytes_of("att_scratch");
-    void* q_split = split ? ws + L.find("q_split") : nullptr;
-    void* kv_tiles = split ? ws + L.find("kv_tiles") : nullptr;
+    void* ws = c.workspace;
+    x.st = (hipStream_t)c.stream;
+    x.M = c.bs * c.N; x.S = c.num_seeds; x.k = c.cfg->k < c.N - 1 ? c.cfg->k : c.N - 1;
+    x.ld = pdsc_compat_ld(c.N);
+    x.compat = L.at<float>(ws, WS_COMPAT); x.featA = L.at<float>(ws, WS_FEATA); x.featB = L.at<float>(ws, WS_FEATB);
+    x.featC = L.at<float>(ws, WS_FEATC); x.qkv = L.at<float>(ws, WS_QKV); x.msg = L.at<float>(ws, WS_MSG);
+    x.normed = L.at<float>(ws, WS_NORMED); x.conf = L.at<float>(ws, WS_CONF); x.keys = L.at<float>(ws, WS_KEYS);
+    x.seed_trans = L.at<float>(ws, WS_SEED_TRANS); x.seeds = L.at<int>(ws, WS_SEEDS); x.knn_idx = L.at<int>(ws, WS_KNN_IDX);
+    x.counts = L.at<int>(ws, WS_COUNTS); x.conv_mask = L.at<unsigned int>(ws, WS_CONV_MASK); x.att_scratch = L.at<void>(ws, WS_ATT_SCRATCH);
+    const bool split = x.split = x.plan.split;
+    PDSC_REQUIRE(!split || c.wsplit, "pdsc_forward_testing: the split-precision modes need the split-weight buffer (pdsc_wsplit_build)");
+    x.q_split = split ? L.at<void>(ws, WS_Q_SPLIT) : nullptr;
+    x.kv_tiles = split ? L.at<void>(ws, WS_KV_TILES) : nullptr;
     // fp16 range sentinel: zeroed by the layer0 launch, set by the layer kernels' conversion sites (LayerArgs.range_flag), read by
     // the refinement launch
-    unsigned int* range_flag = split && !probe ? (unsigned int*)(ws + L.find("range_flag")) : nullptr;
+    x.range_flag = split && c.mode != ForwardMode::Probe ? L.at<unsigned int>(ws, WS_RANGE_FLAG) : nullptr;
+    x.cfmt = split && c.cfg->compat_format == PDSC_COMPAT_U16 ? PDSC_COMPAT_U16 : PDSC_COMPAT_F32;
+    // (testing forward, large batches: the seeds' kNN runs fused -- knn_fused_kernel -- and takes the normalised rows in
+    // point-fragment order too; normed_pf != NULL says so)
+    const bool knn_fused = c.mode == ForwardMode::Testing && knn_seeds_uses_fused(c.bs, c.N, x.S, x.k);
+    x.normed_pf = knn_fused ? L.at<float>(ws, WS_NORMED_PF) : nullptr;
+    return PDSC_OK;
+}
 
-    // Step 1 (models/PointDSC.py:150-155): compat, then the SCNonlocal encoder
-    const bool compat16 = split && cfg->compat_format == PDSC_COMPAT_U16;
-    if (compat16)
-        PDSC_TRY(pdsc_spatial_compat_u16(src, tgt, W(PDSC_W_SIGMA_SPAT, 0), (unsigned short*)compat, ld, bs, N, stream));
+// Probe: slot[kind] := max(slot[kind], max |v|); every other mode: nothing
+static int probe_absmax(const ForwardCtx& x, int kind, const float* v, size_t count) {
+    return x.c.probe ? launch_absmax(v, count, x.c.probe + kind, x.st) : PDSC_OK;
+}
+
+// Step 1 (models/PointDSC.py:150-155): compat, then layer0 of the SCNonlocal encoder
+static int run_compat_layer0(const ForwardCtx& x) {
+    const ForwardCall& c = x.c;
+    if (x.cfmt == PDSC_COMPAT_U16)
+        PDSC_TRY(pdsc_spatial_compat_u16(c.src, c.tgt, x.W(PDSC_W_SIGMA_SPAT, 0), (unsigned short*)x.compat, x.ld, c.bs, c.N, x.st));
     else
-        PDSC_TRY(pdsc_spatial_compat(src, tgt, W(PDSC_W_SIGMA_SPAT, 0), compat, nullptr, ld, bs, N, stream));
-    auto attention_split = [&](float* msg_out, int nsplit) {
-        return launch_attention_split_ex(q_split, kv_tiles, compat, compat16 ? PDSC_COMPAT_U16 : PDSC_COMPAT_F32, ld, msg_out, att_scratch,
-                                         att_bytes, bs, N, nsplit, PDSC_PARTIALS_ROWS, nvalid, hst);
-    };
-    PDSC_TRY(launch_layer0(corr_pos, cfg->in_dim, W(PDSC_W_LAYER0_W, 0), W(PDSC_W_LAYER0_B, 0), featA, M, range_flag, bs, hst));
-    // probe != NULL (pdsc_encoder_range_probe): one launch per conv, every intermediate in the workspace, |max| of each kind recorded
-    auto P = [&](int kind, const float* x, size_t count) { return probe ? launch_absmax(x, count, probe + kind, hst) : PDSC_OK; };
-    PDSC_TRY(P(PDSC_RANGE_LAYER0, featA, (size_t)M * C));
-    if (plan.fused && !probe) {
-        // head of layer 0, then per layer: attention + ONE launch for the merge of the key-split partials (when they are left
-        // un-merged), the tail of layer i and the head of layer i+1
-        const bool parts = plan.pf || plan.fuse_merge;
-        const int nparts = plan.leaves ? plan.nleaf : plan.ns;
-        const float* part_o = parts ? (const float*)att_scratch : nullptr;
-        const float* part_ml = parts ? part_o + (size_t)bs * nparts * plan.Npad * plan.value_width : nullptr;
-        // tail of layer i (i = -1: none, the input is featA) and head of layer i+1 (last: none, the result is featA)
-        auto layer = [&](int i, bool last, const float* cur, float* nxt) -> int {
-            const bool tail = i >= 0, head = !last;
-            pdsc_layer_call c{};
-            // exact fp32: the batch is ONE run of M independent rows (bs = 1, N = M), so the per-pair counts of a ragged batch do
-            // not describe it (with them the kernel took counts[0] for the row count of the whole batch).  Padding rows are computed
-            // like any row; nothing valid reads them.
-            c.bs = split ? bs : 1; c.N = split ? N : M;
-            if (tail) {
-                c.msg = parts ? nullptr : msg;
-                c.part_o = part_o; c.part_ml = part_ml; c.nsplit = nparts; c.Npad = plan.Npad;
-                c.res = cur;
-            } else
-                c.feat_in = featA;
-            if (last) c.feat_out = featA;
-            if (head) {
-                c.featB_out = nxt; c.qkv_out = split ? nullptr : qkv;
-                c.q_split = q_split; c.kv_tiles = kv_tiles;
-            }
-            if (plan.frag) {
-                if (tail) c.wfrag_tail = WS(plan.ws_tail, i);
-                if (head) c.wfrag_head = WS(plan.ws_head, i + 1);
-                c.gemm_format = plan.gemm;
-            } else {
-                // natural layout; x3 (experiments builds: layer_split.hip): the hi|lo matrices of the split-weight buffer instead
-                auto mat = [&](int section, int l) { return plan.x3 ? WS(section, l) : (const void*)W(section, l); };
-                if (tail) {
-                    c.w1 = mat(PDSC_W_FC1_W, i); c.b1 = W(PDSC_W_FC1_B, i); c.w2 = mat(PDSC_W_FC2_W, i); c.b2 = W(PDSC_W_FC2_B, i);
-                    c.w3 = mat(PDSC_W_FC3_W, i); c.b3 = W(PDSC_W_FC3_B, i);
-                }
-                if (head) {
-                    c.wp = mat(PDSC_W_PCN_W, i + 1); c.bp = W(PDSC_W_PCN_B, i + 1); c.wq = mat(PDSC_W_QKV_W, i + 1); c.bq = W(PDSC_W_QKV_B, i + 1);
-                    if (split) c.wq_split = WS(PDSC_W_QKV_W, i + 1);
-                }
-            }
-            if (plan.pf) c.io_flags = (tail ? PDSC_IO_PARTIALS_PF | PDSC_IO_RES_PF : 0) | (head ? PDSC_IO_FEATB_PF : 0);
-            // the forward's own fields: the point-fragment route reports to the range sentinel and takes no trace (layer_args.h)
-            LayerArgs a = layer_args_from_call(c);
-            a.nvalid = split ? nvalid : nullptr;
-            if (plan.pf) {
-                a.value_fold = plan.fold;
-                a.range_flag = range_flag;
-            } else
-                a.trace = pdsc_layer_trace_buffer();      // range_flag stays NULL here: wiring these routes is a follow-up of its own
-            PDSC_TRY(validate_layer_args(a, plan.kernel, "pdsc_forward_testing(layer)"));
-            return dispatch_layer(a, plan.kernel, hst);
-        };
-        const int cfmt = compat16 ? PDSC_COMPAT_U16 : PDSC_COMPAT_F32;
-        PDSC_TRY(layer(-1, false, nullptr, featB));
-        float *cur = featB, *nxt = featC;
-        for (int i = 0; i < cfg->num_layers; ++i) {
-            if (!split)
-                PDSC_TRY(launch_attention_fp32(qkv, compat, ld, msg, att_scratch, att_bytes, bs, N, 0, nvalid, hst));      // (r06: ragged batches too)
-            else if (plan.leaves)
-                PDSC_TRY(launch_attention_leaves(q_split, kv_tiles, compat, cfmt, ld, att_scratch, att_bytes, bs, N, cfg->att_leaves, nvalid,
-                                                 n_min, hst, plan.value_width));
-            else if (plan.pf)
-                PDSC_TRY(launch_attention_split_ex(q_split, kv_tiles, compat, cfmt, ld, nullptr, att_scratch, att_bytes, bs, N, plan.ns,
-                                                   PDSC_PARTIALS_PF, nvalid, hst, plan.value_width));
-            else
-                PDSC_TRY(attention_split(plan.fuse_merge ? nullptr : msg, plan.ns));
-            PDSC_TRY(layer(i, i + 1 == cfg->num_layers, cur, nxt));
-            float* tmp = cur; cur = nxt; nxt = tmp;
-        }
+        PDSC_TRY(pdsc_spatial_compat(c.src, c.tgt, x.W(PDSC_W_SIGMA_SPAT, 0), x.compat, nullptr, x.ld, c.bs, c.N, x.st));
+    PDSC_TRY(launch_layer0(c.corr_pos, c.cfg->in_dim, x.W(PDSC_W_LAYER0_W, 0), x.W(PDSC_W_LAYER0_B, 0), x.featA, x.M, x.range_flag, c.bs, x.st));
+    return probe_absmax(x, PDSC_RANGE_LAYER0, x.featA, (size_t)x.M * PDSC_CHANNELS);
+}
+
+// the row-order split attention: merged rows in msg_out, or (msg_out == NULL) the key-split partials left in att_scratch
+static int attention_split(const ForwardCtx& x, float* msg_out, int nsplit) {
+    return launch_attention_split_ex(x.q_split, x.kv_tiles, x.compat, x.cfmt, x.ld, msg_out, x.att_scratch, x.L.bytes[WS_ATT_SCRATCH], x.c.bs,
+                                     x.c.N, nsplit, PDSC_PARTIALS_ROWS, x.c.nvalid, x.st);
+}
+
+// One fused launch: the tail of layer i (i = -1: none, the input is featA) and the head of layer i+1 (last: none, the result is
+// featA); cur = the residual input of the tail, nxt = where the head leaves featB.
+static int run_fused_layer(const ForwardCtx& x, int i, bool last, const float* cur, float* nxt) {
+    const EncoderPlan& plan = x.plan;
+    const bool tail = i >= 0, head = !last, split = x.split;
+    // the attention's partials (leaves or key splits), when the layer kernel merges them itself
+    const bool parts = plan.pf || plan.fuse_merge;
+    const int nparts = plan.leaves ? plan.nleaf : plan.ns;
+    const float* part_o = parts ? (const float*)x.att_scratch : nullptr;
+    const float* part_ml = parts ? part_o + (size_t)x.c.bs * nparts * plan.Npad * plan.value_width : nullptr;
+    pdsc_layer_call c{};
+    // exact fp32: the batch is ONE run of M independent rows (bs = 1, N = M), so the per-pair counts of a ragged batch do
+    // not describe it (with them the kernel took counts[0] for the row count of the whole batch).  Padding rows are computed
+    // like any row; nothing valid reads them.
+    c.bs = split ? x.c.bs : 1; c.N = split ? x.c.N : x.M;
+    if (tail) {
+        c.msg = parts ? nullptr : x.msg;
+        c.part_o = part_o; c.part_ml = part_ml; c.nsplit = nparts; c.Npad = plan.Npad;
+        c.res = cur;
     } else
-    for (int i = 0; i < cfg->num_layers; ++i) {
-        PDSC_TRY(pdsc_linear(featA, C, W(PDSC_W_PCN_W, i), W(PDSC_W_PCN_B, i), nullptr, 0, featB, C, M, C, C, 1, stream));
-        PDSC_TRY(P(PDSC_RANGE_POINTCN, featB, (size_t)M * C));
-        PDSC_TRY(pdsc_linear(featB, C, W(PDSC_W_QKV_W, i), W(PDSC_W_QKV_B, i), nullptr, 0, qkv, 3 * C, M, C, 3 * C, 0, stream));
-        PDSC_TRY(P(PDSC_RANGE_QKV, qkv, (size_t)M * 3 * C));
-        if (split) {
-            PDSC_TRY(pdsc_pack_qkv_split(qkv, q_split, kv_tiles, bs, N, stream));
-            PDSC_TRY(attention_split(msg, 0));
-        } else
-            PDSC_TRY(pdsc_sc_attention(qkv, compat, ld, msg, att_scratch, att_bytes, bs, N, 0, stream));
-        PDSC_TRY(P(PDSC_RANGE_MESSAGE, msg, (size_t)M * C));
-        PDSC_TRY(pdsc_linear(msg, C, W(PDSC_W_FC1_W, i), W(PDSC_W_FC1_B, i), nullptr, 0, t64a, C / 2, M, C, C / 2, 1, stream));
-        PDSC_TRY(P(PDSC_RANGE_FC1, t64a, (size_t)M * (C / 2)));
-        PDSC_TRY(pdsc_linear(t64a, C / 2, W(PDSC_W_FC2_W, i), W(PDSC_W_FC2_B, i), nullptr, 0, t64b, C / 2, M, C / 2, C / 2, 1, stream));
-        PDSC_TRY(P(PDSC_RANGE_FC2, t64b, (size_t)M * (C / 2)));
-        PDSC_TRY(pdsc_linear(t64b, C / 2, W(PDSC_W_FC3_W, i), W(PDSC_W_FC3_B, i), featB, C, featA, C, M, C / 2, C, 0, stream));
-        PDSC_TRY(P(PDSC_RANGE_FEATURE, featA, (size_t)M * C));
+        c.feat_in = x.featA;
+    if (last) c.feat_out = x.featA;
+    if (head) {
+        c.featB_out = nxt; c.qkv_out = split ? nullptr : x.qkv;
+        c.q_split = x.q_split; c.kv_tiles = x.kv_tiles;
     }
-    if (probe) return PDSC_OK;
-    // pdsc_forward_testing_streams: everything after the encoder -- a strictly sequential chain of ~15 small, latency-bound
-    // launches -- goes to the caller's second (high-priority) stream: with several forwards in flight its workgroups are then
-    // dispatched ahead of the queued workgroups of another forward's attention launch instead of behind them.
-    void* const main_stream = stream;
-    if (tail_stream) {
-        if (hipEventRecord((hipEvent_t)ev_fork, (hipStream_t)main_stream) != hipSuccess ||
-            hipStreamWaitEvent((hipStream_t)tail_stream, (hipEvent_t)ev_fork, 0) != hipSuccess)
-            return check_launch("pdsc_forward_testing_streams(fork)");
-        stream = tail_stream;
-        hst = (hipStream_t)tail_stream;
-    }
-    // Step 2.1 (:156,:171,:174): normalise, confidence head, NMS seeds
-    if (env_int("PDSC_CLS_FUSED", 1))       // (A/B knob, experiments builds: 0 = the two pdsc_linear launches of r01-r03; same bits)
-        PDSC_TRY(launch_classifier_hidden(featA, W(PDSC_W_CLS1_W, 0), W(PDSC_W_CLS1_B, 0), W(PDSC_W_CLS2_W, 0), W(PDSC_W_CLS2_B, 0), h2, M, hst));
-    else {
-        PDSC_TRY(pdsc_linear(featA, C, W(PDSC_W_CLS1_W, 0), W(PDSC_W_CLS1_B, 0), nullptr, 0, h1, 32, M, C, 32, 1, stream));
-        PDSC_TRY(pdsc_linear(h1, 32, W(PDSC_W_CLS2_W, 0), W(PDSC_W_CLS2_B, 0), nullptr, 0, h2, 32, M, 32, 32, 1, stream));
-    }
-    // (mode 0, large batches: the seeds' kNN runs fused -- knn_fused_kernel -- and takes the normalised rows in point-fragment order too)
-    const bool knn_fused = mode == 0 && knn_seeds_uses_fused(bs, N, S, k);
-    float* normed_pf = knn_fused ? F("normed_pf") : nullptr;
-    if (knn_fused)
-        PDSC_TRY(launch_normalize_conf_pf(featA, h2, W(PDSC_W_CLS3_W, 0), W(PDSC_W_CLS3_B, 0), normed, normed_pf, conf, bs, N, hst));
-    else
-        PDSC_TRY(pdsc_normalize_confidence(featA, h2, W(PDSC_W_CLS3_W, 0), W(PDSC_W_CLS3_B, 0), normed, conf, M, stream));
-    if (mode == 0) {
-        PDSC_TRY(launch_nms_keys_grid(src, conf, cfg->nms_radius, keys, ws + L.find("nms_ws"), pdsc_nms_workspace_bytes(bs, N), bs, N, nvalid, hst));
-        PDSC_TRY(launch_rank_select(keys, seeds, bs, N, S, nvalid, svalid, hst, conv_mask));      // (+ the solver's mask := all-ones)
+    if (plan.frag) {
+        if (tail) c.wfrag_tail = x.WS(plan.ws_tail, i);
+        if (head) c.wfrag_head = x.WS(plan.ws_head, i + 1);
+        c.gemm_format = plan.gemm;
     } else {
-        // models/PointDSC.py:158-163 and :176
-        PDSC_TRY(pdsc_feature_compat(normed, W(PDSC_W_SIGMA, 0), Mout, ldM, bs, N, stream));
-        PDSC_TRY(pdsc_rank_select(conf, seeds, bs, N, S, stream));
+        // natural layout; x3 (experiments builds: layer_split.hip): the hi|lo matrices of the split-weight buffer instead
+        auto mat = [&](int section, int l) { return plan.x3 ? x.WS(section, l) : (const void*)x.W(section, l); };
+        if (tail) {
+            c.w1 = mat(PDSC_W_FC1_W, i); c.b1 = x.W(PDSC_W_FC1_B, i); c.w2 = mat(PDSC_W_FC2_W, i); c.b2 = x.W(PDSC_W_FC2_B, i);
+            c.w3 = mat(PDSC_W_FC3_W, i); c.b3 = x.W(PDSC_W_FC3_B, i);
+        }
+        if (head) {
+            c.wp = mat(PDSC_W_PCN_W, i + 1); c.bp = x.W(PDSC_W_PCN_B, i + 1); c.wq = mat(PDSC_W_QKV_W, i + 1); c.bq = x.W(PDSC_W_QKV_B, i + 1);
+            if (split) c.wq_split = x.WS(PDSC_W_QKV_W, i + 1);
+        }
     }
-    // Step 3 & 4 (:182 -> :234-336): per-seed hypotheses, scoring, best
-    PDSC_TRY(launch_knn_seeds_form(normed, normed_pf, seeds, knn_dist, knn_idx, bs, N, S, k, nvalid, knn_fused ? 2 : 1, hst));
-    if (mode == 1 && bs > 1) {
+    if (plan.pf) c.io_flags = (tail ? PDSC_IO_PARTIALS_PF | PDSC_IO_RES_PF : 0) | (head ? PDSC_IO_FEATB_PF : 0);
+    // the forward's own fields: the point-fragment route reports to the range sentinel and takes no trace (layer_args.h)
+    LayerArgs a = layer_args_from_call(c);
+    a.nvalid = split ? x.c.nvalid : nullptr;
+    if (plan.pf) {
+        a.value_fold = plan.fold;
+        a.range_flag = x.range_flag;
+    } else
+        a.trace = pdsc_layer_trace_buffer();      // range_flag stays NULL here: wiring these routes is a follow-up of its own
+    PDSC_TRY(validate_layer_args(a, plan.kernel, "pdsc_forward_testing(layer)"));
+    return dispatch_layer(a, plan.kernel, x.st);
+}
+
+// head of layer 0, then per layer: attention + ONE launch for the merge of the key-split partials (when they are left
+// un-merged), the tail of layer i and the head of layer i+1
+static int run_encoder_fused(const ForwardCtx& x) {
+    const ForwardCall& c = x.c;
+    const EncoderPlan& plan = x.plan;
+    const size_t att_bytes = x.L.bytes[WS_ATT_SCRATCH];
+    PDSC_TRY(run_fused_layer(x, -1, false, nullptr, x.featB));
+    float *cur = x.featB, *nxt = x.featC;
+    for (int i = 0; i < c.cfg->num_layers; ++i) {
+        if (!x.split)
+            PDSC_TRY(launch_attention_fp32(x.qkv, x.compat, x.ld, x.msg, x.att_scratch, att_bytes, c.bs, c.N, 0, c.nvalid, x.st));      // (r06: ragged batches too)
+        else if (plan.leaves)
+            PDSC_TRY(launch_attention_leaves(x.q_split, x.kv_tiles, x.compat, x.cfmt, x.ld, x.att_scratch, att_bytes, c.bs, c.N,
+                                             c.cfg->att_leaves, c.nvalid, c.n_min, x.st, plan.value_width));
+        else if (plan.pf)
+            PDSC_TRY(launch_attention_split_ex(x.q_split, x.kv_tiles, x.compat, x.cfmt, x.ld, nullptr, x.att_scratch, att_bytes, c.bs, c.N,
+                                               plan.ns, PDSC_PARTIALS_PF, c.nvalid, x.st, plan.value_width));
+        else
+            PDSC_TRY(attention_split(x, plan.fuse_merge ? nullptr : x.msg, plan.ns));
+        PDSC_TRY(run_fused_layer(x, i, i + 1 == c.cfg->num_layers, cur, nxt));
+        float* tmp = cur; cur = nxt; nxt = tmp;
+    }
+    return PDSC_OK;
+}
+
+// One launch per conv, every intermediate in the workspace: the probe (which records |max| of each kind), num_layers == 0 and
+// the tuning knob PDSC_FUSED_LAYERS = 0
+static int run_encoder_per_conv(const ForwardCtx& x) {
+    const int C = PDSC_CHANNELS, H = C / 2, M = x.M;
+    float *t64a = x.L.at<float>(x.c.workspace, WS_T64A), *t64b = x.L.at<float>(x.c.workspace, WS_T64B);
+    for (int i = 0; i < x.c.cfg->num_layers; ++i) {
+        PDSC_TRY(pdsc_linear(x.featA, C, x.W(PDSC_W_PCN_W, i), x.W(PDSC_W_PCN_B, i), nullptr, 0, x.featB, C, M, C, C, 1, x.st));
+        PDSC_TRY(probe_absmax(x, PDSC_RANGE_POINTCN, x.featB, (size_t)M * C));
+        PDSC_TRY(pdsc_linear(x.featB, C, x.W(PDSC_W_QKV_W, i), x.W(PDSC_W_QKV_B, i), nullptr, 0, x.qkv, 3 * C, M, C, 3 * C, 0, x.st));
+        PDSC_TRY(probe_absmax(x, PDSC_RANGE_QKV, x.qkv, (size_t)M * 3 * C));
+        if (x.split) {
+            PDSC_TRY(pdsc_pack_qkv_split(x.qkv, x.q_split, x.kv_tiles, x.c.bs, x.c.N, x.st));
+            PDSC_TRY(attention_split(x, x.msg, 0));
+        } else
+            PDSC_TRY(pdsc_sc_attention(x.qkv, x.compat, x.ld, x.msg, x.att_scratch, x.L.bytes[WS_ATT_SCRATCH], x.c.bs, x.c.N, 0, x.st));
+        PDSC_TRY(probe_absmax(x, PDSC_RANGE_MESSAGE, x.msg, (size_t)M * C));
+        PDSC_TRY(pdsc_linear(x.msg, C, x.W(PDSC_W_FC1_W, i), x.W(PDSC_W_FC1_B, i), nullptr, 0, t64a, H, M, C, H, 1, x.st));
+        PDSC_TRY(probe_absmax(x, PDSC_RANGE_FC1, t64a, (size_t)M * H));
+        PDSC_TRY(pdsc_linear(t64a, H, x.W(PDSC_W_FC2_W, i), x.W(PDSC_W_FC2_B, i), nullptr, 0, t64b, H, M, H, H, 1, x.st));
+        PDSC_TRY(probe_absmax(x, PDSC_RANGE_FC2, t64b, (size_t)M * H));
+        PDSC_TRY(pdsc_linear(t64b, H, x.W(PDSC_W_FC3_W, i), x.W(PDSC_W_FC3_B, i), x.featB, C, x.featA, C, M, H, C, 0, x.st));
+        PDSC_TRY(probe_absmax(x, PDSC_RANGE_FEATURE, x.featA, (size_t)M * C));
+    }
+    return PDSC_OK;
+}
+
+// pdsc_forward_testing_streams: everything after the encoder -- a strictly sequential chain of ~15 small, latency-bound
+// launches -- goes to the caller's second (high-priority) stream: with several forwards in flight its workgroups are then
+// dispatched ahead of the queued workgroups of another forward's attention launch instead of behind them.
+static int fork_tail(ForwardCtx& x) {
+    if (!x.c.tail_stream) return PDSC_OK;
+    if (hipEventRecord((hipEvent_t)x.c.ev_fork, (hipStream_t)x.c.stream) != hipSuccess ||
+        hipStreamWaitEvent((hipStream_t)x.c.tail_stream, (hipEvent_t)x.c.ev_fork, 0) != hipSuccess)
+        return check_launch("pdsc_forward_testing_streams(fork)");
+    x.st = (hipStream_t)x.c.tail_stream;
+    return PDSC_OK;
+}
+// join: whatever the caller enqueues on the main stream next is ordered after the results
+static int join_tail(const ForwardCtx& x) {
+    if (!x.c.tail_stream) return PDSC_OK;
+    if (hipEventRecord((hipEvent_t)x.c.ev_join, (hipStream_t)x.c.tail_stream) != hipSuccess ||
+        hipStreamWaitEvent((hipStream_t)x.c.stream, (hipEvent_t)x.c.ev_join, 0) != hipSuccess)
+        return check_launch("pdsc_forward_testing_streams(join)");
+    return PDSC_OK;
+}
+
+// Step 2.1 (:156,:171,:174): confidence head, normalise, then the seeds: by NMS (Testing), or the top S by confidence next to the
+// feature similarity matrix (Validation, :158-163 and :176)
+static int run_seed_selection(const ForwardCtx& x) {
+    const ForwardCall& c = x.c;
+    const int C = PDSC_CHANNELS, M = x.M;
+    float *h1 = x.L.at<float>(c.workspace, WS_H1), *h2 = x.L.at<float>(c.workspace, WS_H2);
+    if (env_int("PDSC_CLS_FUSED", 1))       // (A/B knob, experiments builds: 0 = the two pdsc_linear launches of r01-r03; same bits)
+        PDSC_TRY(launch_classifier_hidden(x.featA, x.W(PDSC_W_CLS1_W, 0), x.W(PDSC_W_CLS1_B, 0), x.W(PDSC_W_CLS2_W, 0), x.W(PDSC_W_CLS2_B, 0), h2, M, x.st));
+    else {
+        PDSC_TRY(pdsc_linear(x.featA, C, x.W(PDSC_W_CLS1_W, 0), x.W(PDSC_W_CLS1_B, 0), nullptr, 0, h1, 32, M, C, 32, 1, x.st));
+        PDSC_TRY(pdsc_linear(h1, 32, x.W(PDSC_W_CLS2_W, 0), x.W(PDSC_W_CLS2_B, 0), nullptr, 0, h2, 32, M, 32, 32, 1, x.st));
+    }
+    if (x.normed_pf)
+        PDSC_TRY(launch_normalize_conf_pf(x.featA, h2, x.W(PDSC_W_CLS3_W, 0), x.W(PDSC_W_CLS3_B, 0), x.normed, x.normed_pf, x.conf, c.bs, c.N, x.st));
+    else
+        PDSC_TRY(pdsc_normalize_confidence(x.featA, h2, x.W(PDSC_W_CLS3_W, 0), x.W(PDSC_W_CLS3_B, 0), x.normed, x.conf, M, x.st));
+    if (c.mode == ForwardMode::Testing) {
+        PDSC_TRY(launch_nms_keys_grid(c.src, x.conf, c.cfg->nms_radius, x.keys, x.L.at<void>(c.workspace, WS_NMS_WS),
+                                      pdsc_nms_workspace_bytes(c.bs, c.N), c.bs, c.N, c.nvalid, x.st));
+        return launch_rank_select(x.keys, x.seeds, c.bs, c.N, x.S, c.nvalid, c.svalid, x.st, x.conv_mask);      // (+ the solver's mask := all-ones)
+    }
+    PDSC_TRY(pdsc_feature_compat(x.normed, x.W(PDSC_W_SIGMA, 0), c.Mout, c.ldM, c.bs, c.N, x.st));
+    return pdsc_rank_select(x.conf, x.seeds, c.bs, c.N, x.S, x.st);
+}
+
+// Step 3 & 4 (:182 -> :234-336): per-seed hypotheses and their scores
+static int run_hypotheses(const ForwardCtx& x) {
+    const ForwardCall& c = x.c;
+    const bool testing = c.mode == ForwardMode::Testing;
+    const int iters = c.cfg->num_iterations;
+    void* ws = c.workspace;
+    float *knn_dist = x.L.at<float>(ws, WS_KNN_DIST), *eig = x.L.at<float>(ws, WS_EIG_ITERS), *seed_w = x.L.at<float>(ws, WS_SEED_W);
+    PDSC_TRY(launch_knn_seeds_form(x.normed, x.normed_pf, x.seeds, knn_dist, x.knn_idx, c.bs, c.N, x.S, x.k, c.nvalid, x.normed_pf ? 2 : 1, x.st));
+    if (!testing && c.bs > 1) {
         // validation forward: the early exit is taken over the seeds of ALL pairs of the batch (one torch.allclose over
         // [bs*S, k]) -- the per-pair masks are AND-ed before the iterate is chosen, so the two steps stay apart
-        PDSC_TRY(pdsc_seed_power_iteration(normed, src, tgt, knn_idx, W(PDSC_W_SIGMA, 0), W(PDSC_W_SIGMA_SPAT, 0), eig,
-                                           conv_mask, nullptr, bs, N, S, k, cfg->num_iterations, stream));
-        PDSC_TRY(pdsc_conv_mask_all_pairs(conv_mask, bs, stream));
-        PDSC_TRY(pdsc_seed_transforms(src, tgt, knn_idx, eig, conv_mask, seed_trans, seed_w, bs, N, S, k,
-                                      cfg->num_iterations, stream));
+        PDSC_TRY(pdsc_seed_power_iteration(x.normed, c.src, c.tgt, x.knn_idx, x.W(PDSC_W_SIGMA, 0), x.W(PDSC_W_SIGMA_SPAT, 0), eig, x.conv_mask,
+                                           nullptr, c.bs, c.N, x.S, x.k, iters, x.st));
+        PDSC_TRY(pdsc_conv_mask_all_pairs(x.conv_mask, c.bs, x.st));
+        PDSC_TRY(pdsc_seed_transforms(c.src, c.tgt, x.knn_idx, eig, x.conv_mask, x.seed_trans, seed_w, c.bs, c.N, x.S, x.k, iters, x.st));
     } else
-        PDSC_TRY(launch_seed_solve_forward(normed, src, tgt, knn_idx, W(PDSC_W_SIGMA, 0), W(PDSC_W_SIGMA_SPAT, 0), eig, conv_mask,
-                                           seed_trans, seed_w, bs, N, S, k, cfg->num_iterations, /*mask_ready=*/mode == 0, hst));
+        PDSC_TRY(launch_seed_solve_forward(x.normed, c.src, c.tgt, x.knn_idx, x.W(PDSC_W_SIGMA, 0), x.W(PDSC_W_SIGMA_SPAT, 0), eig, x.conv_mask,
+                                           x.seed_trans, seed_w, c.bs, c.N, x.S, x.k, iters, /*mask_ready=*/testing, x.st));
 #ifdef PDSC_EXPERIMENTS
-    score_debug_slot() = env_int("PDSC_SCORE_DEBUG", 0) ? F("score_dbg") : nullptr;
+    score_debug_slot() = env_int("PDSC_SCORE_DEBUG", 0) ? x.L.at<float>(ws, WS_SCORE_DBG) : nullptr;
 #endif
-    PDSC_TRY(launch_score_hypotheses(seed_trans, src, tgt, cfg->inlier_threshold, counts, bs, N, S, nvalid, hst));
+    PDSC_TRY(launch_score_hypotheses(x.seed_trans, c.src, c.tgt, c.cfg->inlier_threshold, x.counts, c.bs, c.N, x.S, c.nvalid, x.st));
 #ifdef PDSC_EXPERIMENTS
     score_debug_slot() = nullptr;
 #endif
-    if (mode == 0) {
-        // best hypothesis + its labels, then post refinement (:186 -> :403-438) in the same launch; final_labels stay those of the
-        // pre-refinement best hypothesis
-        PDSC_TRY(launch_select_and_refine(counts, seed_trans, src, tgt, cfg->inlier_threshold, cfg->refine_threshold, cfg->refine_iters, best, initial,
-                                          final_labels, final_trans, solves, bs, N, S, nvalid, hst, I("refine_trace"), range_flag, range_report_slot()));
-    } else {
-        // best hypothesis is the result (:186 is skipped); the labels of the call are the logits (:190-191)
-        PDSC_TRY(pdsc_select_best(counts, seed_trans, src, tgt, cfg->inlier_threshold, best, final_trans, keys /* scratch */,
-                                  bs, N, S, stream));
-        PDSC_TRY(launch_copy_u32((unsigned int*)final_labels, (const unsigned int*)conf, (size_t)M, (hipStream_t)stream));
-    }
-    if (tail_stream) {       // join: whatever the caller enqueues on the main stream next is ordered after the results
-        if (hipEventRecord((hipEvent_t)ev_join, (hipStream_t)tail_stream) != hipSuccess ||
-            hipStreamWaitEvent((hipStream_t)main_stream, (hipEvent_t)ev_join, 0) != hipSuccess)
-            return check_launch("pdsc_forward_testing_streams(join)");
-    }
     return PDSC_OK;
+}
+
+// best hypothesis + its labels, then post refinement (:186 -> :403-438) in the same launch; final_labels stay those of the
+// pre-refinement best hypothesis
+static int finish_testing(const ForwardCtx& x) {
+    const ForwardCall& c = x.c;
+    const WsLayout& L = x.L;
+    void* ws = c.workspace;
+    return launch_select_and_refine(x.counts, x.seed_trans, c.src, c.tgt, c.cfg->inlier_threshold, c.cfg->refine_threshold, c.cfg->refine_iters,
+                                    L.at<int>(ws, WS_BEST), L.at<float>(ws, WS_INITIAL_TRANS), c.final_labels, c.final_trans,
+                                    L.at<int>(ws, WS_SOLVES), c.bs, c.N, x.S, c.nvalid, x.st, L.at<int>(ws, WS_REFINE_TRACE), x.range_flag,
+                                    range_report_slot());
+}
+// best hypothesis is the result (:186 is skipped); the labels of the call are the logits (:190-191); range_flag is not read here
+static int finish_validation(const ForwardCtx& x) {
+    const ForwardCall& c = x.c;
+    PDSC_TRY(pdsc_select_best(x.counts, x.seed_trans, c.src, c.tgt, c.cfg->inlier_threshold, x.L.at<int>(c.workspace, WS_BEST), c.final_trans,
+                              x.keys /* scratch */, c.bs, c.N, x.S, x.st));
+    return launch_copy_u32((unsigned int*)c.final_labels, (const unsigned int*)x.conf, (size_t)x.M, x.st);
+}
+
+// The whole path: which mode runs which stage.  Every stage only enqueues (no host synchronisation, no allocation, no state).
+static int run_forward(const ForwardCall& call) {
+    const bool probe = call.mode == ForwardMode::Probe, testing = call.mode == ForwardMode::Testing;
+    ForwardCtx x{call};
+    PDSC_TRY(validate_call(call));
+    PDSC_TRY(plan_encoder(call.cfg, call.bs, call.N, call.nvalid, call.n_min, &x.plan));
+    PDSC_TRY(bind_workspace(x));
+    PDSC_TRY(run_compat_layer0(x));
+    PDSC_TRY(x.plan.fused && !probe ? run_encoder_fused(x) : run_encoder_per_conv(x));
+    if (probe) return PDSC_OK;
+    PDSC_TRY(fork_tail(x));
+    PDSC_TRY(run_seed_selection(x));
+    PDSC_TRY(run_hypotheses(x));
+    PDSC_TRY(testing ? finish_testing(x) : finish_validation(x));
+    return join_tail(x);
 }
 
 extern "C" int pdsc_forward_testing(const pdsc_config* cfg, const float* wpack, const void* wsplit, const float* corr_pos,
                                     const float* src, const float* tgt, int bs, int N, int num_seeds,
                                     float* final_trans, float* final_labels, void* workspace, size_t workspace_bytes,
                                     void* stream) {
-    return run_forward(0, cfg, wpack, wsplit, corr_pos, src, tgt, bs, N, num_seeds, final_trans, final_labels, nullptr, 0,
-                       workspace, workspace_bytes, stream);
+    return run_forward({.mode = ForwardMode::Testing, .cfg = cfg, .wpack = wpack, .wsplit = wsplit, .corr_pos = corr_pos, .src = src,
+                        .tgt = tgt, .bs = bs, .N = N, .num_seeds = num_seeds, .final_trans = final_trans, .final_labels = final_labels,
+                        .workspace = workspace, .workspace_bytes = workspace_bytes, .stream = stream});
 }
 
 extern "C" int pdsc_forward_testing_ragged(const pdsc_config* cfg, const float* wpack, const void* wsplit, const float* corr_pos,
@@ -699,8 +806,10 @@ extern "C" int pdsc_forward_testing_ragged(const pdsc_config* cfg, const float* 
                                            const int* num_seeds_per_pair, int n_min, float* final_trans, float* final_labels,
                                            void* workspace, size_t workspace_bytes, void* stream) {
     PDSC_REQUIRE(num_corr && num_seeds_per_pair, "pdsc_forward_testing_ragged: the per-pair count arrays (device, [bs] int32) are required");
-    return run_forward(0, cfg, wpack, wsplit, corr_pos, src, tgt, bs, N, num_seeds, final_trans, final_labels, nullptr, 0,
-                       workspace, workspace_bytes, stream, num_corr, num_seeds_per_pair, n_min);
+    return run_forward({.mode = ForwardMode::Testing, .cfg = cfg, .wpack = wpack, .wsplit = wsplit, .corr_pos = corr_pos, .src = src,
+                        .tgt = tgt, .bs = bs, .N = N, .num_seeds = num_seeds, .final_trans = final_trans, .final_labels = final_labels,
+                        .workspace = workspace, .workspace_bytes = workspace_bytes, .stream = stream, .nvalid = num_corr,
+                        .svalid = num_seeds_per_pair, .n_min = n_min});
 }
 
 extern "C" int pdsc_forward_testing_streams(const pdsc_config* cfg, const float* wpack, const void* wsplit, const float* corr_pos,
@@ -710,8 +819,10 @@ extern "C" int pdsc_forward_testing_streams(const pdsc_config* cfg, const float*
                                             void* join_event) {
     PDSC_REQUIRE((num_corr == nullptr) == (num_seeds_per_pair == nullptr), "pdsc_forward_testing_streams: both count arrays or neither");
     PDSC_REQUIRE(tail_stream && fork_event && join_event, "pdsc_forward_testing_streams: tail stream and both events are required");
-    return run_forward(0, cfg, wpack, wsplit, corr_pos, src, tgt, bs, N, num_seeds, final_trans, final_labels, nullptr, 0,
-                       workspace, workspace_bytes, stream, num_corr, num_seeds_per_pair, n_min, tail_stream, fork_event, join_event);
+    return run_forward({.mode = ForwardMode::Testing, .cfg = cfg, .wpack = wpack, .wsplit = wsplit, .corr_pos = corr_pos, .src = src,
+                        .tgt = tgt, .bs = bs, .N = N, .num_seeds = num_seeds, .final_trans = final_trans, .final_labels = final_labels,
+                        .workspace = workspace, .workspace_bytes = workspace_bytes, .stream = stream, .nvalid = num_corr,
+                        .svalid = num_seeds_per_pair, .n_min = n_min, .tail_stream = tail_stream, .ev_fork = fork_event, .ev_join = join_event});
 }
 
 // Range probe for layer_gemm = PDSC_LAYER_GEMM_H3 (fp16 hi/lo operands: every activation of the chain must stay below 65504): the
@@ -721,9 +832,9 @@ extern "C" int pdsc_encoder_range_probe(const pdsc_config* cfg, const float* wpa
                                         void* workspace, size_t workspace_bytes, void* stream) {
     PDSC_REQUIRE(absmax, "pdsc_encoder_range_probe: absmax [PDSC_RANGE_NUM_KINDS] (device) required");
     PDSC_TRY(launch_fill_u32((unsigned int*)absmax, 0u, PDSC_RANGE_NUM_KINDS, (hipStream_t)stream));
-    float dummy_T = 0.f;         // (outputs of the tail are not produced in probe mode; the pointers only pass the null checks)
-    return run_forward(0, cfg, wpack, wsplit, corr_pos, src, tgt, bs, N, num_seeds, &dummy_T, &dummy_T, nullptr, 0, workspace,
-                       workspace_bytes, stream, nullptr, nullptr, 0, nullptr, nullptr, nullptr, (unsigned int*)absmax);
+    return run_forward({.mode = ForwardMode::Probe, .cfg = cfg, .wpack = wpack, .wsplit = wsplit, .corr_pos = corr_pos, .src = src, .tgt = tgt,
+                        .bs = bs, .N = N, .num_seeds = num_seeds, .workspace = workspace, .workspace_bytes = workspace_bytes, .stream = stream,
+                        .probe = (unsigned int*)absmax});
 }
 
 extern "C" int pdsc_forward_validation(const pdsc_config* cfg, const float* wpack, const void* wsplit, const float* corr_pos,
@@ -731,6 +842,7 @@ extern "C" int pdsc_forward_validation(const pdsc_config* cfg, const float* wpac
                                        float* final_trans, float* logits, float* Mout, long long ldM, void* workspace,
                                        size_t workspace_bytes, void* stream) {
     PDSC_REQUIRE(Mout && ldM >= N, "pdsc_forward_validation: M matrix [bs][N][ldM >= N] required");
-    return run_forward(1, cfg, wpack, wsplit, corr_pos, src, tgt, bs, N, num_seeds, final_trans, logits, Mout, ldM,
-                       workspace, workspace_bytes, stream);
+    return run_forward({.mode = ForwardMode::Validation, .cfg = cfg, .wpack = wpack, .wsplit = wsplit, .corr_pos = corr_pos, .src = src,
+                        .tgt = tgt, .bs = bs, .N = N, .num_seeds = num_seeds, .final_trans = final_trans, .final_labels = logits, .Mout = Mout,
+                        .ldM = ldM, .workspace = workspace, .workspace_bytes = workspace_bytes, .stream = stream});
 }
