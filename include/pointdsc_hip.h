@@ -368,7 +368,9 @@ int    pdsc_pack_qkv_split(const float* qkv, void* q_split, void* kv_tiles, int 
 size_t pdsc_attention_split_scratch_bytes(int bs, int N, int nsplit);
 int    pdsc_attention_split_default_split(int bs, int N);
 /* leaf form (enum pdsc_att_leaves >= PDSC_LEAVES_CANONICAL): canonical leaf count of N; the plan (key split = workgroups per query
- * block, leaves per pair) the forward uses for (bs, N, leaves_mode); bytes of its scratch (the leaf partials) */
+ * block, leaves per pair) the forward uses for (bs, N, leaves_mode); bytes of its scratch (the leaf partials).  A key split of 1
+ * with more than one leaf: the workgroup merges its leaves itself and the pair's leaf-0 slot holds the ONE partial the layer
+ * launch loads (un-normalised sum, m = 0, l = the merge's denominator). */
 int    pdsc_attention_leaf_count(int N);
 int    pdsc_attention_leaf_plan(int bs, int N, int leaves_mode, int* nsplit, int* nleaf);
 size_t pdsc_attention_leaf_scratch_bytes(int bs, int N, int leaves_mode);
@@ -388,6 +390,13 @@ int    pdsc_sc_attention_split_u16(const void* q_split, const void* kv_tiles, co
  * phases (0 prologue, 1 first tile, 2 own-DMA wait, 3 barrier, 4 DMA issue, 5 phase A, 6 phase B, 7 rest) there.
  * NULL (default) switches it off.  Used by tools/attention_trace.py only. */
 int pdsc_attention_trace(long long* device_buffer);
+
+/* Diagnostics hook of the leaf form: workgroups per query block of every later leaf-form attention launch of this process.
+ * 0 (default): the planner decides (a function of bs and N).  Otherwise d must divide the launch's leaf count -- the call that
+ * plans a launch (pdsc_attention_leaf_plan, the forwards) fails where it does not.  The key split decides speed only: with d = 1
+ * every workgroup merges the leaves of its query block itself, with d > 1 the layer kernel merges them, same arithmetic, same
+ * bits.  Used by the tests and the A/B tools; process-wide, not thread-safe against running forwards. */
+int pdsc_attention_leaf_split_override(int d);
 
 /* Same for the fused layer kernel: buffer of (#workgroups * 4 waves * 16) int64 receiving raw shader-clock stamps at the
  * stage boundaries of layer_fused_kernel (tools/layer_trace.py); NULL switches it off. */

@@ -88,6 +88,7 @@ SIGNATURES = {
     "pdsc_attention_leaf_plan": (_i, [_i, _i, _i, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "pdsc_attention_leaf_scratch_bytes": (_sz, [_i, _i, _i]),
     "pdsc_attention_trace": (_i, [_vp]),
+    "pdsc_attention_leaf_split_override": (_i, [_i]),
     "pdsc_layer_trace": (_i, [_vp]),
     "pdsc_sc_attention_split": (_i, [_vp, _vp, _vp, _ll, _vp, _vp, _sz, _i, _i, _i, _vp]),
     "pdsc_sc_attention_split_u16": (_i, [_vp, _vp, _vp, _ll, _vp, _vp, _sz, _i, _i, _i, _vp]),

@@ -388,6 +388,7 @@ struct EncoderPlan {
     int gemm;                // arithmetic of fc1..fc3 / PointCN (enum pdsc_layer_gemm)
     int ns, Npad;            // key split of the attention launch, padded row count of the partials
     int nleaf, value_width;  // leaves per query (leaf form); channels of V and of the partials
+    int leaf_ns;             // leaf form: workgroups per query block (a divisor of nleaf); 1 = each merges its own leaves into one partial
     int ws_tail, ws_head;    // sections of the split-weight buffer that hold the fragment streams
 };
 
@@ -443,7 +444,8 @@ static int plan_encoder(const pdsc_config* cfg, int bs, int N, const int* nvalid
     // leaf form (r05, enum pdsc_att_leaves): the key range cut into leaves that depend on N alone; the H3 layer kernel merges the
     // leaf partials exactly as it merges key-split partials (the other layer kernels keep the per-launch key split)
     int lf_ns = 0, lf_nw = 0;
-    if (canonical) leaf_plan(bs, N, cfg->att_leaves, &lf_nw, &lf_ns, &p.nleaf);
+    if (canonical) PDSC_TRY(leaf_plan(bs, N, cfg->att_leaves, &lf_nw, &lf_ns, &p.nleaf));
+    p.leaf_ns = lf_ns;
     p.leaves = pf_ok && canonical && (!nvalid || min_tiles >= 2 * p.nleaf);
     // ... and this one alone catches a canonical-leaves configuration whose launch ends up not using the leaves
     if (nvalid && !p.leaves) PDSC_REQUIRE_SHORTEST_PAIR(min_tiles >= p.ns);
@@ -584,9 +586,12 @@ static int run_fused_layer(const ForwardCtx& x, int i, bool last, const float* c
     const bool tail = i >= 0, head = !last, split = x.split;
     // the attention's partials (leaves or key splits), when the layer kernel merges them itself
     const bool parts = plan.pf || plan.fuse_merge;
-    const int nparts = plan.leaves ? plan.nleaf : plan.ns;
+    // slots = partials per pair in the scratch layout; nparts = partials the layer kernel merges: one where every attention
+    // workgroup owned all the leaves of its query block and merged them itself (it sits in the pair's leaf-0 slot)
+    const int slots = plan.leaves ? plan.nleaf : plan.ns;
+    const int nparts = plan.leaves && plan.leaf_ns == 1 ? 1 : slots;
     const float* part_o = parts ? (const float*)x.att_scratch : nullptr;
-    const float* part_ml = parts ? part_o + (size_t)x.c.bs * nparts * plan.Npad * plan.value_width : nullptr;
+    const float* part_ml = parts ? part_o + (size_t)x.c.bs * slots * plan.Npad * plan.value_width : nullptr;
     pdsc_layer_call c{};
     // exact fp32: the batch is ONE run of M independent rows (bs = 1, N = M), so the per-pair counts of a ragged batch do
     // not describe it (with them the kernel took counts[0] for the row count of the whole batch).  Padding rows are computed
@@ -623,6 +628,7 @@ static int run_fused_layer(const ForwardCtx& x, int i, bool last, const float* c
     // the forward's own fields: the point-fragment route reports to the range sentinel and takes no trace (layer_args.h)
     LayerArgs a = layer_args_from_call(c);
     a.nvalid = split ? x.c.nvalid : nullptr;
+    if (tail) a.part_slots = slots;
     if (plan.pf) {
         a.value_fold = plan.fold;
         a.range_flag = x.range_flag;

@@ -22,6 +22,7 @@
 #include <stdlib.h>
 #include <type_traits>
 #include "attention_common.h"
+#include "merge_partials.h"
 #include "split_layout.h"
 #include "ragged.h"
 
@@ -274,7 +275,7 @@ __global__ __launch_bounds__(NW * 64, 2) void sc_attention_split_kernel(AttSplit
             }
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (!(a.nsplit != 1 && a.part_frag)) __syncthreads();        // the row-order epilogue's barrier
+        if (!MG && !(a.nsplit != 1 && a.part_frag)) __syncthreads();  // the row-order epilogue's barrier (the leaf form has none)
         return;
     }
 
@@ -341,6 +342,11 @@ __global__ __launch_bounds__(NW * 64, 2) void sc_attention_split_kernel(AttSplit
     // instruction).  The stores of a leaf that ends inside the workgroup's range leave at the top of the next loop iteration (after
     // its barrier, like the persistent form's): a whole tile of time before the next s_waitcnt vmcnt(0) meets them.
     const int q0w = qb * (NW * 32) + wave * 32;                       // first query of this wave inside the pair
+    // (m, l) of a row: BOTH lane halves of a query store the same two values to the same address, so that each lane of a workgroup
+    // that merges its own leaves (epilogue) reads back only what it wrote itself
+    auto leaf_store_ml = [&](size_t slot, float m_st, float l_st) {
+        *reinterpret_cast<float2*>(a.part_ml + (slot + l31) * 2) = float2{m_st, l_st};
+    };
     auto leaf_store = [&](int lf, float m_st, float l_st) {
         const size_t slot = ((size_t)b * a.nleaf + lf) * a.Npad + q0w;
         float* base = a.part_o + slot * VW + lane * 4;
@@ -349,10 +355,7 @@ __global__ __launch_bounds__(NW * 64, 2) void sc_attention_split_kernel(AttSplit
 #pragma unroll
             for (int g = 0; g < 4; ++g)
                 *reinterpret_cast<f32x4*>(base + pf_offset_floats(4 * c + g)) = f32x4{o[c][4 * g], o[c][4 * g + 1], o[c][4 * g + 2], o[c][4 * g + 3]};
-        if (h == 0) {
-            a.part_ml[(slot + l31) * 2 + 0] = m_st;
-            a.part_ml[(slot + l31) * 2 + 1] = l_st;
-        }
+        leaf_store_ml(slot, m_st, l_st);
     };
     int leaf_prev = 0;                          // MG: the leaf whose partial is pending (m_prev, l_prev, pend)
 
@@ -718,7 +721,52 @@ __global__ __launch_bounds__(NW * 64, 2) void sc_attention_split_kernel(AttSplit
     const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
     const int q0 = qb * (NW * 32) + wave * 32;
     if constexpr (MG) {
-        leaf_store(leaf, m_run, l_tot);          // the last leaf of this workgroup's range (lanes past N: copies of query N-1, the tile's padding)
+        if (a.nsplit != 1 || a.nleaf == 1) {
+            leaf_store(leaf, m_run, l_tot);      // the last leaf of this workgroup's range (lanes past N: copies of query N-1, the tile's padding)
+            return;
+        }
+        // This workgroup owns EVERY leaf of its query block: it runs the layer kernel's flat merge (merge_partials.h: the same row
+        // weights, the same fmaf chain in leaf order) itself and leaves ONE partial, the un-normalised chain sum with (m, l) =
+        // (0, den), in the pair's leaf-0 slot -- the layer launch then loads one partial per point instead of nleaf, and its one-way
+        // merge returns the bits of the nleaf-way merge (merge_chain).  The earlier leaves come back from the slots they were stored
+        // to: every lane reads the pieces and the (m, l) values it stored itself, in program order behind a wait that covers its
+        // stores (the last of them left at the top of the last leaf's first iteration; every iteration since, and the wait above,
+        // drained the counter) -- nothing another wave or workgroup wrote, no flag, no barrier.  The last leaf never leaves its
+        // registers: one round trip of loads, all in flight together, then arithmetic and stores.
+        const size_t slot0 = (size_t)b * a.nleaf * a.Npad + q0w;
+        with_split_count<MERGE_MAX_SPLIT_H3>(a.nleaf, [&](auto nl_tag) {
+            constexpr int L = decltype(nl_tag)::value;
+            if constexpr (L >= 2) {
+                float2 ml[L];
+#pragma unroll
+                for (int lf = 0; lf < L - 1; ++lf) ml[lf] = *reinterpret_cast<const float2*>(a.part_ml + (slot0 + l31 + (size_t)lf * a.Npad) * 2);
+                ml[L - 1] = float2{m_run, l_tot};
+                float* base = a.part_o + slot0 * VW + lane * 4;
+                const size_t lstride = (size_t)a.Npad * VW;                // floats between two leaves of a pair
+                constexpr int GQ = (L <= 4 ? 8 : 4) * 64 / VW;               // pieces per batch of loads (<= 112 registers in flight)
+                MergeWeights<L> mw;
+#pragma unroll
+                for (int q0 = 0; q0 < 4 * NC; q0 += GQ) {
+                    f32x4 pv[GQ][L];
+#pragma unroll
+                    for (int q = 0; q < GQ; ++q)
+#pragma unroll
+                        for (int lf = 0; lf < L - 1; ++lf)
+                            pv[q][lf] = *reinterpret_cast<const f32x4*>(base + (size_t)lf * lstride + pf_offset_floats(q0 + q));
+                    if (q0 == 0) mw = merge_weights_of<L>(ml);        // (behind the first batch's loads)
+#pragma unroll
+                    for (int q = 0; q < GQ; ++q) {
+                        const int c = (q0 + q) >> 2, g = (q0 + q) & 3;
+                        pv[q][L - 1] = f32x4{o[c][4 * g], o[c][4 * g + 1], o[c][4 * g + 2], o[c][4 * g + 3]};
+                        f32x4 v;
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) v[e] = merge_chain<L>(pv[q], mw, e);
+                        *reinterpret_cast<f32x4*>(base + pf_offset_floats(q0 + q)) = v;
+                    }
+                }
+                leaf_store_ml(slot0, 0.f, mw.den);
+            }
+        });
         return;
     }
     if (a.nsplit != 1 && a.part_frag) {
@@ -885,7 +933,12 @@ int attention_leaf_count(int N) {
 
 // leaves_mode (pdsc_config.att_leaves): PDSC_LEAVES_CANONICAL = attention_leaf_count(N) leaves, the key split a divisor of it;
 // >= 2: that many leaves (tuning, at most PDSC_ATT_MAX_LEAVES).  (PDSC_LEAVES_PER_LAUNCH does not come here: it is the key-split form.)
-void leaf_plan(int bs, int N, int leaves_mode, int* nw_out, int* nsplit_out, int* nleaf_out) {
+// The key split (workgroups per query block) is a pure function of (bs, N) and decides speed only: a workgroup that owns all the
+// leaves of its query block merges them itself with the layer kernel's arithmetic (the kernel's epilogue), so the bits are those
+// of the leaf count whatever the split.  pdsc_attention_leaf_split_override (diagnostics) replaces the rule by a divisor of the
+// leaf count; a value that does not divide it is an error here, where the leaf count is known.
+static int g_leaf_split_override = 0;
+int leaf_plan(int bs, int N, int leaves_mode, int* nw_out, int* nsplit_out, int* nleaf_out) {
     int nw, ns;
     split_plan(bs, N, &nw, &ns);
     const int tiles = spl_num_tiles(N);
@@ -904,7 +957,23 @@ void leaf_plan(int bs, int N, int leaves_mode, int* nw_out, int* nsplit_out, int
         if (((d * bs) & 7) != 0) cost *= 1.03;
         if (cost < best_cost - 1e-9) { best_cost = cost; best = d; }
     }
+    // One workgroup per query block wherever these alone give every CU an 8-wave workgroup: the model above counts whole rounds of ONE
+    // launch and so pays for the ragged last round (32 pairs of N = 5000: 640 workgroups = 2.5 rounds), which the forward in
+    // flight beside this one fills; the workgroup then merges its own leaves and the layer launch loads one partial per point instead
+    // of nleaf.  Measured with two forwards in flight (profiles/leaf_merge_ab.txt): 32 / 16 pairs of N = 5000 +1.3 / +2.8 %, 16 KITTI
+    // pairs +1.9 %, 8 pairs of N = 10000 +1.1 %; below a full round (8 pairs of N = 5000: within the spread; 4 pairs: -12 %) the
+    // model's choice stands.  A single forward on its own stream pays the last round (attention launch +10 % at 32 pairs).
+    if (C > 1 && nw == 8 && (long long)nq * bs >= slots) best = 1;
+    int force = g_leaf_split_override;
+#ifdef PDSC_EXPERIMENTS
+    if (force == 0) force = env_int("PDSC_ATT_LEAF_SPLIT", 0);       // A/B knob (experiments builds): as the override
+#endif
     *nw_out = nw; *nsplit_out = best; *nleaf_out = C;
+    if (force != 0) {
+        PDSC_REQUIRE(force > 0 && C % force == 0, "attention leaf plan: the split override %d does not divide the %d leaves of N=%d", force, C, N);
+        *nsplit_out = force;
+    }
+    return PDSC_OK;
 }
 
 }  // namespace pdsc
@@ -917,14 +986,19 @@ extern "C" int pdsc_attention_leaf_plan(int bs, int N, int leaves_mode, int* nsp
     PDSC_REQUIRE(bs > 0 && N > 0 && leaves_mode >= PDSC_LEAVES_CANONICAL && leaves_mode <= PDSC_ATT_MAX_LEAVES && nsplit && nleaf,
                  "pdsc_attention_leaf_plan: bs=%d N=%d leaves_mode=%d", bs, N, leaves_mode);
     int nw;
-    leaf_plan(bs, N, leaves_mode, &nw, nsplit, nleaf);
+    return leaf_plan(bs, N, leaves_mode, &nw, nsplit, nleaf);
+}
+
+extern "C" int pdsc_attention_leaf_split_override(int d) {   // diagnostics: see include/pointdsc_hip.h
+    PDSC_REQUIRE(d >= 0 && d <= PDSC_ATT_MAX_LEAVES, "pdsc_attention_leaf_split_override: d=%d (0 = the planner decides, else a divisor of the leaf count)", d);
+    g_leaf_split_override = d;
     return PDSC_OK;
 }
 
 extern "C" size_t pdsc_attention_leaf_scratch_bytes(int bs, int N, int leaves_mode) {
     if (bs <= 0 || N <= 0 || leaves_mode < PDSC_LEAVES_CANONICAL) return 0;
     int nw, ns, C;
-    leaf_plan(bs, N, leaves_mode, &nw, &ns, &C);
+    leaf_plan(bs, N, leaves_mode, &nw, &ns, &C);     // (the leaf count does not depend on the split: an override error is the launch's to report)
     return (size_t)bs * C * round_up(N, 256) * (PDSC_CHANNELS + 2) * sizeof(float);
 }
 
@@ -942,7 +1016,7 @@ int pdsc::launch_attention_leaves(const void* q_split, const void* kv_tiles, con
     PDSC_REQUIRE(ld >= round_up(N, SPL_BK) && ld % (c16 ? 8 : 4) == 0,
                  "pdsc_sc_attention_leaves: ld=%lld must be a multiple of %d and >= N rounded up to 32", ld, c16 ? 8 : 4);
     int nw, ns, C;
-    leaf_plan(bs, N, leaves_mode, &nw, &ns, &C);
+    if (const int prc = leaf_plan(bs, N, leaves_mode, &nw, &ns, &C); prc != PDSC_OK) return prc;
     // ragged batches: every pair cuts ITS OWN tiles into C leaves -- the shortest pair needs at least C of them
     PDSC_REQUIRE(!nvalid || (n_min + 31) / 32 >= 2 * C, "pdsc_sc_attention_leaves: the shortest pair (%d correspondences) has fewer than two "
                  "32-key tiles for each of the %d leaves planned for bs=%d, N=%d", n_min, C, bs, N);

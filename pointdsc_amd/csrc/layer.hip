@@ -351,6 +351,9 @@ int validate_layer_args(const LayerArgs& a, LayerKernel kernel, const char* who)
         if (!a.msg) PDSC_REQUIRE(a.part_ml && a.nsplit >= 1 && a.nsplit <= layer_merge_limit(kernel) && a.Npad >= a.N,
                                  "%s: partials need part_ml, 1 <= nsplit <= %d (what this launch's kernel merges), Npad >= N", who,
                                  layer_merge_limit(kernel));
+        if (!a.msg) PDSC_REQUIRE(a.part_slots == a.nsplit || (h3 && a.part_slots > a.nsplit),
+                                 "%s: part_slots=%d (partials per pair in the layout) must be nsplit=%d, or more in the H3 kernels", who,
+                                 a.part_slots, a.nsplit);
         PDSC_REQUIRE(!(io & PDSC_IO_PARTIALS_PF) || (!a.msg && a.Npad % 32 == 0), "%s: PF partials come un-merged (msg NULL), Npad a multiple of 32", who);
     } else {
         PDSC_REQUIRE(a.feat_in, "%s: head-only needs feat_in", who);

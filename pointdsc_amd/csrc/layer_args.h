@@ -12,7 +12,10 @@ struct LayerArgs {
     const float* msg;        // [M][128]  attention output            (tail), or NULL when the partials below are given
     const float* part_o;     // [bs][nsplit][Npad][128] un-normalised partial outputs of the attention key splits
     const float* part_ml;    // [bs][nsplit][Npad][2]   (reference exponent (log2), partial sum)
-    int nsplit, Npad;
+    int nsplit, Npad;        // nsplit = partials the kernel merges per row
+    int part_slots;          // partials per pair in the LAYOUT of part_o / part_ml (>= nsplit).  Larger than nsplit where the attention
+                             // workgroups merged their leaves themselves (attention_split.hip): ONE partial to merge, left in
+                             // the pair's leaf-0 slot of the [bs][nleaf][Npad] scratch (layer_h3.hip / layer_coop.hip only)
     const float* res;        // [M][128]  featB of this layer         (tail residual)
     const float* feat_in;    // [M][128]  used when there is no tail  (first head)
     float* feat_out;         // [M][128]  tail result, written when non-null
@@ -58,7 +61,7 @@ constexpr int layer_merge_limit(LayerKernel k) {
 // the point-fragment route reports to the fp16 range sentinel so far).
 inline LayerArgs layer_args_from_call(const pdsc_layer_call& c) {
     LayerArgs a{};
-    a.msg = c.msg; a.part_o = c.part_o; a.part_ml = c.part_ml; a.nsplit = c.nsplit; a.Npad = c.Npad;
+    a.msg = c.msg; a.part_o = c.part_o; a.part_ml = c.part_ml; a.nsplit = c.nsplit; a.part_slots = c.nsplit; a.Npad = c.Npad;
     a.res = c.res; a.feat_in = c.feat_in; a.feat_out = c.feat_out; a.featB_out = c.featB_out; a.qkv_out = c.qkv_out;
     a.qs = (sp16*)c.q_split; a.kv = (unsigned char*)c.kv_tiles;
     a.w1 = (const float*)c.w1; a.b1 = c.b1; a.w2 = (const float*)c.w2; a.b2 = c.b2; a.w3 = (const float*)c.w3; a.b3 = c.b3;

@@ -111,11 +111,11 @@ __global__ __launch_bounds__(64 * LC_WAVES, NB <= 4 ? 2 : 1) void layer_h3_coop_
         } else {
             with_split_count<MERGE_MAX_SPLIT_H3>(a.nsplit, [&](auto ns_tag) {
                 constexpr int NS = decltype(ns_tag)::value;
-                const size_t slot0 = (size_t)b * NS * a.Npad + (row - (size_t)b * a.N);
+                const size_t slot0 = (size_t)b * a.part_slots * a.Npad + (row - (size_t)b * a.N);
                 const MergeWeights<NS> mw = merge_row_weights<NS>(a.part_ml, slot0, (size_t)a.Npad);
                 // (own addresses: <T, H, PF, 4> keeps 253 registers with them, 254 through a shared address helper)
                 const bool pf = a.io_flags & PDSC_IO_PARTIALS_PF;
-                const size_t e0 = pf ? ((size_t)b * NS * a.Npad + (size_t)td.tile * 32) * VW + lane * 4 : slot0 * VW + 4 * h;
+                const size_t e0 = pf ? ((size_t)b * a.part_slots * a.Npad + (size_t)td.tile * 32) * VW + lane * 4 : slot0 * VW + 4 * h;
                 const int eq = pf ? 256 : 8;
                 // q per batch of loads: everything at once in the latency form; <= 32 registers of partials in flight in the
                 // two-workgroups-per-CU form (256 registers)

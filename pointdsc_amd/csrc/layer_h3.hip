@@ -122,10 +122,10 @@ __global__ __launch_bounds__(64 * NWV, NBUF > 2 ? 1 : 2) void layer_h3_kernel(La
             with_split_count<MERGE_MAX_SPLIT_H3>(a.nsplit, [&](auto ns_tag) {
                 constexpr int NS = decltype(ns_tag)::value;
                 constexpr int GQ = (NS <= 2 ? 16 : NS <= 4 ? 8 : 4) < NQ ? (NS <= 2 ? 16 : NS <= 4 ? 8 : 4) : NQ;   // pieces per batch of loads (<= 128 registers in flight)
-                const size_t slot0 = (size_t)b * NS * a.Npad + (row - (size_t)b * a.N);
+                const size_t slot0 = (size_t)b * a.part_slots * a.Npad + (row - (size_t)b * a.N);
                 // element q of split sp: rows order = row `slot`, floats 8q + 4h; point-fragment order = tile base + 256 q + 4 lane
                 const bool pf = a.io_flags & PDSC_IO_PARTIALS_PF;
-                const size_t e0 = pf ? ((size_t)b * NS * a.Npad + (size_t)tile * 32) * VW + lane * 4 : slot0 * VW + 4 * h;
+                const size_t e0 = pf ? ((size_t)b * a.part_slots * a.Npad + (size_t)tile * 32) * VW + lane * 4 : slot0 * VW + 4 * h;
                 const int eq = pf ? 256 : 8;
                 const MergeWeights<NS> mw = merge_row_weights<NS>(a.part_ml, slot0, (size_t)a.Npad);
 #pragma unroll

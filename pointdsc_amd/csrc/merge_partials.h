@@ -42,22 +42,19 @@ __device__ __forceinline__ void with_split_count(int ns, F&& f) {
     }
 }
 
-// weights of one row: w[sp] = exp2(m_sp - max m), rden = 1 / sum l_sp w[sp]
+// weights of one row: w[sp] = exp2(m_sp - max m), den = sum l_sp w[sp], rden = 1 / den
 template <int NS>
 struct MergeWeights {
-    float w[NS], rden;
+    float w[NS], den, rden;
 };
 
-// slot0 = the row's slot in split 0 of its pair, sp_stride = slots per split (Npad)
+// ... from the row's (m, l) pairs (the attention workgroup that merges its own leaves holds the last leaf's pair in registers)
 template <int NS>
-__device__ __forceinline__ MergeWeights<NS> merge_row_weights(const float* __restrict__ part_ml, size_t slot0, size_t sp_stride) {
+__device__ __forceinline__ MergeWeights<NS> merge_weights_of(const float2 (&ml)[NS]) {
     MergeWeights<NS> r;
     float ls[NS];
 #pragma unroll
-    for (int sp = 0; sp < NS; ++sp) {
-        const float2 ml = *reinterpret_cast<const float2*>(part_ml + (slot0 + (size_t)sp * sp_stride) * 2);
-        r.w[sp] = ml.x; ls[sp] = ml.y;
-    }
+    for (int sp = 0; sp < NS; ++sp) { r.w[sp] = ml[sp].x; ls[sp] = ml[sp].y; }
     float mmax = r.w[0];
 #pragma unroll
     for (int sp = 1; sp < NS; ++sp) mmax = fmaxf(mmax, r.w[sp]);
@@ -67,17 +64,35 @@ __device__ __forceinline__ MergeWeights<NS> merge_row_weights(const float* __res
         r.w[sp] = __builtin_amdgcn_exp2f(r.w[sp] - mmax);
         den = fmaf(ls[sp], r.w[sp], den);
     }
+    r.den = den;
     r.rden = 1.0f / den;                   // one correctly-rounded reciprocal per row, then multiplies
     return r;
 }
-
-// one 4-channel piece from its NS loaded partials (and channel e of it alone, for callers that pin each value as it is made)
+// ... loaded: slot0 = the row's slot in split 0 of its pair, sp_stride = slots per split (Npad)
 template <int NS>
-__device__ __forceinline__ float merge_apply(const f32x4 (&pv)[NS], const MergeWeights<NS>& mw, int e) {
+__device__ __forceinline__ MergeWeights<NS> merge_row_weights(const float* __restrict__ part_ml, size_t slot0, size_t sp_stride) {
+    float2 ml[NS];
+#pragma unroll
+    for (int sp = 0; sp < NS; ++sp) ml[sp] = *reinterpret_cast<const float2*>(part_ml + (slot0 + (size_t)sp * sp_stride) * 2);
+    return merge_weights_of<NS>(ml);
+}
+
+// The un-normalised sum of channel e of one 4-channel piece over its NS loaded partials, in partial order.  Two sites run it: the
+// layer kernels (merge_apply below), and the attention workgroup that owns every leaf of its query block (attention_split.hip),
+// which leaves the sum with (m, l) = (0, den) as the pair's ONE partial.  Merging that partial reproduces the NS-way merge bit for
+// bit: w = exp2(0 - 0) = 1, den' = fmaf(den, 1, 0) = den, hence the same reciprocal, and fmaf(s, 1, 0) = s (a chain that starts
+// from +0 never ends in -0), so s * rden is the same product.
+template <int NS>
+__device__ __forceinline__ float merge_chain(const f32x4 (&pv)[NS], const MergeWeights<NS>& mw, int e) {
     float s = 0.f;
 #pragma unroll
     for (int sp = 0; sp < NS; ++sp) s = fmaf(pv[sp][e], mw.w[sp], s);
-    return s * mw.rden;
+    return s;
+}
+// one 4-channel piece from its NS loaded partials (and channel e of it alone, for callers that pin each value as it is made)
+template <int NS>
+__device__ __forceinline__ float merge_apply(const f32x4 (&pv)[NS], const MergeWeights<NS>& mw, int e) {
+    return merge_chain<NS>(pv, mw, e) * mw.rden;
 }
 template <int NS>
 __device__ __forceinline__ f32x4 merge_apply(const f32x4 (&pv)[NS], const MergeWeights<NS>& mw) {

@@ -59,7 +59,7 @@ int launch_attention_split_ex(const void* q_split, const void* kv_tiles, const v
 // point-fragment order for the H3 layer kernel to merge
 constexpr int PDSC_ATT_MAX_LEAVES = 8;       // = MERGE_MAX_SPLIT_H3 (merge_partials.h): what the layer kernel merges while it loads
 int attention_leaf_count(int N);
-void leaf_plan(int bs, int N, int leaves_mode, int* nw_out, int* nsplit_out, int* nleaf_out);
+int leaf_plan(int bs, int N, int leaves_mode, int* nw_out, int* nsplit_out, int* nleaf_out);
 int launch_attention_leaves(const void* q_split, const void* kv_tiles, const void* compat, int compat_format, long long ld,
                             void* scratch, size_t scratch_bytes, int bs, int N, int leaves_mode, const int* nvalid, int n_min,
                             hipStream_t st, int value_width = PDSC_CHANNELS);
