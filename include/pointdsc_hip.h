@@ -980,6 +980,37 @@ int pdsc_sm_loss_features(const float* normed, const float* sigma, const float* 
 int pdsc_transformation_loss(const float* trans, const float* gt_trans, const float* src, const float* tgt, const float* probs,
                              float re_thre, float te_thre, double* out, void* ws, size_t ws_bytes, int bs, int N, void* stream);
 
+/* ---- backward of the spatial-consistency attention --------------------------------------------
+ * The one operation of the training path that torch can only differentiate by materialising bs x N x N scores.  Exact fp32 on
+ * v_mfma_f32_32x32x2_f32 like pdsc_sc_attention; no floating-point atomics: every sum has a fixed order and repeat calls are
+ * bit-identical.  Asynchronous on `stream`, no allocation, no synchronisation.
+ *   qkv, dqkv [bs*N][384] rows (q | k | v), q pre-scaled by log2(e)/sqrt(128) as everywhere in the library; dqkv is the gradient
+ *   with respect to the rows AS PASSED (the caller scales dq back by the same factor for the gradient of an un-scaled q).
+ *   compat [bs][N][ld] fp32, ld a multiple of 4 and >= N rounded up to 32; it gets no gradient (the reference builds it under
+ *   no_grad).   msg, dmsg [bs*N][128];   lse [bs*N].
+ * pdsc_sc_attention_lse: pdsc_sc_attention that also leaves lse[o] = m_o + log2(l_o), the log2-domain row statistic of the
+ *   softmax (P_oi = exp2(compat_oi <q_o, k_i> - lse_o)); msg is bit for bit pdsc_sc_attention's at the same nsplit; scratch as
+ *   pdsc_attention_scratch_bytes.
+ * pdsc_sc_attention_backward: D_o = <dmsg_o, msg_o>; dV_i = sum_o P_oi dmsg_o; dZ_oi = compat_oi P_oi (<dmsg_o, v_i> - D_o);
+ *   dq_o = ln2 sum_i dZ_oi k_i; dk_i = ln2 sum_o dZ_oi q_o.  Launches: the row dots, one workgroup per 128 queries and key split
+ *   (dq), one per 128 keys and query split (dk, dv), both recomputing the scores from lse, and for nsplit > 1 the merge of the
+ *   per-split partial sums in index order.  workspace: pdsc_attention_backward_workspace_bytes.
+ * pdsc_sc_attention_backward_split: the same with the split count given (<= 0: pdsc_attention_backward_default_split, which aims
+ *   at one workgroup per CU; clamped to the number of 32-row tiles); workspace: pdsc_attention_backward_split_workspace_bytes at
+ *   the same nsplit.  pdsc_sc_attention_backward is nsplit = 0.  Results at different nsplit differ in summation order only.
+ * Bad arguments (null pointer, bs or N <= 0, bad ld, workspace too small) return an error with nothing enqueued. */
+int pdsc_sc_attention_lse(const float* qkv, const float* compat, long long ld, float* msg, float* lse, void* scratch,
+                          size_t scratch_bytes, int bs, int N, int nsplit, void* stream);
+size_t pdsc_attention_backward_workspace_bytes(int bs, int N);
+int pdsc_sc_attention_backward(const float* qkv, const float* compat, long long ld, const float* msg, const float* lse,
+                               const float* dmsg, float* dqkv, void* workspace, size_t workspace_bytes, int bs, int N,
+                               void* stream);
+int pdsc_attention_backward_default_split(int bs, int N);
+size_t pdsc_attention_backward_split_workspace_bytes(int bs, int N, int nsplit);
+int pdsc_sc_attention_backward_split(const float* qkv, const float* compat, long long ld, const float* msg, const float* lse,
+                                     const float* dmsg, float* dqkv, void* workspace, size_t workspace_bytes, int bs, int N,
+                                     int nsplit, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -134,6 +134,12 @@ SIGNATURES = {
     "pdsc_sm_loss_matrix": (_i, [_vp, _ll, _vp, _i, _vp, _vp, _vp, _sz, _i, _i, _vp]),
     "pdsc_sm_loss_features": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _sz, _i, _i, _vp]),
     "pdsc_transformation_loss": (_i, [_vp, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp, _sz, _i, _i, _vp]),
+    "pdsc_sc_attention_lse": (_i, [_vp, _vp, _ll, _vp, _vp, _vp, _sz, _i, _i, _i, _vp]),
+    "pdsc_attention_backward_workspace_bytes": (_sz, [_i, _i]),
+    "pdsc_sc_attention_backward": (_i, [_vp, _vp, _ll, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _vp]),
+    "pdsc_attention_backward_default_split": (_i, [_i, _i]),
+    "pdsc_attention_backward_split_workspace_bytes": (_sz, [_i, _i, _i]),
+    "pdsc_sc_attention_backward_split": (_i, [_vp, _vp, _ll, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _vp]),
     "pdsc_icp_workspace_bytes": (_sz, [_i, _i, _i]),
     "pdsc_icp_refine": (_i, [_vp, _vp, _vp, _vp, _vp, C.c_double, C.c_double, C.c_double, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                              _sz, _i, _i, _i, _vp]),

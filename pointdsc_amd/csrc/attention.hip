@@ -217,6 +217,7 @@ __global__ __launch_bounds__(256, 2) void sc_attention_kernel(AttArgs a) {
                 f32x4 v = {o[0][r] / l_tot, o[1][r] / l_tot, o[2][r] / l_tot, o[3][r] / l_tot};
                 *reinterpret_cast<f32x4*>(dst + 4 * i) = v;
             }
+            if (a.lse && h == 0) a.lse[(size_t)b * NS + query] = m_run + __builtin_amdgcn_logf(l_tot);
         } else {
             const size_t slot = ((size_t)b * a.nsplit + sp) * a.Npad + query;
             float* dst = a.part_o + slot * ATT_C;
@@ -259,6 +260,7 @@ __global__ __launch_bounds__(256) void attention_combine_kernel(AttArgs a) {
     const float rL = 1.0f / L;             // as merge_partials.h
     f32x4 out = {acc[0] * rL, acc[1] * rL, acc[2] * rL, acc[3] * rL};
     *reinterpret_cast<f32x4*>(a.msg + ((size_t)b * a.N + query) * ATT_C + c4) = out;
+    if (a.lse && c4 == 0) a.lse[(size_t)b * a.N + query] = mmax + __builtin_amdgcn_logf(L);
 }
 
 static int attention_npad(int N) { return (int)round_up(N, ATT_BQ); }
@@ -293,7 +295,7 @@ extern "C" size_t pdsc_attention_scratch_bytes(int bs, int N, int nsplit) {
 
 namespace pdsc {
 int launch_attention_fp32(const float* qkv, const float* compat, long long ld, float* msg, void* scratch, size_t scratch_bytes, int bs, int N,
-                          int nsplit, const int* nvalid, hipStream_t st_in) {
+                          int nsplit, const int* nvalid, hipStream_t st_in, float* lse) {
     void* stream = (void*)st_in;
 
     PDSC_REQUIRE(qkv && compat && msg, "pdsc_sc_attention: null pointer");
@@ -312,6 +314,7 @@ int launch_attention_fp32(const float* qkv, const float* compat, long long ld, f
     a.qkv = qkv; a.compat = compat; a.ld = ld; a.msg = msg;
     a.N = N; a.Npad = pdsc::attention_npad(N); a.nsplit = nsplit; a.num_tiles = tiles;
     a.nvalid = nvalid;
+    a.lse = lse;
     a.part_o = (float*)scratch;
     a.part_ml = a.part_o ? a.part_o + (size_t)bs * nsplit * a.Npad * pdsc::ATT_C : nullptr;
     hipStream_t st = (hipStream_t)stream;
@@ -344,4 +347,10 @@ int launch_attention_fp32(const float* qkv, const float* compat, long long ld, f
 extern "C" int pdsc_sc_attention(const float* qkv, const float* compat, long long ld, float* msg, void* scratch,
                                  size_t scratch_bytes, int bs, int N, int nsplit, void* stream) {
     return pdsc::launch_attention_fp32(qkv, compat, ld, msg, scratch, scratch_bytes, bs, N, nsplit, nullptr, (hipStream_t)stream);
+}
+
+extern "C" int pdsc_sc_attention_lse(const float* qkv, const float* compat, long long ld, float* msg, float* lse, void* scratch,
+                                     size_t scratch_bytes, int bs, int N, int nsplit, void* stream) {
+    PDSC_REQUIRE(lse, "pdsc_sc_attention_lse: null pointer");
+    return pdsc::launch_attention_fp32(qkv, compat, ld, msg, scratch, scratch_bytes, bs, N, nsplit, nullptr, (hipStream_t)stream, lse);
 }

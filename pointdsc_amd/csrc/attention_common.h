@@ -13,6 +13,7 @@ struct AttArgs {
     float* part_ml;          // [bs][nsplit][Npad][2]     (running max (log2 domain), partial sum)
     int N, Npad, nsplit, num_tiles;
     const int* nvalid;       // ragged batches (r06): [bs] correspondences per pair (<= N; strides stay those of N), or NULL
+    float* lse;              // f-12: [bs*N] row statistic m + log2(l) of the softmax (log2 domain) for the backward, or NULL
 };
 
 // arguments of the split-precision kernels (attention_split.hip)
@@ -44,6 +45,6 @@ typedef __attribute__((address_space(3))) void* lptr_t;
 int launch_attention_combine(const AttArgs& a, int bs, hipStream_t st);
 // exact-fp32 attention with an optional per-pair count array (ragged batches; pdsc_sc_attention = the same with NULL)
 int launch_attention_fp32(const float* qkv, const float* compat, long long ld, float* msg, void* scratch, size_t scratch_bytes, int bs, int N,
-                          int nsplit, const int* nvalid, hipStream_t st);
+                          int nsplit, const int* nvalid, hipStream_t st, float* lse = nullptr);
 
 }  // namespace pdsc

@@ -213,6 +213,39 @@ def sc_attention(qkv: torch.Tensor, compat: torch.Tensor, bs: int, n: int, nspli
 
 
 @_on_device
+def sc_attention_lse(qkv: torch.Tensor, compat: torch.Tensor, bs: int, n: int, nsplit: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """sc_attention that also leaves the softmax's row statistic: -> (msg [bs*N,128], lse [bs*N]), lse = m + log2(l) in the
+    log2 domain of the pre-scaled q.  msg is bit for bit sc_attention's at the same nsplit."""
+    lib = _lib.load()
+    qkv, compat = _chk(qkv, "qkv"), _chk(compat, "compat")
+    ld = compat.shape[-1]
+    msg = torch.empty(bs * n, 128, device=qkv.device, dtype=torch.float32)
+    lse = torch.empty(bs * n, device=qkv.device, dtype=torch.float32)
+    nb = int(lib.pdsc_attention_scratch_bytes(bs, n, nsplit))
+    scratch = torch.empty(max(nb, 16), device=qkv.device, dtype=torch.uint8)
+    _lib.check(lib.pdsc_sc_attention_lse(_p(qkv), _p(compat), ld, _p(msg), _p(lse), _p(scratch), nb, bs, n, nsplit, _stream()),
+               "pdsc_sc_attention_lse")
+    return msg, lse
+
+
+@_on_device
+def sc_attention_backward(qkv: torch.Tensor, compat: torch.Tensor, msg: torch.Tensor, lse: torch.Tensor, dmsg: torch.Tensor,
+                          bs: int, n: int, nsplit: int = 0) -> torch.Tensor:
+    """Backward of sc_attention: (qkv, compat, msg, lse) of sc_attention_lse and dmsg [bs*N,128] -> dqkv [bs*N,384], the gradient
+    with respect to the (q | k | v) rows as passed (q pre-scaled).  compat gets no gradient.  nsplit forces the number of ranges
+    the tile walk of both kernels is split into (0: the library's choice for the shape)."""
+    lib = _lib.load()
+    qkv, compat, msg, lse, dmsg = (_chk(t, name) for t, name in ((qkv, "qkv"), (compat, "compat"), (msg, "msg"), (lse, "lse"),
+                                                                 (dmsg, "dmsg")))
+    dqkv = torch.empty(bs * n, 384, device=qkv.device, dtype=torch.float32)
+    nb = int(lib.pdsc_attention_backward_split_workspace_bytes(bs, n, nsplit))
+    ws = torch.empty(max(nb, 16), device=qkv.device, dtype=torch.uint8)
+    _lib.check(lib.pdsc_sc_attention_backward_split(_p(qkv), _p(compat), compat.shape[-1], _p(msg), _p(lse), _p(dmsg), _p(dqkv), _p(ws),
+                                                    nb, bs, n, nsplit, _stream()), "pdsc_sc_attention_backward")
+    return dqkv
+
+
+@_on_device
 def pack_qkv_split(qkv: torch.Tensor, bs: int, n: int):
     """fp32 (q|k|v) rows [bs*N,384] -> (q_split, kv_tiles) byte tensors in the layout of csrc/split_layout.h."""
     lib = _lib.load()

@@ -19,7 +19,11 @@ and of section 8 f-9 (the raw-cloud path: the many-workgroups chains in front of
 
 and of section 8 f-8 (pose-graph optimisation):
 
-    python tools/kernel_resources.py posegraph"""
+    python tools/kernel_resources.py posegraph
+
+and of section 8 f-12 (the attention's backward):
+
+    python tools/kernel_resources.py att_bwd sc_attention_kernel attention_combine"""
 import re
 import subprocess
 import sys
