@@ -1011,6 +1011,23 @@ int pdsc_sc_attention_backward_split(const float* qkv, const float* compat, long
                                      const float* dmsg, float* dqkv, void* workspace, size_t workspace_bytes, int bs, int N,
                                      int nsplit, void* stream);
 
+/* ---- backward of the feature-similarity matrix -------------------------------------------------
+ * What lets a loss of res['M'] (the train-mode forward's M, pdsc_feature_compat) reach the weights: for an upstream gradient
+ * dM [bs][N][ld >= N] (fp32, NOT assumed symmetric; the pad columns [N, ld) are never read) and normed = F [bs*N][128]
+ *   live_ij = (i != j) and 0 <= raw_ij <= 1 with raw_ij = 1 - (1 - <F_i, F_j>) / sigma^2 computed by the text pdsc_feature_compat
+ *   uses (the mask is that of the M the forward wrote; inclusive, as torch.clamp's backward);   g_ij = live_ij ? dM_ij : 0
+ *   dnormed [bs*N][128] (fp32, or NULL): dF_i = (1 / sigma^2) sum_j (g_ij + g_ji) F_j, both products exact fp32 on
+ *   v_mfma_f32_32x32x2_f32;   dsigma [1] (fp64, or NULL) = (2 / sigma^3) sum_b sum_ij g_ij (1 - <F_i, F_j>).
+ * At least one of the two must be asked for; either alone gives the bits it has in the pair.  Dead entries, the diagonal and
+ * everything outside the N x N matrix are selected to 0: NaN or inf there does not reach the result.  No floating-point atomics:
+ * one workgroup owns 128 rows of a pair, dsigma goes through fp64 partials in `ws` (pdsc_feature_compat_backward_workspace_bytes)
+ * that a finishing launch adds in index order; repeat calls are bit-identical, and a pair's dnormed does not depend on the batch
+ * it shares the launch with.  Asynchronous on `stream`, no allocation, no synchronisation.  Bad arguments (null pointer, bs or
+ * N <= 0, ld < N, workspace too small) return an error with nothing enqueued. */
+size_t pdsc_feature_compat_backward_workspace_bytes(int bs, int N);
+int pdsc_feature_compat_backward(const float* normed, const float* sigma, const float* dM, long long ld, float* dnormed,
+                                 double* dsigma, void* ws, size_t ws_bytes, int bs, int N, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -140,6 +140,8 @@ SIGNATURES = {
     "pdsc_attention_backward_default_split": (_i, [_i, _i]),
     "pdsc_attention_backward_split_workspace_bytes": (_sz, [_i, _i, _i]),
     "pdsc_sc_attention_backward_split": (_i, [_vp, _vp, _ll, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _vp]),
+    "pdsc_feature_compat_backward_workspace_bytes": (_sz, [_i, _i]),
+    "pdsc_feature_compat_backward": (_i, [_vp, _vp, _vp, _ll, _vp, _vp, _vp, _sz, _i, _i, _vp]),
     "pdsc_icp_workspace_bytes": (_sz, [_i, _i, _i]),
     "pdsc_icp_refine": (_i, [_vp, _vp, _vp, _vp, _vp, C.c_double, C.c_double, C.c_double, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                              _sz, _i, _i, _i, _vp]),

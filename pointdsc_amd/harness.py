@@ -426,3 +426,60 @@ def validate(model, batches: Iterable[Dict[str, torch.Tensor]], balanced: bool =
             counts += ok.to(torch.float64)
         means = (sums / counts).cpu().tolist()          # the one read-back (a meter that never got a value is NaN)
     return dict(zip(names, means))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the training loop (libs/trainer.py:79-136)
+# ---------------------------------------------------------------------------------------------------------------------------
+def train_epoch(model, batches: Iterable[Dict[str, torch.Tensor]], optimizer, weights=(1.0, 1.0, 0.0), balanced: bool = False,
+                re_thre: float = 15.0, te_thre: float = 30.0) -> Dict[str, float]:
+    """``Trainer.train_epoch`` (libs/trainer.py:79-136) on the device: for every batch (the dict ``validate`` takes) zero_grad, the
+    train()-mode forward of `model` (a ``training.TrainablePointDSC`` in train() mode), the three losses of pointdsc_amd.losses,
+    ``weights[0] class_loss + weights[1] sm_loss``, backward, and the reference's rule that the optimiser step is skipped when any
+    gradient is non-finite (one boolean per step is read for it, as the reference reads one).  `balanced` is the reference's
+    config.balanced (default False).  The transformation loss has no gradient here: it is a meter, and a weight above 0 for it raises
+    NotImplementedError (the reference's default is 0.0).
+    -> the nine meters of the reference (running means kept on the device in fp64, NaN values skipped, as in ``validate``), and
+    "loss_first" / "loss_last" (the weighted sum at the first and the last step), "steps", "skipped" -- ONE read-back at the end."""
+    from .losses import ClassificationLoss, SpectralMatchingLoss, transformation_loss_raw
+    w_cls, w_sm, w_tr = (float(w) for w in weights)
+    if w_tr > 0.0:
+        raise NotImplementedError("the transformation loss has no gradient on the device (forward only): use weight 0.0, the reference's default")
+    if not model.training:
+        raise RuntimeError("train_epoch needs the model in train() mode")
+    dev = next(model.parameters()).device
+    cls_fn, sm_fn = ClassificationLoss(balanced), SpectralMatchingLoss(balanced)
+    params = [p for p in model.parameters() if p.requires_grad]
+    sums = torch.zeros(len(VALIDATE_NAMES), device=dev, dtype=torch.float64)
+    counts = torch.zeros(len(VALIDATE_NAMES), device=dev, dtype=torch.float64)
+    totals, steps, skipped = [], 0, 0
+    for batch in batches:
+        d = {k: v.to(dev) for k, v in batch.items() if torch.is_tensor(v)}
+        gt = d["gt_labels"]
+        optimizer.zero_grad()
+        res = model({k: d[k] for k in ("corr_pos", "src_keypts", "tgt_keypts")})
+        logits = res["final_labels"]
+        cls = cls_fn(logits, gt, device_stats=True)
+        sm = sm_fn(res["M"], gt)
+        loss = w_cls * cls["loss"] + w_sm * sm
+        loss.backward()
+        grads = [p.grad for p in params if p.grad is not None]
+        if bool(torch.stack([torch.isfinite(g).all() for g in grads]).all()):
+            optimizer.step()
+        else:
+            skipped += 1
+        steps += 1
+        with torch.no_grad():
+            tr = transformation_loss_raw(res["final_trans"], d["gt_trans"], d["src_keypts"], d["tgt_keypts"], logits, re_thre, te_thre)
+            vals = torch.stack([cls["loss"].detach().double(), tr[0], sm.detach().double(), tr[1], tr[2], tr[3],
+                                cls["precision"], cls["recall"], cls["f1"]])
+            ok = ~torch.isnan(vals) & ~torch.isnan(loss.detach())          # the reference updates no meter on a NaN loss
+            sums += torch.where(ok, vals, torch.zeros_like(vals))
+            counts += ok.to(torch.float64)
+            totals.append(loss.detach().double())
+    if not steps:
+        raise ValueError("train_epoch: no batch")
+    out = torch.cat([sums / counts, torch.stack([totals[0], totals[-1]])]).cpu().tolist()          # the one read-back
+    res = dict(zip(VALIDATE_NAMES, out))
+    res.update(loss_first=out[-2], loss_last=out[-1], steps=steps, skipped=skipped)
+    return res

@@ -359,8 +359,9 @@ class PointDSC(nn.Module):
         if self.training:
             raise RuntimeError(
                 "call .eval() first: BatchNorm is folded with its running statistics.  The train()-mode forward (batch "
-                "statistics + autograd, reference libs/trainer.py:68-156) is out of scope; the validation forward "
-                "(eval() mode without the 'testing' key, libs/trainer.py:158-222) is supported.")
+                "statistics + autograd, reference libs/trainer.py:68-156) is pointdsc_amd.training.TrainablePointDSC (the same "
+                "parameters and state_dict) or training.train_forward(model, data); the validation forward (eval() mode without "
+                "the 'testing' key, libs/trainer.py:158-222) is supported here.")
         corr_pos, src_keypts, tgt_keypts = data["corr_pos"], data["src_keypts"], data["tgt_keypts"]
         if isinstance(corr_pos, (list, tuple)):
             return self._forward_list(list(corr_pos), list(src_keypts), list(tgt_keypts), testing)

@@ -412,6 +412,28 @@ def feature_compat(normed: torch.Tensor, sigma: torch.Tensor, bs: int, n: int) -
 
 
 @_on_device
+def feature_compat_backward(normed: torch.Tensor, sigma: torch.Tensor, dM: torch.Tensor, bs: int, n: int, want_dnormed: bool = True,
+                            want_dsigma: bool = True):
+    """Backward of feature_compat: normed [bs*N,128], sigma [1], dM [bs,N,ld >= N] (any values, not assumed symmetric; the pad
+    columns are never read) -> (dnormed fp32 [bs*N,128] or None, dsigma fp64 [1] or None).  pdsc_feature_compat_backward."""
+    if not (want_dnormed or want_dsigma):
+        raise ValueError("feature_compat_backward: ask for at least one of dnormed and dsigma")
+    lib = _lib.load()
+    normed, sig, dM = _chk(normed, "normed"), _chk(sigma.reshape(-1), "sigma"), _chk(dM, "dM")
+    if normed.numel() != bs * n * 128 or normed.shape[-1] != 128 or sig.numel() != 1:
+        raise ValueError("normed must hold bs * N rows of 128 channels and sigma one value")
+    if dM.dim() != 3 or dM.shape[0] != bs or dM.shape[1] != n or dM.shape[2] < n:
+        raise ValueError(f"dM must be [bs,N,N] or [bs,N,ld >= N], got {tuple(dM.shape)}")
+    nb = int(lib.pdsc_feature_compat_backward_workspace_bytes(bs, n))
+    ws = torch.empty(max(nb // 8, 1), device=normed.device, dtype=torch.float64)
+    dnormed = torch.empty(bs * n, 128, device=normed.device, dtype=torch.float32) if want_dnormed else None
+    dsigma = torch.empty(1, device=normed.device, dtype=torch.float64) if want_dsigma else None
+    _lib.check(lib.pdsc_feature_compat_backward(_p(normed), _p(sig), _p(dM), dM.shape[2], _p(dnormed), _p(dsigma), _p(ws), ws.numel() * 8,
+                                                bs, n, _stream()), "pdsc_feature_compat_backward")
+    return dnormed, dsigma
+
+
+@_on_device
 def normalize_confidence(feat, h2, w3, b3) -> Tuple[torch.Tensor, torch.Tensor]:
     lib = _lib.load()
     feat, h2, w3, b3 = _chk(feat, "feat"), _chk(h2, "h2"), _chk(w3.reshape(-1), "w3"), _chk(b3.reshape(-1), "b3")

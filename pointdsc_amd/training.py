@@ -1,10 +1,14 @@
-"""The differentiable spatial-consistency attention (f-12) and the reference's NonLocalBlock built on it.
+"""The training path: the differentiable spatial-consistency attention (f-12), the reference's NonLocalBlock built on it, and
+(f-13) the differentiable feature-similarity matrix, the train()-mode forward and ``TrainablePointDSC``.
 
-Of the training path only the attention needs a hand-written backward: its 1x1 convolutions, batch-norms and ReLUs are operations
-torch differentiates well, while the attention in torch materialises bs x N x N scores twice per layer.  ``sc_attention`` is a
-``torch.autograd.Function`` over ``ops.sc_attention_lse`` / ``ops.sc_attention_backward``; ``NonLocalBlock`` is the reference block
-(models/PointDSC.py:9-45) with torch layers around it, so a trainer can swap it in layer by layer.  ``PointDSC.forward`` in
-``train()`` mode is not part of this.
+Of the training path two operations need a hand-written backward: the attention (in torch it materialises bs x N x N scores twice
+per layer) and the feature-similarity matrix M (its gradient for an arbitrary dM is a second N x N x 128 product behind a clamp
+mask).  ``sc_attention`` is a ``torch.autograd.Function`` over ``ops.sc_attention_lse`` / ``ops.sc_attention_backward``;
+``feature_similarity`` one over ``ops.feature_compat`` / ``ops.feature_compat_backward``.  The 1x1 convolutions, batch-norms and
+ReLUs around them are operations torch differentiates well and stay torch's.  ``NonLocalBlock`` is the reference block
+(models/PointDSC.py:9-45) for a trainer that swaps layer by layer; ``train_forward`` is the reference's whole forward without the
+'testing' key (models/PointDSC.py:143-197) on a ``PointDSC`` module's own parameters, and ``TrainablePointDSC`` the module that
+calls it in ``train()`` mode.  ``PointDSC.forward`` itself keeps refusing ``train()`` mode.
 """
 from __future__ import annotations
 
@@ -12,8 +16,10 @@ import math
 
 import torch
 import torch.nn as nn
+import torch.nn.functional as F
 
-from . import ops
+from . import _lib, ops
+from .model import PointDSC
 
 CHANNELS = 128
 # q rows enter the library pre-scaled: scores are taken in the log2 domain, p = exp2(compat * <q', k> - lse)
@@ -105,3 +111,141 @@ class NonLocalBlock(nn.Module):
         v = self.projection_v(feat).transpose(1, 2)
         message = sc_attention(q.contiguous(), k.contiguous(), v.contiguous(), attention).transpose(1, 2)
         return feat + self.fc_message(message)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# f-13: the differentiable M, the train()-mode forward
+# ---------------------------------------------------------------------------------------------------------------------------
+class _SCAttentionRows(torch.autograd.Function):
+    """_SCAttention on rows as the library takes them: qkv [bs*N,384] = (q | k | v) with q pre-scaled, as ONE GEMM with the
+    concatenated weights leaves them -- no cat and no transposes of activations; the gradient is the one with respect to these rows
+    (the q scale lives in the weights, where autograd finds it)."""
+
+    @staticmethod
+    def forward(ctx, qkv, compat, bs, n):
+        msg, lse = ops.sc_attention_lse(qkv, compat, bs, n)
+        ctx.save_for_backward(qkv, compat, msg, lse)
+        ctx.shape = (bs, n)
+        return msg
+
+    @staticmethod
+    def backward(ctx, dmsg):
+        qkv, compat, msg, lse = ctx.saved_tensors
+        bs, n = ctx.shape
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None
+        return ops.sc_attention_backward(qkv, compat, msg, lse, dmsg.contiguous(), bs, n), None, None, None
+
+
+class _FeatureSimilarity(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, normed, sigma):
+        bs, n, _ = normed.shape
+        ctx.save_for_backward(normed, sigma)                  # no N x N tensor is kept: the backward recomputes the mask
+        return ops.feature_compat(normed.reshape(bs * n, CHANNELS), sigma, bs, n)
+
+    @staticmethod
+    def backward(ctx, dM):
+        normed, sigma = ctx.saved_tensors
+        bs, n, _ = normed.shape
+        need_n, need_s = ctx.needs_input_grad
+        if not (need_n or need_s):
+            return None, None
+        dn, ds = ops.feature_compat_backward(normed.reshape(bs * n, CHANNELS), sigma, dM, bs, n, want_dnormed=need_n, want_dsigma=need_s)
+        return (dn.view(bs, n, CHANNELS) if need_n else None), (ds.to(torch.float32).reshape(sigma.shape) if need_s else None)
+
+
+def feature_similarity(normed: torch.Tensor, sigma: torch.Tensor) -> torch.Tensor:
+    """M = clamp(1 - (1 - F F^T) / sigma^2, 0, 1) with a zero diagonal (models/PointDSC.py:160-163), with gradients for the
+    features and sigma.  normed [bs,N,128] fp32 (unit rows), sigma one fp32 value -> M [bs,N,N], bit for bit ops.feature_compat's."""
+    for t, name in ((normed, "normed"), (sigma, "sigma")):
+        if not t.is_cuda:
+            raise RuntimeError(f"{name} must live on the GPU (pointdsc_amd has no CPU path)")
+        if t.dtype != torch.float32:
+            raise TypeError(f"{name} must be torch.float32, got {t.dtype}")
+    if normed.dim() != 3 or normed.shape[-1] != CHANNELS:
+        raise ValueError(f"feature_similarity: normed must be [bs,N,{CHANNELS}], got {tuple(normed.shape)}")
+    if sigma.numel() != 1:
+        raise ValueError(f"feature_similarity: sigma must hold one value, got {tuple(sigma.shape)}")
+    return _FeatureSimilarity.apply(normed.contiguous(), sigma)
+
+
+def _conv_rows(conv: nn.Conv1d, x: torch.Tensor) -> torch.Tensor:
+    """A 1x1 Conv1d on channel-last rows [M, Cin] -> [M, Cout]."""
+    return F.linear(x, conv.weight[:, :, 0], conv.bias)
+
+
+def _train_encoder(enc, x: torch.Tensor, compat: torch.Tensor, bs: int, n: int) -> torch.Tensor:
+    """NonLocalNet.forward (models/PointDSC.py:65-77) on rows [bs*N, C].  The batch-norms are the modules' own forward on (M, C)
+    rows (BatchNorm1d takes that layout: the statistics run over the bs * N rows exactly as over [bs, C, N]): F.batch_norm on
+    the module's buffers with batch statistics, running_mean / running_var / num_batches_tracked updated by torch itself."""
+    feat = _conv_rows(enc.layer0, x)
+    for i in range(enc.num_layers):
+        pcn, nl = enc.blocks[f"PointCN_layer_{i}"], enc.blocks[f"NonLocal_layer_{i}"]
+        feat = F.relu(pcn[1](_conv_rows(pcn[0], feat)))
+        w = torch.cat((nl.projection_q.weight[:, :, 0] * Q_SCALE, nl.projection_k.weight[:, :, 0], nl.projection_v.weight[:, :, 0]))
+        b = torch.cat((nl.projection_q.bias * Q_SCALE, nl.projection_k.bias, nl.projection_v.bias))
+        msg = _SCAttentionRows.apply(F.linear(feat, w, b), compat, bs, n)
+        fc = nl.fc_message
+        h = F.relu(fc[1](_conv_rows(fc[0], msg)))
+        h = F.relu(fc[4](_conv_rows(fc[3], h)))
+        feat = feat + _conv_rows(fc[6], h)
+    return feat
+
+
+def train_forward(model: PointDSC, data) -> dict:
+    """The reference's forward without the 'testing' key (models/PointDSC.py:143-197) in train() mode, on `model`'s own Parameters
+    and buffers: batch-statistics batch-norm (running statistics updated as torch's BatchNorm1d does), autograd through the
+    encoder, the classification head and M.  data: corr_pos [bs,N,in_dim], src_keypts, tgt_keypts [bs,N,3] on the GPU.
+    -> {'final_trans': the best seed hypothesis [bs,4,4] (no gradient), 'final_labels': the logits [bs,N], 'M': [bs,N,N]}.
+    The spatial-consistency matrix, the seeds and everything behind them (kNN, power iteration, Procrustes, vote) carry no gradient,
+    as in the reference, and run as the library's stage ops."""
+    if not model.training:
+        raise RuntimeError("train_forward needs the module in train() mode; in eval() mode call the module (PointDSC.forward)")
+    if "testing" in data.keys():
+        raise ValueError("the 'testing' key belongs to eval() mode: the reference never runs its testing forward in train() mode")
+    corr_pos, src, tgt = data["corr_pos"], data["src_keypts"], data["tgt_keypts"]
+    for t, name in ((corr_pos, "corr_pos"), (src, "src_keypts"), (tgt, "tgt_keypts")):
+        if not t.is_cuda:
+            raise RuntimeError(f"{name} must live on the GPU (pointdsc_amd has no CPU path)")
+    dev = corr_pos.device
+    corr_pos = corr_pos.detach().to(torch.float32).contiguous()
+    src = src.detach().to(device=dev, dtype=torch.float32).contiguous()
+    tgt = tgt.detach().to(device=dev, dtype=torch.float32).contiguous()
+    bs, n = corr_pos.shape[0], corr_pos.shape[1]
+    if corr_pos.shape[2] != model.in_dim or src.shape != (bs, n, 3) or tgt.shape != (bs, n, 3):
+        raise ValueError("bad input shapes for train_forward")
+    num_seeds, k = int(n * model.ratio), min(model.k, n - 1)
+    if num_seeds < 1 or k < 1:
+        raise ValueError(f"train_forward needs int(N * ratio) >= 1 seeds and N >= 2 (N = {n}, ratio = {model.ratio})")
+    with torch.cuda.device(dev):
+        with torch.no_grad():
+            compat = _pad_compat(ops.spatial_compat(src, tgt, model.sigma_spat), n)
+        feat = _train_encoder(model.encoder, corr_pos.view(bs * n, model.in_dim), compat, bs, n)
+        normed = F.normalize(feat, p=2, dim=-1).view(bs, n, CHANNELS)
+        cls = model.classification
+        logits = _conv_rows(cls[4], F.relu(_conv_rows(cls[2], F.relu(_conv_rows(cls[0], feat))))).view(bs, n)
+        M = feature_similarity(normed, model.sigma)
+        with torch.no_grad():
+            nd, sigma = normed.detach(), model.sigma.detach()
+            seeds = ops.rank_select(logits.detach().contiguous(), num_seeds)          # argsort(logits, descending)[:, :num_seeds]
+            knn_idx = ops.knn_seeds(nd, seeds, k, form="matrix")
+            iters, mask, _ = ops.seed_power_iteration(nd, src, tgt, knn_idx, sigma, model.sigma_spat, model.num_iterations)
+            if bs > 1:
+                # the reference takes the power iteration's early exit over the seeds of ALL pairs (one allclose over [bs*S, k])
+                _lib.check(_lib.load().pdsc_conv_mask_all_pairs(ops._p(mask), bs, ops._stream()), "pdsc_conv_mask_all_pairs")
+            seed_trans, _ = ops.seed_transforms(src, tgt, knn_idx, iters, mask, model.num_iterations)
+            final_trans = ops.score_hypotheses(seed_trans, src, tgt, float(model.inlier_threshold))[2]
+    return {"final_trans": final_trans, "final_labels": logits, "M": M}
+
+
+class TrainablePointDSC(PointDSC):
+    """``PointDSC`` a trainer can hold: the same constructor, parameters and 358-key state_dict (strict loading both ways).
+    In ``train()`` mode ``forward`` is ``train_forward`` (batch statistics, autograd; the reference's Trainer.train_epoch,
+    libs/trainer.py:79-136, runs on it unchanged); in ``eval()`` mode it is ``PointDSC.forward``, which sees every optimiser step
+    through the weights' version counters."""
+
+    def forward(self, data):
+        if self.training:
+            return train_forward(self, data)
+        return super().forward(data)

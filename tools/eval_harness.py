@@ -124,6 +124,32 @@ def validate(a):
         print(f"{k}: {v:.6f}")
 
 
+def train(a):
+    """--train: a few optimiser steps of harness.train_epoch on the synthetic batches --validate uses; the validation meters of
+    the same batches before and after."""
+    from pointdsc_amd import TrainablePointDSC, synthetic
+    model = TrainablePointDSC(**dict(workloads.BASE_MODEL))
+    if a.snapshot:
+        print(model.load_state_dict(torch.load(a.snapshot, map_location="cpu"), strict=False))
+    else:
+        model.load_state_dict(workloads.state_dict("n5000_b32", model.state_dict()))
+    model = model.cuda()
+    batches = [synthetic.make_batch(16, 1000, seed=100 + 16 * i, inlier_ratio=0.3) for i in range(a.num_batches)]
+    optimizer = torch.optim.Adam(model.parameters(), lr=a.lr, weight_decay=1e-6)          # config.py:48-53
+    before = harness.validate(model.eval(), batches)
+    steps = [batches[i % len(batches)] for i in range(a.train_steps)]
+    meters = harness.train_epoch(model.train(), steps, optimizer)
+    after = harness.validate(model.eval(), batches)
+    if a.json:
+        print(json.dumps({"before": before, "train": meters, "after": after}))
+        return
+    print(f"{a.train_steps} Adam steps (lr {a.lr}) over {a.num_batches} synthetic batches of 16 pairs x 1000 correspondences; "
+          f"{meters['skipped']} skipped; weighted loss {meters['loss_first']:.6f} -> {meters['loss_last']:.6f}")
+    print(f"{'meter':18s} {'validation before':>18s} {'training mean':>18s} {'validation after':>18s}")
+    for k in harness.VALIDATE_NAMES:
+        print(f"{k:18s} {before[k]:18.6f} {meters[k]:18.6f} {after[k]:18.6f}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--pcd1", default=None, help="PLY file (binary LE / ascii, float xyz); default: the demo fixture")
@@ -152,8 +178,17 @@ def main():
     ap.add_argument("--validate", action="store_true", help="the validation loop of libs/trainer.py:158-222 on the device "
                     "(harness.validate: validation forward + the three losses) over --num-batches synthetic batches (bs 16, N 1000)")
     ap.add_argument("--num-batches", type=int, default=4, help="with --validate: batches of 16 pairs")
+    ap.add_argument("--train", action="store_true", help="the training loop of libs/trainer.py:79-136 on the device (harness.train_epoch on a "
+                    "TrainablePointDSC: train()-mode forward, classification + spectral-matching loss, backward, Adam) for --train-steps "
+                    "steps over the --num-batches synthetic batches of --validate, with the validation meters before and after")
+    ap.add_argument("--train-steps", type=int, default=8)
+    ap.add_argument("--lr", type=float, default=1e-4, help="with --train (config.py:52)")
     ap.add_argument("--json", action="store_true")
     a = ap.parse_args()
+    if a.train:
+        if a.validate or a.baseline or a.pcd1 or a.pcd2 or a.multiway or a.posegraph:
+            ap.error("--train runs the model on synthetic batches: not with --validate, --baseline, --pcd1, --pcd2, --multiway or --posegraph")
+        return train(a)
     if a.validate:
         if a.baseline or a.pcd1 or a.pcd2 or a.multiway or a.posegraph:
             ap.error("--validate runs the model on synthetic batches: not with --baseline, --pcd1, --pcd2, --multiway or --posegraph")

@@ -23,7 +23,11 @@ and of section 8 f-8 (pose-graph optimisation):
 
 and of section 8 f-12 (the attention's backward):
 
-    python tools/kernel_resources.py att_bwd sc_attention_kernel attention_combine"""
+    python tools/kernel_resources.py att_bwd sc_attention_kernel attention_combine
+
+and of section 8 f-13 (the backward of the feature-similarity matrix, next to its forward and its sibling of the loss):
+
+    python tools/kernel_resources.py feature_compat_backward gram_rows_kernel sm_loss_features_kernel"""
 import re
 import subprocess
 import sys

@@ -1,0 +1,137 @@
+#!/usr/bin/env python3
+"""Time of the training path's f-13 pieces at the training shape (bs 16, N 1000, 12 layers), next to torch on the same device.
+
+  kernel      training.feature_similarity forward + backward against torch's autograd of the reference's three formula lines
+              (models/PointDSC.py:160-163), for a given dM;
+  whole step  zero_grad, train()-mode forward, classification + spectral-matching loss, backward, Adam: TrainablePointDSC with
+              the device losses against the pure-torch model of the tests (tests/train_oracle.TorchPointDSC: formula attention,
+              formula M, torch losses; it has NO tail -- no seeds, kNN, power iteration, Procrustes or vote -- so the comparison
+              favours it) with the same weights on the same batch.
+
+The method of tools/attention_backward_bench.py: device events around a window of back-to-back calls that fills `--window` seconds
+after `--warmup` calls; the two sides alternate inside one process; the median of `--rounds` windows is printed with the spread.
+These are CALL times, host work included.
+
+    --profile-steps K    run K device steps and exit: the program of the one `rocprofv3 --kernel-trace --stats` run
+    --breakdown FILE     group the per-kernel table tools/rocpd_kernel_stats.py made of that run into the step's six parts"""
+import argparse
+import re
+import statistics
+import sys
+from pathlib import Path
+
+ROOT = Path(__file__).resolve().parents[1]
+sys.path.insert(0, str(ROOT))
+sys.path.insert(0, str(ROOT / "tests"))
+
+GROUPS = [      # first match wins
+    ("attention forward", r"sc_attention_kernel|attention_combine_kernel"),
+    ("attention backward", r"att_bwd_"),
+    ("M forward + backward", r"gram_rows_kernel<2|feature_compat_backward"),
+    ("losses", r"pdsc::(cls_|sm_loss_|trans_partial|trans_finish)"),
+    ("tail and compat (the library's other kernels)", r"pdsc::"),
+    ("torch (GEMMs, batch-norm, point-wise, optimiser)", r"."),
+]
+
+
+def breakdown(path):
+    totals, calls, total = {g: 0.0 for g, _ in GROUPS}, {g: 0 for g, _ in GROUPS}, 0.0
+    for line in Path(path).read_text().splitlines():
+        m = re.match(r"^(.{64}) +(\d+) +([0-9.]+) ", line)
+        if not m or line.startswith("kernel "):
+            continue
+        name, n, us = m.group(1), int(m.group(2)), float(m.group(3))
+        group = next(g for g, pat in GROUPS if re.search(pat, name))
+        totals[group] += us
+        calls[group] += n
+        total += us
+    print(f"# {path}: kernel time by part of the step, total {total / 1e3:.3f} ms")
+    print(f"{'part':52s} {'launches':>9s} {'total_us':>11s} {'%':>6s}")
+    for g, _ in GROUPS:
+        print(f"{g:52s} {calls[g]:9d} {totals[g]:11.1f} {100 * totals[g] / total:6.2f}")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--window", type=float, default=0.5, help="seconds of back-to-back calls per timed window")
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--bs", type=int, default=16)
+    ap.add_argument("--n", type=int, default=1000)
+    ap.add_argument("--layers", type=int, default=12)
+    ap.add_argument("--profile-steps", type=int, default=0)
+    ap.add_argument("--breakdown", default=None)
+    a = ap.parse_args()
+    if a.breakdown:
+        return breakdown(a.breakdown)
+
+    import torch
+    import torch.nn.functional as F
+    import train_oracle as TO
+    from loss_bench import timed, torch_sm_matrix
+    from pointdsc_amd import ClassificationLoss, PointDSC, SpectralMatchingLoss, synthetic, training
+    assert torch.cuda.is_available(), "train_step_bench needs the GPU: a CPU run gives no time"
+    dev, bs, n = "cuda:0", a.bs, a.n
+
+    def spread(ts):
+        return f"{statistics.median(ts):10.1f} ({min(ts):.1f} .. {max(ts):.1f})"
+
+    def compare(name, ours, theirs):
+        t_ours, t_theirs = [], []
+        for _ in range(a.rounds):                         # alternate the two sides
+            t_ours.append(timed(ours, a.warmup, a.window)[0])
+            t_theirs.append(timed(theirs, a.warmup, a.window)[0])
+        mo, mt = statistics.median(t_ours), statistics.median(t_theirs)
+        print(f"  {name:42s} device {spread(t_ours)}   torch {spread(t_theirs)}   torch / device {mt / mo:6.2f}")
+
+    state = synthetic.make_state_dict(PointDSC(num_layers=a.layers).state_dict(), seed=1)
+    batch = {k: v.to(dev) for k, v in synthetic.make_batch(bs, n, seed=100, inlier_ratio=0.3).items()}
+    data = {k: batch[k] for k in ("corr_pos", "src_keypts", "tgt_keypts")}
+    gt = batch["gt_labels"]
+    model = training.TrainablePointDSC(num_layers=a.layers)
+    model.load_state_dict(state, strict=True)
+    model = model.to(dev).train()
+    opt = torch.optim.Adam(model.parameters(), lr=1e-4, weight_decay=1e-6)
+    cls_fn, sm_fn = ClassificationLoss(False), SpectralMatchingLoss(False)
+
+    def device_step():
+        opt.zero_grad()
+        res = model(data)
+        loss = cls_fn(res["final_labels"], gt, device_stats=True)["loss"] + sm_fn(res["M"], gt)
+        loss.backward()
+        opt.step()
+        return loss
+
+    if a.profile_steps:
+        for _ in range(a.profile_steps):
+            device_step()
+        torch.cuda.synchronize()
+        return
+
+    print(f"bs={bs} N={n} layers={a.layers}: microseconds per call, median of {a.rounds} windows of {a.window} s (min .. max)")
+    gen = torch.Generator().manual_seed(bs * n)
+    normed = F.normalize(torch.randn(bs, n, 128, generator=gen), dim=-1).to(dev).requires_grad_(True)
+    sigma = torch.tensor([1.0], device=dev, requires_grad=True)
+    dM = torch.randn(bs, n, n, generator=gen).to(dev)
+    compare("feature_similarity forward + backward",
+            lambda: torch.autograd.grad(training.feature_similarity(normed, sigma), (normed, sigma), dM),
+            lambda: torch.autograd.grad(TO.formula_lines(normed, sigma), (normed, sigma), dM))
+
+    ref = TO.TorchPointDSC(num_layers=a.layers)
+    ref.load_state_dict(state, strict=True)
+    ref = ref.to(dev).train()
+    ref_opt = torch.optim.Adam(ref.parameters(), lr=1e-4, weight_decay=1e-6)
+
+    def torch_step():
+        ref_opt.zero_grad()
+        logits, M, _ = ref(data["corr_pos"], data["src_keypts"], data["tgt_keypts"])
+        loss = F.binary_cross_entropy_with_logits(logits, gt) + torch_sm_matrix(M, gt, False)
+        loss.backward()
+        ref_opt.step()
+        return loss
+
+    compare("training step (forward, 2 losses, backward, Adam)", device_step, torch_step)
+
+
+if __name__ == "__main__":
+    main()
