@@ -1028,6 +1028,34 @@ size_t pdsc_feature_compat_backward_workspace_bytes(int bs, int N);
 int pdsc_feature_compat_backward(const float* normed, const float* sigma, const float* dM, long long ld, float* dnormed,
                                  double* dsigma, void* ws, size_t ws_bytes, int bs, int N, void* stream);
 
+/* ---- transformation loss with a gradient: backward of the per-seed solver -----------------------
+ * pdsc_seed_solve_backward: for an upstream gradient d_seed_trans [bs][S][16] of the hypotheses pdsc_seed_transforms writes (row 3
+ * of every 4x4 is ignored), the gradient of the whole per-seed chain of models/PointDSC.py:248-320 -- gather, k x k feature *
+ * spatial matrix, power iteration, weight normalisation, rigid_transform_3d -- with respect to the features and sigma:
+ *   dnormed [bs][N][128] (fp32, or NULL; every row is written, rows no active seed names are 0) and dsigma [1] (fp64, or NULL).
+ * normed, src, tgt, knn_idx, sigma, sigma_spat, num_iterations as pdsc_seed_power_iteration takes them (1 <= k <= PDSC_MAX_K,
+ * 0 <= num_iterations <= PDSC_MAX_POWER_ITERS); conv_mask [bs] as pdsc_seed_transforms takes it (after pdsc_conv_mask_all_pairs
+ * where the forward applied it): the iterate T the forward chose is replayed, nothing else of the forward is read.
+ * One wavefront per seed rebuilds G = F F^T (accumulated in fp64) and M, keeps them in LDS, replays v_1 .. v_T, redoes the
+ * Procrustes (3x3 part in fp64 registers) and walks the chain backwards.  A seed whose twelve upstream values are all zero returns
+ * at once.  num_iterations == 0: v = 1, no path to the features -- both gradients are exact zeros.
+ * No floating-point atomics: per-seed k x 128 blocks and fp64 dsigma terms in `ws`, then an owner pass that adds the blocks of a
+ * row in (seed, neighbour) order; repeat calls are bit-identical.  An entry of knn_idx outside [0, N) is never used as an address:
+ * that seed's block and dsigma term become NaN.  A seed whose M v is the zero vector gives NaN, as torch's autograd does.
+ * src, tgt, sigma_spat and knn_idx get no gradient.  Asynchronous on `stream`, no allocation, no synchronisation.  Bad arguments
+ * (null pointer, sizes out of range, workspace too small) return an error with nothing enqueued. */
+size_t pdsc_seed_solve_backward_workspace_bytes(int bs, int N, int S, int k);
+int pdsc_seed_solve_backward(const float* normed, const float* src, const float* tgt, const int* knn_idx, const float* sigma,
+                             const float* sigma_spat, const unsigned int* conv_mask, const float* d_seed_trans, float* dnormed,
+                             double* dsigma, void* ws, size_t ws_bytes, int bs, int N, int S, int k, int num_iterations,
+                             void* stream);
+
+/* d loss / d trans of the value pdsc_transformation_loss returns in out[0]: dtrans [bs][16] fp64, row 3 of every 4x4 zero.
+ *   d / dT_i[r][c] = (2 / (bs bs N)) sum_(j,n) (R_i src[i][n] + t_i - tgt[j][n])_r (src[i][n]_c | 1): the reference's broadcast
+ *   over the batch included; a pair with no probs > 0 gets exact zeros.  fp64 sums in a fixed order; workspace as the losses'. */
+int pdsc_transformation_loss_grad(const float* trans, const float* src, const float* tgt, const float* probs, double* dtrans,
+                                  void* ws, size_t ws_bytes, int bs, int N, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

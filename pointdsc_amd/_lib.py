@@ -142,6 +142,9 @@ SIGNATURES = {
     "pdsc_sc_attention_backward_split": (_i, [_vp, _vp, _ll, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _vp]),
     "pdsc_feature_compat_backward_workspace_bytes": (_sz, [_i, _i]),
     "pdsc_feature_compat_backward": (_i, [_vp, _vp, _vp, _ll, _vp, _vp, _vp, _sz, _i, _i, _vp]),
+    "pdsc_seed_solve_backward_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "pdsc_seed_solve_backward": (_i, [_vp] * 11 + [_sz, _i, _i, _i, _i, _i, _vp]),
+    "pdsc_transformation_loss_grad": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _vp]),
     "pdsc_icp_workspace_bytes": (_sz, [_i, _i, _i]),
     "pdsc_icp_refine": (_i, [_vp, _vp, _vp, _vp, _vp, C.c_double, C.c_double, C.c_double, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                              _sz, _i, _i, _i, _vp]),

@@ -3,7 +3,7 @@
 //   pdsc_classification_loss   libs/loss.py:85-102   (BCE with logits in three weightings + the precision / recall / F1 row)
 //   pdsc_sm_loss_matrix        libs/loss.py:129-138  on a stored M
 //   pdsc_sm_loss_features      the same loss of M = clamp(1 - (1 - F F^T) / sigma^2, 0, 1) straight from F: M is never stored
-//   pdsc_transformation_loss   libs/loss.py:34-63    (forward only)
+//   pdsc_transformation_loss   libs/loss.py:34-63    (+ pdsc_transformation_loss_grad: its gradient with respect to trans, f-14)
 // Determinism: no floating-point atomics anywhere.  Every workgroup reduces in a fixed tree (wave shuffle, then the waves in order)
 // and writes fp64 partials into the workspace; a one-workgroup finishing launch adds them in index order.
 //
@@ -430,6 +430,62 @@ __global__ __launch_bounds__(256) void trans_finish_kernel(const float* __restri
     out[threadIdx.x] = threadIdx.x == 1 ? acc * 100.0 / (double)bs : acc / (double)bs;
 }
 
+// d loss / d trans[:, :3, :] of the value above (f-14): loss = (1 / bs) sum_i [some probs_i > 0] (1 / (bs N)) sum_(j,n) |R_i s_in + t_i - g_jn|^2,
+// so d / dT_i[r][c] = (2 / (bs bs N)) sum_(j,n) d_r (s_c | 1).  Partial: the 12 sums of d_r (s_c | 1) and #probs > 0.
+constexpr int TRG_NP = 13;
+__global__ __launch_bounds__(256) void trans_grad_partial_kernel(const float* __restrict__ trans, const float* __restrict__ src,
+                                                                 const float* __restrict__ tgt, const float* __restrict__ probs,
+                                                                 double* __restrict__ part, int bs, int N) {
+    __shared__ double red[4 * TRG_NP];
+    const int i = blockIdx.y;
+    const float* T = trans + (size_t)i * 16;
+    double R[3][3], tv[3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) R[r][c] = (double)T[r * 4 + c];
+        tv[r] = (double)T[r * 4 + 3];
+    }
+    const long long total = (long long)bs * N;
+    double v[TRG_NP];
+#pragma unroll
+    for (int q = 0; q < TRG_NP; ++q) v[q] = 0.0;
+    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long long)gridDim.x * 256) {
+        const int n = (int)(e % N);
+        const float* s = src + ((size_t)i * N + n) * 3;
+        const float* g = tgt + (size_t)e * 3;
+        const double sx = (double)s[0], sy = (double)s[1], sz = (double)s[2];
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+            const double w = ((R[r][0] * sx + R[r][1] * sy) + R[r][2] * sz) + tv[r];
+            const double d = w - (double)g[r];
+            v[r * 4 + 0] += d * sx; v[r * 4 + 1] += d * sy; v[r * 4 + 2] += d * sz; v[r * 4 + 3] += d;
+        }
+        if (e < N) v[12] += probs[(size_t)i * N + e] > 0.f ? 1.0 : 0.0;
+    }
+    block_sum_f64<TRG_NP>(v, red);
+    if (threadIdx.x == 0) {
+        double* p = part + ((size_t)i * gridDim.x + blockIdx.x) * TRG_NP;
+#pragma unroll
+        for (int q = 0; q < TRG_NP; ++q) p[q] = v[q];
+    }
+}
+
+// dtrans [bs][16]: the chunks added in index order; row 3 and the pairs without a positive prob are exact zeros
+__global__ __launch_bounds__(256) void trans_grad_finish_kernel(const double* __restrict__ part, int chunks, double* __restrict__ dtrans,
+                                                                int bs, int N) {
+    for (int f = threadIdx.x; f < bs * 16; f += 256) {
+        const int i = f >> 4, e = f & 15;
+        double acc = 0.0, np = 0.0;
+        for (int c = 0; c < chunks; ++c) {
+            const double* p = part + ((size_t)i * chunks + c) * TRG_NP;
+            if (e < 12) acc += p[e];
+            np += p[12];
+        }
+        dtrans[f] = (e < 12 && np > 0.0) ? 2.0 * acc / ((double)bs * (double)N * (double)bs) : 0.0;
+    }
+}
+
 static int sm_row_blocks(int N) { return ceil_div(N, SM_ROWS); }
 static int trans_chunks(int bs, int N) {
     const long long c = ((long long)bs * N + 1023) / 1024;
@@ -439,8 +495,10 @@ static size_t loss_ws_doubles(int bs, int N) {
     const size_t sm = (size_t)2 * bs + (size_t)bs * sm_row_blocks(N) * SM_NP;
     const size_t cls = (size_t)CLS_MAX_BLOCKS * CLS_NQ;
     const size_t tr = (size_t)bs * 5 + (size_t)bs * trans_chunks(bs, N) * TR_NP;
+    const size_t trg = (size_t)bs * trans_chunks(bs, N) * TRG_NP;
     size_t m = sm > cls ? sm : cls;
-    return m > tr ? m : tr;
+    m = m > tr ? m : tr;
+    return m > trg ? m : trg;
 }
 
 }  // namespace pdsc
@@ -523,4 +581,16 @@ extern "C" int pdsc_transformation_loss(const float* trans, const float* gt_tran
     hipLaunchKernelGGL(pdsc::trans_finish_kernel, dim3(1), dim3(256), 0, st, trans, gt_trans, part, chunks, pair_vals, re_thre, te_thre,
                        out, bs, N);
     return pdsc::check_launch("pdsc_transformation_loss");
+}
+
+extern "C" int pdsc_transformation_loss_grad(const float* trans, const float* src, const float* tgt, const float* probs, double* dtrans,
+                                             void* ws, size_t ws_bytes, int bs, int N, void* stream) {
+    PDSC_REQUIRE(trans && src && tgt && probs && dtrans, "pdsc_transformation_loss_grad: null pointer");
+    PDSC_LOSS_WS("pdsc_transformation_loss_grad")
+    hipStream_t st = (hipStream_t)stream;
+    const int chunks = pdsc::trans_chunks(bs, N);
+    double* part = (double*)ws;
+    hipLaunchKernelGGL(pdsc::trans_grad_partial_kernel, dim3(chunks, bs), dim3(256), 0, st, trans, src, tgt, probs, part, bs, N);
+    hipLaunchKernelGGL(pdsc::trans_grad_finish_kernel, dim3(1), dim3(256), 0, st, part, chunks, dtrans, bs, N);
+    return pdsc::check_launch("pdsc_transformation_loss_grad");
 }

@@ -437,18 +437,21 @@ def train_epoch(model, batches: Iterable[Dict[str, torch.Tensor]], optimizer, we
     train()-mode forward of `model` (a ``training.TrainablePointDSC`` in train() mode), the three losses of pointdsc_amd.losses,
     ``weights[0] class_loss + weights[1] sm_loss``, backward, and the reference's rule that the optimiser step is skipped when any
     gradient is non-finite (one boolean per step is read for it, as the reference reads one).  `balanced` is the reference's
-    config.balanced (default False).  The transformation loss has no gradient here: it is a meter, and a weight above 0 for it raises
-    NotImplementedError (the reference's default is 0.0).
+    config.balanced (default False).  ``weights[2]`` is the reference's weight_transformation (libs/trainer.py:105-107; default 0.0,
+    and the caller keeps it 0 until transformation_loss_start_epoch): above 0 the model must have been built with
+    ``differentiable_trans=True``, so that its final_trans carries a gradient, and ``weights[2] * trans_loss`` joins the objective;
+    for any other model a weight above 0 raises NotImplementedError.  With weight 0 the transformation loss is a meter only.
     -> the nine meters of the reference (running means kept on the device in fp64, NaN values skipped, as in ``validate``), and
     "loss_first" / "loss_last" (the weighted sum at the first and the last step), "steps", "skipped" -- ONE read-back at the end."""
-    from .losses import ClassificationLoss, SpectralMatchingLoss, transformation_loss_raw
+    from .losses import ClassificationLoss, SpectralMatchingLoss, TransformationLoss, transformation_loss_raw
     w_cls, w_sm, w_tr = (float(w) for w in weights)
-    if w_tr > 0.0:
-        raise NotImplementedError("the transformation loss has no gradient on the device (forward only): use weight 0.0, the reference's default")
+    if w_tr > 0.0 and not getattr(model, "differentiable_trans", False):
+        raise NotImplementedError("a transformation-loss weight above 0 needs a final_trans with a gradient: build the model as "
+                                  "TrainablePointDSC(..., differentiable_trans=True), or use weight 0.0, the reference's default")
     if not model.training:
         raise RuntimeError("train_epoch needs the model in train() mode")
     dev = next(model.parameters()).device
-    cls_fn, sm_fn = ClassificationLoss(balanced), SpectralMatchingLoss(balanced)
+    cls_fn, sm_fn, tr_fn = ClassificationLoss(balanced), SpectralMatchingLoss(balanced), TransformationLoss(re_thre, te_thre)
     params = [p for p in model.parameters() if p.requires_grad]
     sums = torch.zeros(len(VALIDATE_NAMES), device=dev, dtype=torch.float64)
     counts = torch.zeros(len(VALIDATE_NAMES), device=dev, dtype=torch.float64)
@@ -462,6 +465,10 @@ def train_epoch(model, batches: Iterable[Dict[str, torch.Tensor]], optimizer, we
         cls = cls_fn(logits, gt, device_stats=True)
         sm = sm_fn(res["M"], gt)
         loss = w_cls * cls["loss"] + w_sm * sm
+        tr = None
+        if w_tr > 0.0:
+            tr = tr_fn(res["final_trans"], d["gt_trans"], d["src_keypts"], d["tgt_keypts"], logits, device_stats=True)
+            loss = loss + w_tr * tr[0]
         loss.backward()
         grads = [p.grad for p in params if p.grad is not None]
         if bool(torch.stack([torch.isfinite(g).all() for g in grads]).all()):
@@ -470,8 +477,9 @@ def train_epoch(model, batches: Iterable[Dict[str, torch.Tensor]], optimizer, we
             skipped += 1
         steps += 1
         with torch.no_grad():
-            tr = transformation_loss_raw(res["final_trans"], d["gt_trans"], d["src_keypts"], d["tgt_keypts"], logits, re_thre, te_thre)
-            vals = torch.stack([cls["loss"].detach().double(), tr[0], sm.detach().double(), tr[1], tr[2], tr[3],
+            if tr is None:
+                tr = transformation_loss_raw(res["final_trans"], d["gt_trans"], d["src_keypts"], d["tgt_keypts"], logits, re_thre, te_thre)
+            vals = torch.stack([cls["loss"].detach().double(), tr[0].detach().double(), sm.detach().double(), tr[1], tr[2], tr[3],
                                 cls["precision"], cls["recall"], cls["f1"]])
             ok = ~torch.isnan(vals) & ~torch.isnan(loss.detach())          # the reference updates no meter on a NaN loss
             sums += torch.where(ok, vals, torch.zeros_like(vals))

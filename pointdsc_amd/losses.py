@@ -3,8 +3,8 @@
 ``ClassificationLoss``, ``SpectralMatchingLoss`` and ``TransformationLoss`` keep the reference's constructor arguments, call
 signatures and return shapes, so ``Trainer.evaluate_metric`` (libs/trainer.py:186-194) can hold them unchanged.  All arithmetic
 runs in libpointdsc_hip.so: fp64 sums of fp64 per-element terms, deterministic (no atomics).  The loss values are fp32 0-dim device
-tensors (the rounding of the library's fp64 slot); the classification loss and both forms of the spectral-matching loss are
-``torch.autograd.Function``s whose backward scales the gradient the kernels computed for an upstream gradient of 1 -- the
+tensors (the rounding of the library's fp64 slot); the classification loss, both forms of the spectral-matching loss and (f-14) the
+transformation loss are ``torch.autograd.Function``s whose backward scales the gradient the kernels computed for an upstream gradient of 1 -- the
 gradient buffers are requested only when an input requires a gradient.  There is no CPU path.
 
 The ``*_raw`` functions are the thin wrappers over the C entry points (fp64 slots, fp64 / fp32 gradient buffers as the library
@@ -119,6 +119,24 @@ def transformation_loss_raw(trans, gt_trans, src_keypts, tgt_keypts, probs, re_t
     return out
 
 
+@_on_device
+def transformation_loss_grad_raw(trans, src_keypts, tgt_keypts, probs):
+    """-> fp64 [bs,4,4] = d loss / d trans of transformation_loss_raw's loss (row 3 zero; the broadcast over the batch and the
+    `some probs > 0` rule of the reference included).  pdsc_transformation_loss_grad."""
+    _need_gpu(("trans", trans), ("src_keypts", src_keypts), ("tgt_keypts", tgt_keypts), ("probs", probs))
+    lib = _lib.load()
+    T = _chk(trans.detach(), "trans")
+    s, t, p = _chk(src_keypts.detach(), "src_keypts"), _chk(tgt_keypts.detach(), "tgt_keypts"), _chk(probs.detach(), "probs")
+    bs, n = p.shape
+    if T.shape != (bs, 4, 4) or s.shape != (bs, n, 3) or t.shape != (bs, n, 3):
+        raise ValueError("bad shapes for the transformation loss")
+    ws = _workspace(bs, n, p.device)
+    out = torch.empty(bs, 4, 4, device=p.device, dtype=torch.float64)
+    _lib.check(lib.pdsc_transformation_loss_grad(_p(T), _p(s), _p(t), _p(p), _p(out), _p(ws), ws.numel() * 8, bs, n, _stream()),
+               "pdsc_transformation_loss_grad")
+    return out
+
+
 # ---------------------------------------------------------------------------------------------------------------------------
 # autograd
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -171,6 +189,20 @@ class _SmFeaturesFn(torch.autograd.Function):
         return gn, gs, None, None, None, None
 
 
+class _TransformationFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, trans, gt_trans, src_keypts, tgt_keypts, probs, re_thre, te_thre):
+        out = transformation_loss_raw(trans, gt_trans, src_keypts, tgt_keypts, probs, re_thre, te_thre)
+        ctx.save_for_backward(transformation_loss_grad_raw(trans, src_keypts, tgt_keypts, probs))
+        ctx.mark_non_differentiable(out)
+        return out[0].to(torch.float32), out
+
+    @staticmethod
+    def backward(ctx, g_loss, _g_out):
+        (dtrans,) = ctx.saved_tensors
+        return (dtrans * g_loss).to(torch.float32), None, None, None, None, None, None
+
+
 # ---------------------------------------------------------------------------------------------------------------------------
 # the reference's modules
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -209,8 +241,10 @@ class SpectralMatchingLoss(nn.Module):
 
 
 class TransformationLoss(nn.Module):
-    """libs/loss.py:12-63, forward only (no graph).  forward(trans, gt_trans, src_keypts, tgt_keypts, probs) ->
+    """libs/loss.py:12-63.  forward(trans, gt_trans, src_keypts, tgt_keypts, probs) ->
     (loss, recall, RE, TE, RMSE): fp32 0-dim device tensors, recall a Python float (one copy), as the reference returns them.
+    The loss is differentiable in trans (rows 0..2) when trans requires a gradient and grad mode is on; otherwise no graph is
+    built and no gradient kernel runs.  recall, RE, TE and RMSE never carry a graph.
     device_stats=True: recall, RE, TE and RMSE are fp64 0-dim device tensors and nothing synchronises.
     For bs > 1 the reference subtracts the whole [bs,N,3] target from every pair's warped source; that broadcast is mirrored."""
 
@@ -220,8 +254,11 @@ class TransformationLoss(nn.Module):
         self.te_thre = te_thre
 
     def forward(self, trans, gt_trans, src_keypts, tgt_keypts, probs, device_stats: bool = False):
-        out = transformation_loss_raw(trans, gt_trans, src_keypts, tgt_keypts, probs, self.re_thre, self.te_thre)
-        loss = out[0].to(torch.float32)
+        if _wants_grad(trans):
+            loss, out = _TransformationFn.apply(trans, gt_trans, src_keypts, tgt_keypts, probs, self.re_thre, self.te_thre)
+        else:
+            out = transformation_loss_raw(trans, gt_trans, src_keypts, tgt_keypts, probs, self.re_thre, self.te_thre)
+            loss = out[0].to(torch.float32)
         if device_stats:
             return loss, out[1], out[2], out[3], out[4]
         f32 = out.to(torch.float32)

@@ -553,6 +553,39 @@ def seed_transforms(src, tgt, knn_idx, iters, mask, num_iterations: int):
 
 
 @_on_device
+def seed_solve_backward(normed, src, tgt, knn_idx, sigma, sigma_spat, mask, num_iterations: int, d_seed_trans,
+                        want_dnormed: bool = True, want_dsigma: bool = True):
+    """Backward of seed_power_iteration + seed_transforms (pdsc_seed_solve_backward): normed [bs,N,128], src, tgt [bs,N,3],
+    knn_idx [bs,S,k] int32, sigma, sigma_spat one value each, mask [bs] int32 as seed_transforms took it, d_seed_trans [bs,S,4,4]
+    (row 3 ignored) -> (dnormed fp32 [bs,N,128] or None, dsigma fp64 [1] or None)."""
+    if not (want_dnormed or want_dsigma):
+        raise ValueError("seed_solve_backward: ask for at least one of dnormed and dsigma")
+    lib = _lib.load()
+    normed, src, tgt = _chk(normed, "normed"), _chk(src, "src"), _chk(tgt, "tgt")
+    knn_idx, mask = _chk(knn_idx, "knn_idx", torch.int32), _chk(mask, "mask", torch.int32)
+    sigma, sigma_spat = _chk(sigma.reshape(-1), "sigma"), _chk(sigma_spat.reshape(-1), "sigma_spat")
+    d_seed_trans = _chk(d_seed_trans, "d_seed_trans")
+    if src.dim() != 3 or src.shape[2] != 3 or tgt.shape != src.shape:
+        raise ValueError(f"src and tgt must be [bs,N,3] alike, got {tuple(src.shape)} {tuple(tgt.shape)}")
+    bs, n = src.shape[0], src.shape[1]
+    if normed.shape != (bs, n, 128) or knn_idx.dim() != 3 or knn_idx.shape[0] != bs:
+        raise ValueError(f"normed must be [bs,N,128] and knn_idx [bs,S,k], got {tuple(normed.shape)} {tuple(knn_idx.shape)}")
+    s, k = knn_idx.shape[1], knn_idx.shape[2]
+    if d_seed_trans.shape != (bs, s, 4, 4) or mask.numel() != bs or sigma.numel() != 1 or sigma_spat.numel() != 1:
+        raise ValueError("d_seed_trans must be [bs,S,4,4], mask [bs], sigma and sigma_spat one value each")
+    if not 1 <= k <= 64:
+        raise ValueError(f"seed_solve_backward: k = {k} (1 .. 64)")
+    nb = int(lib.pdsc_seed_solve_backward_workspace_bytes(bs, n, s, k))
+    ws = torch.empty(max((nb + 7) // 8, 1), device=src.device, dtype=torch.float64)
+    dnormed = torch.empty(bs, n, 128, device=src.device, dtype=torch.float32) if want_dnormed else None
+    dsigma = torch.empty(1, device=src.device, dtype=torch.float64) if want_dsigma else None
+    _lib.check(lib.pdsc_seed_solve_backward(_p(normed), _p(src), _p(tgt), _p(knn_idx), _p(sigma), _p(sigma_spat), _p(mask),
+                                            _p(d_seed_trans), _p(dnormed), _p(dsigma), _p(ws), ws.numel() * 8, bs, n, s, k,
+                                            int(num_iterations), _stream()), "pdsc_seed_solve_backward")
+    return dnormed, dsigma
+
+
+@_on_device
 def rigid_transform_3d(A: torch.Tensor, B: torch.Tensor, weights: Optional[torch.Tensor] = None,
                        weight_threshold: float = 0) -> torch.Tensor:
     """Drop-in for reference models/common.py:rigid_transform_3d: A,B [bs,n,3] -> [bs,4,4]."""

@@ -4,8 +4,9 @@
 Of the training path two operations need a hand-written backward: the attention (in torch it materialises bs x N x N scores twice
 per layer) and the feature-similarity matrix M (its gradient for an arbitrary dM is a second N x N x 128 product behind a clamp
 mask).  ``sc_attention`` is a ``torch.autograd.Function`` over ``ops.sc_attention_lse`` / ``ops.sc_attention_backward``;
-``feature_similarity`` one over ``ops.feature_compat`` / ``ops.feature_compat_backward``.  The 1x1 convolutions, batch-norms and
-ReLUs around them are operations torch differentiates well and stay torch's.  ``NonLocalBlock`` is the reference block
+``feature_similarity`` one over ``ops.feature_compat`` / ``ops.feature_compat_backward``; (f-14) ``seed_solve`` one over the per-seed
+solver (``ops.seed_power_iteration`` + ``ops.seed_transforms`` / ``ops.seed_solve_backward``), which gives ``final_trans`` a
+gradient.  The 1x1 convolutions, batch-norms and ReLUs around them are operations torch differentiates well and stay torch's.  ``NonLocalBlock`` is the reference block
 (models/PointDSC.py:9-45) for a trainer that swaps layer by layer; ``train_forward`` is the reference's whole forward without the
 'testing' key (models/PointDSC.py:143-197) on a ``PointDSC`` module's own parameters, and ``TrainablePointDSC`` the module that
 calls it in ``train()`` mode.  ``PointDSC.forward`` itself keeps refusing ``train()`` mode.
@@ -170,6 +171,66 @@ def feature_similarity(normed: torch.Tensor, sigma: torch.Tensor) -> torch.Tenso
     return _FeatureSimilarity.apply(normed.contiguous(), sigma)
 
 
+# ---------------------------------------------------------------------------------------------------------------------------
+# f-14: the differentiable per-seed solver
+# ---------------------------------------------------------------------------------------------------------------------------
+class _SeedSolve(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, normed, sigma, src, tgt, knn_idx, sigma_spat, num_iterations):
+        bs = src.shape[0]
+        iters, mask, _ = ops.seed_power_iteration(normed, src, tgt, knn_idx, sigma, sigma_spat, num_iterations)
+        if bs > 1:
+            # the reference takes the power iteration's early exit over the seeds of ALL pairs (one allclose over [bs*S, k])
+            _lib.check(_lib.load().pdsc_conv_mask_all_pairs(ops._p(mask), bs, ops._stream()), "pdsc_conv_mask_all_pairs")
+        seed_trans, _ = ops.seed_transforms(src, tgt, knn_idx, iters, mask, num_iterations)
+        ctx.save_for_backward(normed, sigma, src, tgt, knn_idx, sigma_spat, mask)       # the iterates are replayed, not kept
+        ctx.num_iterations = num_iterations
+        return seed_trans
+
+    @staticmethod
+    def backward(ctx, d_seed_trans):
+        normed, sigma, src, tgt, knn_idx, sigma_spat, mask = ctx.saved_tensors
+        need_n, need_s = ctx.needs_input_grad[:2]
+        if not (need_n or need_s):
+            return (None,) * 7
+        dn, ds = ops.seed_solve_backward(normed, src, tgt, knn_idx, sigma, sigma_spat, mask, ctx.num_iterations,
+                                         d_seed_trans.contiguous(), want_dnormed=need_n, want_dsigma=need_s)
+        return (dn if need_n else None), (ds.to(torch.float32).reshape(sigma.shape) if need_s else None), None, None, None, None, None
+
+
+def seed_solve(normed: torch.Tensor, src: torch.Tensor, tgt: torch.Tensor, knn_idx: torch.Tensor, sigma: torch.Tensor,
+               sigma_spat: torch.Tensor, num_iterations: int) -> torch.Tensor:
+    """cal_seed_trans (models/PointDSC.py:248-320) with gradients for the features and sigma: the seeds' k x k feature * spatial
+    matrices, the power iteration (the reference's early exit over all pairs included) and the weighted Procrustes.
+    normed [bs,N,128], src, tgt [bs,N,3] fp32, knn_idx [bs,S,k] int32 (k <= 64), sigma, sigma_spat one fp32 value each ->
+    seed_trans [bs,S,4,4], bit for bit ops.seed_power_iteration + ops.seed_transforms.  src, tgt, sigma_spat and knn_idx get no
+    gradient: one of them that requires grad is refused rather than silently given None."""
+    for t, name in ((src, "src"), (tgt, "tgt"), (sigma_spat, "sigma_spat")):
+        if t.requires_grad:
+            raise ValueError(f"seed_solve: {name} gets no gradient (only the features and sigma do); detach it")
+    for t, name in ((normed, "normed"), (src, "src"), (tgt, "tgt"), (knn_idx, "knn_idx"), (sigma, "sigma"), (sigma_spat, "sigma_spat")):
+        if not t.is_cuda:
+            raise RuntimeError(f"{name} must live on the GPU (pointdsc_amd has no CPU path)")
+        want = torch.int32 if name == "knn_idx" else torch.float32
+        if t.dtype != want:
+            raise TypeError(f"{name} must be {want}, got {t.dtype}")
+    if src.dim() != 3 or src.shape[-1] != 3 or tgt.shape != src.shape:
+        raise ValueError(f"seed_solve: src and tgt must be [bs,N,3] alike, got {tuple(src.shape)} {tuple(tgt.shape)}")
+    bs, n, _ = src.shape
+    if normed.shape != (bs, n, CHANNELS):
+        raise ValueError(f"seed_solve: normed must be [bs,N,{CHANNELS}], got {tuple(normed.shape)}")
+    if knn_idx.dim() != 3 or knn_idx.shape[0] != bs or knn_idx.shape[1] < 1:
+        raise ValueError(f"seed_solve: knn_idx must be [bs,S,k], got {tuple(knn_idx.shape)}")
+    if not 1 <= knn_idx.shape[2] <= 64:
+        raise ValueError(f"seed_solve: k = {knn_idx.shape[2]} neighbours per seed (1 .. 64)")
+    if sigma.numel() != 1 or sigma_spat.numel() != 1:
+        raise ValueError("seed_solve: sigma and sigma_spat must hold one value each")
+    if not 0 <= int(num_iterations) <= 32:
+        raise ValueError(f"seed_solve: num_iterations = {num_iterations} (0 .. 32)")
+    return _SeedSolve.apply(normed.contiguous(), sigma, src.contiguous(), tgt.contiguous(), knn_idx.contiguous(), sigma_spat,
+                            int(num_iterations))
+
+
 def _conv_rows(conv: nn.Conv1d, x: torch.Tensor) -> torch.Tensor:
     """A 1x1 Conv1d on channel-last rows [M, Cin] -> [M, Cout]."""
     return F.linear(x, conv.weight[:, :, 0], conv.bias)
@@ -193,13 +254,15 @@ def _train_encoder(enc, x: torch.Tensor, compat: torch.Tensor, bs: int, n: int) 
     return feat
 
 
-def train_forward(model: PointDSC, data) -> dict:
+def train_forward(model: PointDSC, data, differentiable_trans: bool = False) -> dict:
     """The reference's forward without the 'testing' key (models/PointDSC.py:143-197) in train() mode, on `model`'s own Parameters
     and buffers: batch-statistics batch-norm (running statistics updated as torch's BatchNorm1d does), autograd through the
     encoder, the classification head and M.  data: corr_pos [bs,N,in_dim], src_keypts, tgt_keypts [bs,N,3] on the GPU.
-    -> {'final_trans': the best seed hypothesis [bs,4,4] (no gradient), 'final_labels': the logits [bs,N], 'M': [bs,N,N]}.
-    The spatial-consistency matrix, the seeds and everything behind them (kNN, power iteration, Procrustes, vote) carry no gradient,
-    as in the reference, and run as the library's stage ops."""
+    -> {'final_trans': the best seed hypothesis [bs,4,4], 'final_labels': the logits [bs,N], 'M': [bs,N,N]}.
+    The spatial-consistency matrix, the seeds, their neighbours and the vote carry no gradient, as in the reference, and run as the
+    library's stage ops.  differentiable_trans=False: neither do the power iteration and the Procrustes -- final_trans has no
+    gradient and nothing is kept for one.  True: they run behind ``seed_solve`` and final_trans carries the gradient of the winning
+    seed of each pair into the features and sigma (the reference's cal_seed_trans under autograd); the values are the same."""
     if not model.training:
         raise RuntimeError("train_forward needs the module in train() mode; in eval() mode call the module (PointDSC.forward)")
     if "testing" in data.keys():
@@ -230,12 +293,21 @@ def train_forward(model: PointDSC, data) -> dict:
             nd, sigma = normed.detach(), model.sigma.detach()
             seeds = ops.rank_select(logits.detach().contiguous(), num_seeds)          # argsort(logits, descending)[:, :num_seeds]
             knn_idx = ops.knn_seeds(nd, seeds, k, form="matrix")
-            iters, mask, _ = ops.seed_power_iteration(nd, src, tgt, knn_idx, sigma, model.sigma_spat, model.num_iterations)
-            if bs > 1:
-                # the reference takes the power iteration's early exit over the seeds of ALL pairs (one allclose over [bs*S, k])
-                _lib.check(_lib.load().pdsc_conv_mask_all_pairs(ops._p(mask), bs, ops._stream()), "pdsc_conv_mask_all_pairs")
-            seed_trans, _ = ops.seed_transforms(src, tgt, knn_idx, iters, mask, model.num_iterations)
-            final_trans = ops.score_hypotheses(seed_trans, src, tgt, float(model.inlier_threshold))[2]
+        if differentiable_trans:
+            # the same launches behind an autograd.Function; the winner gathered with the vote's own index, so final_trans carries
+            # the gradient of one seed per pair (models/PointDSC.py:325-335: the reference indexes seed_trans with argmax too)
+            seed_trans = seed_solve(normed, src, tgt, knn_idx, model.sigma, model.sigma_spat.detach(), model.num_iterations)
+            with torch.no_grad():
+                best = ops.score_hypotheses(seed_trans.detach(), src, tgt, float(model.inlier_threshold))[1]
+            final_trans = seed_trans[torch.arange(bs, device=dev), best.long()]
+        else:
+            with torch.no_grad():
+                iters, mask, _ = ops.seed_power_iteration(nd, src, tgt, knn_idx, sigma, model.sigma_spat, model.num_iterations)
+                if bs > 1:
+                    # the reference takes the power iteration's early exit over the seeds of ALL pairs (one allclose over [bs*S, k])
+                    _lib.check(_lib.load().pdsc_conv_mask_all_pairs(ops._p(mask), bs, ops._stream()), "pdsc_conv_mask_all_pairs")
+                seed_trans, _ = ops.seed_transforms(src, tgt, knn_idx, iters, mask, model.num_iterations)
+                final_trans = ops.score_hypotheses(seed_trans, src, tgt, float(model.inlier_threshold))[2]
     return {"final_trans": final_trans, "final_labels": logits, "M": M}
 
 
@@ -243,9 +315,14 @@ class TrainablePointDSC(PointDSC):
     """``PointDSC`` a trainer can hold: the same constructor, parameters and 358-key state_dict (strict loading both ways).
     In ``train()`` mode ``forward`` is ``train_forward`` (batch statistics, autograd; the reference's Trainer.train_epoch,
     libs/trainer.py:79-136, runs on it unchanged); in ``eval()`` mode it is ``PointDSC.forward``, which sees every optimiser step
-    through the weights' version counters."""
+    through the weights' version counters.  ``differentiable_trans=True`` (keyword only, not part of the reference's constructor):
+    the train-mode ``final_trans`` carries a gradient (``train_forward``), what a transformation-loss weight above 0 needs."""
+
+    def __init__(self, *args, differentiable_trans: bool = False, **kwargs):
+        super().__init__(*args, **kwargs)
+        self.differentiable_trans = bool(differentiable_trans)
 
     def forward(self, data):
         if self.training:
-            return train_forward(self, data)
+            return train_forward(self, data, differentiable_trans=self.differentiable_trans)
         return super().forward(data)

@@ -128,7 +128,7 @@ def train(a):
     """--train: a few optimiser steps of harness.train_epoch on the synthetic batches --validate uses; the validation meters of
     the same batches before and after."""
     from pointdsc_amd import TrainablePointDSC, synthetic
-    model = TrainablePointDSC(**dict(workloads.BASE_MODEL))
+    model = TrainablePointDSC(**dict(workloads.BASE_MODEL), differentiable_trans=a.weight_transformation > 0)
     if a.snapshot:
         print(model.load_state_dict(torch.load(a.snapshot, map_location="cpu"), strict=False))
     else:
@@ -138,7 +138,7 @@ def train(a):
     optimizer = torch.optim.Adam(model.parameters(), lr=a.lr, weight_decay=1e-6)          # config.py:48-53
     before = harness.validate(model.eval(), batches)
     steps = [batches[i % len(batches)] for i in range(a.train_steps)]
-    meters = harness.train_epoch(model.train(), steps, optimizer)
+    meters = harness.train_epoch(model.train(), steps, optimizer, weights=(1.0, 1.0, a.weight_transformation))
     after = harness.validate(model.eval(), batches)
     if a.json:
         print(json.dumps({"before": before, "train": meters, "after": after}))
@@ -183,6 +183,8 @@ def main():
                     "steps over the --num-batches synthetic batches of --validate, with the validation meters before and after")
     ap.add_argument("--train-steps", type=int, default=8)
     ap.add_argument("--lr", type=float, default=1e-4, help="with --train (config.py:52)")
+    ap.add_argument("--weight-transformation", type=float, default=0.0, help="with --train: config.py:43, the weight of the transformation "
+                    "loss in the objective; above 0 the model is built with differentiable_trans=True")
     ap.add_argument("--json", action="store_true")
     a = ap.parse_args()
     if a.train:
