@@ -473,10 +473,12 @@ int pdsc_seed_transforms(const float* src_keypts, const float* tgt_keypts, const
                          float* seed_weights /* optional [bs][S][k] */,
                          int bs, int N, int S, int k, int num_iterations, void* stream);
 
-/* ---- a-7 + a-8 + a-9 in one launch (what the forward calls) -------------------------------------
- * pdsc_seed_power_iteration and, for the LAST iterate, pdsc_seed_transforms by the same wavefront that owns the seed;
- * a second, normally empty launch re-solves the seeds of a pair whose global early exit (conv_mask) selected an earlier
- * iterate.  seed_trans / seed_weights / seed_M may be NULL (then this is pdsc_seed_power_iteration). */
+/* ---- a-7 + a-8 + a-9: the launches of the testing forward ------------------------------------------
+ * Launch 1: pdsc_seed_power_iteration and, for the LAST iterate, the Procrustes sums of pdsc_seed_transforms by the same
+ * wavefront that owns the seed.  Launch 2 (one wavefront per 64 consecutive seeds of the flattened bs * S list) re-solves the
+ * seeds of a pair whose global early exit (conv_mask) selected an earlier iterate, then turns every slot into its 4x4; with
+ * num_iterations = 0 it is the plain decomposition launch.  Same bits as pdsc_seed_power_iteration + pdsc_seed_transforms.
+ * seed_weights / seed_M may be NULL.  seed_trans == NULL: launch 1 alone (this is then pdsc_seed_power_iteration). */
 int pdsc_seed_solve(const float* normed, const float* src_keypts, const float* tgt_keypts, const int* knn_idx,
                     const float* sigma, const float* sigma_spat, float* eig_iters, unsigned int* conv_mask, float* seed_M,
                     float* seed_trans, float* seed_weights, int bs, int N, int S, int k, int num_iterations, void* stream);

@@ -751,7 +751,7 @@ static int run_hypotheses(const ForwardCtx& x) {
         PDSC_TRY(pdsc_seed_transforms(c.src, c.tgt, x.knn_idx, eig, x.conv_mask, x.seed_trans, seed_w, c.bs, c.N, x.S, x.k, iters, x.st));
     } else
         PDSC_TRY(launch_seed_solve_forward(x.normed, c.src, c.tgt, x.knn_idx, x.W(PDSC_W_SIGMA, 0), x.W(PDSC_W_SIGMA_SPAT, 0), eig, x.conv_mask,
-                                           x.seed_trans, seed_w, c.bs, c.N, x.S, x.k, iters, /*mask_ready=*/testing, x.st));
+                                           /*seed_M=*/nullptr, x.seed_trans, seed_w, c.bs, c.N, x.S, x.k, iters, /*mask_ready=*/testing, x.st));
 #ifdef PDSC_EXPERIMENTS
     score_debug_slot() = env_int("PDSC_SCORE_DEBUG", 0) ? x.L.at<float>(ws, WS_SCORE_DBG) : nullptr;
 #endif

@@ -17,10 +17,12 @@ int launch_nms_keys_grid(const float* src, const float* conf, float radius, floa
 // convergence mask: launch_seed_solve_forward then skips its own fill launch)
 int launch_rank_select(const float* keys, int* seeds, int bs, int N, int num_seeds, const int* nvalid, const int* svalid, hipStream_t st,
                        unsigned int* conv_mask_init = nullptr);
-// solver.hip: pdsc_seed_solve as the forward runs it; mask_ready: conv_mask already holds its start value (no fill launch)
+// solver.hip: the forward's per-seed solver, seed_solve_kernel + fixup_kabsch_kernel (kabsch_batch_kernel for 0 iterations);
+// pdsc_seed_solve with a non-NULL seed_trans is this function with mask_ready = false.  seed_M: optional [bs][S][k][k];
+// mask_ready: conv_mask already holds its start value (no fill launch)
 int launch_seed_solve_forward(const float* normed, const float* src, const float* tgt, const int* knn_idx, const float* sigma,
-                              const float* sigma_spat, float* eig_iters, unsigned int* conv_mask, float* seed_trans, float* seed_weights,
-                              int bs, int N, int S, int k, int num_iterations, bool mask_ready, hipStream_t st);
+                              const float* sigma_spat, float* eig_iters, unsigned int* conv_mask, float* seed_M, float* seed_trans,
+                              float* seed_weights, int bs, int N, int S, int k, int num_iterations, bool mask_ready, hipStream_t st);
 // score.hip: pdsc_select_best + pdsc_post_refinement in one launch (one workgroup per pair does both; same arithmetic, same bits)
 int launch_select_and_refine(const int* counts, const float* seed_trans, const float* src, const float* tgt, float inlier_threshold,
                              float refine_threshold, int max_iters, int* best, float* initial_trans, float* labels, float* final_trans,

@@ -60,20 +60,18 @@ __global__ __launch_bounds__(64) void kabsch_batch_kernel(float* __restrict__ se
     for (int e = 0; e < 16; ++e) slot[e] = T[e];
 }
 
-// only_if_early_exit: the fused solver below already wrote the hypotheses of the LAST iterate; this launch then re-solves
-// a pair's seeds only when the reference's global early exit picked an earlier iterate (rare), and returns at once otherwise.
+// a-9 on stored iterates (pdsc_seed_transforms): every seed's sums from the iterate its pair's mask word names
 __global__ __launch_bounds__(64) void seed_transform_kernel(const float* __restrict__ src, const float* __restrict__ tgt,
                                                             const int* __restrict__ knn_idx,
                                                             const float* __restrict__ eig_iters,
                                                             const unsigned int* __restrict__ conv_mask,
                                                             float* __restrict__ seed_trans, float* __restrict__ seed_w,
-                                                            int N, int S, int k, int num_iter, int only_if_early_exit) {
+                                                            int N, int S, int k, int num_iter) {
     const int lane = threadIdx.x;
     const int s = blockIdx.x, b = blockIdx.y;
     const bool valid = lane < k;
     int it = num_iter - 1;
     if (num_iter > 0) it = chosen_iterate(conv_mask[b], num_iter);
-    if (only_if_early_exit && it == num_iter - 1) return;
     const int idx = knn_idx[((size_t)b * S + s) * k + (valid ? lane : 0)];
     const float* srcb = src + (size_t)b * N * 3;
     const float* tgtb = tgt + (size_t)b * N * 3;
@@ -215,7 +213,7 @@ __global__ __launch_bounds__(64 * SV_WAVES) void seed_solve_kernel(const float* 
         wave_lds_sync();                                  // everyone has read sh.v before it is overwritten
     }
     if (lane == 0) atomicAnd(conv_mask + b, bits);
-    if (seed_trans)                                       // hypothesis of the LAST iterate (the common case, see seed_transform_kernel)
+    if (seed_trans)                                       // hypothesis of the LAST iterate (the common case, see fixup_kabsch_kernel)
         seed_procrustes(lane, valid, valid ? v : 0.f, ax, ay, az, bx, by, bz, seed_trans + ((size_t)b * S + s) * 16,
                         seed_w ? seed_w + ((size_t)b * S + s) * k : nullptr);
 }
@@ -343,9 +341,20 @@ extern "C" int pdsc_seed_power_iteration(const float* normed, const float* src, 
 }
 
 namespace pdsc {
+// the solver launch alone, by NB = ceil(k / 16)
+static int launch_seed_solve_nb(const float* normed, const float* src, const float* tgt, const int* knn_idx, const float* sigma,
+                                const float* sigma_spat, float* eig_iters, unsigned int* conv_mask, float* seed_M, float* seed_trans,
+                                float* seed_weights, int bs, int N, int S, int k, int num_iterations, hipStream_t st) {
+    const int nb = ceil_div(k, 16);
+#define PDSC_SOLVE(NBV) launch_seed_solve<NBV>(normed, src, tgt, knn_idx, sigma, sigma_spat, eig_iters, conv_mask, seed_M, seed_trans, \
+                                               seed_weights, bs, N, S, k, num_iterations, st)
+    return nb == 1 ? PDSC_SOLVE(1) : nb == 2 ? PDSC_SOLVE(2) : nb == 3 ? PDSC_SOLVE(3) : PDSC_SOLVE(4);
+#undef PDSC_SOLVE
+}
+
 int launch_seed_solve_forward(const float* normed, const float* src, const float* tgt, const int* knn_idx, const float* sigma,
-                              const float* sigma_spat, float* eig_iters, unsigned int* conv_mask, float* seed_trans, float* seed_weights,
-                              int bs, int N, int S, int k, int num_iterations, bool mask_ready, hipStream_t st) {
+                              const float* sigma_spat, float* eig_iters, unsigned int* conv_mask, float* seed_M, float* seed_trans,
+                              float* seed_weights, int bs, int N, int S, int k, int num_iterations, bool mask_ready, hipStream_t st) {
     PDSC_REQUIRE(normed && src && tgt && knn_idx && sigma && sigma_spat && eig_iters && conv_mask && seed_trans, "pdsc_seed_solve: null pointer");
     PDSC_REQUIRE(bs > 0 && N > 0 && S > 0, "pdsc_seed_solve: bs=%d N=%d S=%d", bs, N, S);
     PDSC_REQUIRE(k >= 1 && k <= PDSC_MAX_K, "pdsc_seed_solve: k=%d (max %d)", k, PDSC_MAX_K);
@@ -353,11 +362,8 @@ int launch_seed_solve_forward(const float* normed, const float* src, const float
                  num_iterations, PDSC_MAX_POWER_ITERS);
     if (!mask_ready)
         if (const int rc = launch_fill_u32(conv_mask, 0xFFFFFFFFu, (size_t)bs, st); rc != PDSC_OK) return rc;
-    const int nb = ceil_div(k, 16);
-#define PDSC_SOLVE(NBV) launch_seed_solve<NBV>(normed, src, tgt, knn_idx, sigma, sigma_spat, eig_iters, conv_mask, nullptr, seed_trans, \
-                                               seed_weights, bs, N, S, k, num_iterations, st)
-    const int rc = nb == 1 ? PDSC_SOLVE(1) : nb == 2 ? PDSC_SOLVE(2) : nb == 3 ? PDSC_SOLVE(3) : PDSC_SOLVE(4);
-#undef PDSC_SOLVE
+    const int rc = launch_seed_solve_nb(normed, src, tgt, knn_idx, sigma, sigma_spat, eig_iters, conv_mask, seed_M, seed_trans, seed_weights,
+                                        bs, N, S, k, num_iterations, st);
     if (rc != PDSC_OK) return rc;
     // the reference's global early exit (models/PointDSC.py:354-356) may have picked an earlier iterate for some pair (its seeds are
     // re-solved) -- and every slot becomes its 4x4: one launch (fixup_kabsch_kernel)
@@ -370,33 +376,22 @@ int launch_seed_solve_forward(const float* normed, const float* src, const float
 }
 }  // namespace pdsc
 
+// seed_trans != NULL: the forward's own launches (launch_seed_solve_forward); NULL: the solver launch alone
 extern "C" int pdsc_seed_solve(const float* normed, const float* src, const float* tgt, const int* knn_idx, const float* sigma,
                                const float* sigma_spat, float* eig_iters, unsigned int* conv_mask, float* seed_M, float* seed_trans,
                                float* seed_weights, int bs, int N, int S, int k, int num_iterations, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    if (seed_trans)
+        return pdsc::launch_seed_solve_forward(normed, src, tgt, knn_idx, sigma, sigma_spat, eig_iters, conv_mask, seed_M, seed_trans,
+                                               seed_weights, bs, N, S, k, num_iterations, /*mask_ready=*/false, st);
     PDSC_REQUIRE(normed && src && tgt && knn_idx && sigma && sigma_spat && eig_iters && conv_mask, "pdsc_seed_solve: null pointer");
     PDSC_REQUIRE(bs > 0 && N > 0 && S > 0, "pdsc_seed_solve: bs=%d N=%d S=%d", bs, N, S);
     PDSC_REQUIRE(k >= 1 && k <= PDSC_MAX_K, "pdsc_seed_solve: k=%d (max %d)", k, PDSC_MAX_K);
     PDSC_REQUIRE(num_iterations >= 0 && num_iterations <= PDSC_MAX_POWER_ITERS, "pdsc_seed_solve: num_iterations=%d (max %d)",
                  num_iterations, PDSC_MAX_POWER_ITERS);
-    hipStream_t st = (hipStream_t)stream;
     if (const int rc = pdsc::launch_fill_u32(conv_mask, 0xFFFFFFFFu, (size_t)bs, st); rc != PDSC_OK) return rc;
-    const int nb = pdsc::ceil_div(k, 16);
-#define PDSC_SOLVE(NBV) pdsc::launch_seed_solve<NBV>(normed, src, tgt, knn_idx, sigma, sigma_spat, eig_iters, conv_mask, seed_M, seed_trans, \
-                                                     seed_weights, bs, N, S, k, num_iterations, st)
-    int rc = nb == 1 ? PDSC_SOLVE(1) : nb == 2 ? PDSC_SOLVE(2) : nb == 3 ? PDSC_SOLVE(3) : PDSC_SOLVE(4);
-#undef PDSC_SOLVE
-    if (rc != PDSC_OK || !seed_trans) return rc;
-    if (num_iterations <= 0) {
-        hipLaunchKernelGGL(pdsc::kabsch_batch_kernel, dim3(pdsc::ceil_div(bs * S, 64)), dim3(64), 0, st, seed_trans, bs * S);
-        return pdsc::check_launch("pdsc_seed_solve(kabsch)");
-    }
-    // the reference's global early exit (models/PointDSC.py:354-356) picked an earlier iterate for some pair: re-solve its seeds
-    hipLaunchKernelGGL(pdsc::seed_transform_kernel, dim3(S, bs), dim3(64), 0, st, src, tgt, knn_idx, eig_iters, conv_mask, seed_trans,
-                       seed_weights, N, S, k, num_iterations, 1);
-    rc = pdsc::check_launch("pdsc_seed_solve(early-exit fix-up)");
-    if (rc != PDSC_OK) return rc;
-    hipLaunchKernelGGL(pdsc::kabsch_batch_kernel, dim3(pdsc::ceil_div(bs * S, 64)), dim3(64), 0, st, seed_trans, bs * S);
-    return pdsc::check_launch("pdsc_seed_solve(kabsch)");
+    return pdsc::launch_seed_solve_nb(normed, src, tgt, knn_idx, sigma, sigma_spat, eig_iters, conv_mask, seed_M, nullptr, nullptr, bs, N, S, k,
+                                      num_iterations, st);
 }
 
 extern "C" int pdsc_seed_transforms(const float* src, const float* tgt, const int* knn_idx, const float* eig_iters,
@@ -406,7 +401,7 @@ extern "C" int pdsc_seed_transforms(const float* src, const float* tgt, const in
     PDSC_REQUIRE(bs > 0 && N > 0 && S > 0 && k >= 1 && k <= PDSC_MAX_K, "pdsc_seed_transforms: bs=%d N=%d S=%d k=%d", bs, N, S, k);
     PDSC_REQUIRE(num_iterations >= 0 && num_iterations <= PDSC_MAX_POWER_ITERS, "pdsc_seed_transforms: num_iterations=%d", num_iterations);
     hipLaunchKernelGGL(pdsc::seed_transform_kernel, dim3(S, bs), dim3(64), 0, (hipStream_t)stream, src, tgt, knn_idx, eig_iters,
-                       conv_mask, seed_trans, seed_weights, N, S, k, num_iterations, 0);
+                       conv_mask, seed_trans, seed_weights, N, S, k, num_iterations);
     const int rc = pdsc::check_launch("pdsc_seed_transforms");
     if (rc != PDSC_OK) return rc;
     hipLaunchKernelGGL(pdsc::kabsch_batch_kernel, dim3(pdsc::ceil_div(bs * S, 64)), dim3(64), 0, (hipStream_t)stream, seed_trans, bs * S);

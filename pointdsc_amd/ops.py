@@ -553,6 +553,27 @@ def seed_transforms(src, tgt, knn_idx, iters, mask, num_iterations: int):
 
 
 @_on_device
+def seed_solve(normed, src, tgt, knn_idx, sigma, sigma_spat, num_iterations: int, want_M: bool = False):
+    """The per-seed solver as the testing forward launches it (pdsc_seed_solve with seed_trans: the fused solver, then the early-exit
+    fix-up with the 3x3 decompositions) -> (iters [bs,S,max(num_iterations,1),64], mask [bs] int32, trans [bs,S,4,4],
+    weights [bs,S,k], M [bs,S,k,k] or None)."""
+    lib = _lib.load()
+    normed, src, tgt = _chk(normed, "normed"), _chk(src, "src"), _chk(tgt, "tgt")
+    knn_idx = _chk(knn_idx, "knn_idx", torch.int32)
+    sigma, sigma_spat = _chk(sigma.reshape(-1), "sigma"), _chk(sigma_spat.reshape(-1), "sigma_spat")
+    bs, n = src.shape[0], src.shape[1]
+    s, k = knn_idx.shape[1], knn_idx.shape[2]
+    iters = torch.zeros(bs, s, max(num_iterations, 1), 64, device=src.device, dtype=torch.float32)
+    mask = torch.empty(bs, device=src.device, dtype=torch.int32)
+    M = torch.empty(bs, s, k, k, device=src.device, dtype=torch.float32) if want_M else None
+    trans = torch.empty(bs, s, 4, 4, device=src.device, dtype=torch.float32)
+    w = torch.empty(bs, s, k, device=src.device, dtype=torch.float32)
+    _lib.check(lib.pdsc_seed_solve(_p(normed), _p(src), _p(tgt), _p(knn_idx), _p(sigma), _p(sigma_spat), _p(iters), _p(mask), _p(M),
+                                   _p(trans), _p(w), bs, n, s, k, num_iterations, _stream()), "pdsc_seed_solve")
+    return iters, mask, trans, w, M
+
+
+@_on_device
 def seed_solve_backward(normed, src, tgt, knn_idx, sigma, sigma_spat, mask, num_iterations: int, d_seed_trans,
                         want_dnormed: bool = True, want_dsigma: bool = True):
     """Backward of seed_power_iteration + seed_transforms (pdsc_seed_solve_backward): normed [bs,N,128], src, tgt [bs,N,3],
