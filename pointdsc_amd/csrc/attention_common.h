@@ -47,4 +47,21 @@ int launch_attention_combine(const AttArgs& a, int bs, hipStream_t st);
 int launch_attention_fp32(const float* qkv, const float* compat, long long ld, float* msg, void* scratch, size_t scratch_bytes, int bs, int N,
                           int nsplit, const int* nvalid, hipStream_t st, float* lse = nullptr);
 
+// ---- split-precision attention (attention_split.hip); nvalid: ragged batches (ragged.h), NULL = every pair has N -------------
+// msg != NULL: merged output rows (key split 1, or the combine launch); msg == NULL: the key-split partials stay in `scratch`
+int launch_attention_split_ex(const void* q_split, const void* kv_tiles, const void* compat, int compat_format, long long ld,
+                              float* msg, void* scratch, size_t scratch_bytes, int bs, int N, int nsplit, int partial_layout,
+                              const int* nvalid, hipStream_t st, int value_width = PDSC_CHANNELS);
+// value_width (both launchers): channels of V in the tile images and of the partials -- PDSC_CHANNELS, or 64 for the folded value
+// projection (pdsc_config.value_fold; point-fragment partials only)
+
+// leaf form (sc_attention_split_kernel<..., MG = true>): C leaf partials per query, left in `scratch` in point-fragment order for
+// the H3 layer kernel to merge
+constexpr int PDSC_ATT_MAX_LEAVES = 8;       // = MERGE_MAX_SPLIT_H3 (merge_partials.h): what the layer kernel merges while it loads
+int attention_leaf_count(int N);
+int leaf_plan(int bs, int N, int leaves_mode, int* nw_out, int* nsplit_out, int* nleaf_out);
+int launch_attention_leaves(const void* q_split, const void* kv_tiles, const void* compat, int compat_format, long long ld,
+                            void* scratch, size_t scratch_bytes, int bs, int N, int leaves_mode, const int* nvalid, int n_min,
+                            hipStream_t st, int value_width = PDSC_CHANNELS);
+
 }  // namespace pdsc

@@ -185,6 +185,25 @@ def test_folded_forward_is_batch_invariant_and_repeatable():
 
 
 @pytest.mark.gpu
+def test_folded_key_split_forward_over_the_fp32_matrix_treats_a_pair_alone_as_in_a_batch(lib):
+    """The per-launch key split with the fold over the fp32 spatial-consistency matrix below 48 query blocks of 256: the 4-wave,
+    fp32-compat, 64-wide key-split instantiation of the attention kernel, which no other test launches.  N = 255 is the smallest
+    class with a key split above one (8 key tiles, the last one ragged); one pair and two pairs get the same split there, so a
+    pair's arithmetic does not depend on the batch: bit equality with the pairs run one at a time."""
+    n, bs = 255, 2
+    assert lib.pdsc_attention_split_default_split(1, n) == lib.pdsc_attention_split_default_split(bs, n) == 2
+    model = _bench("n1000_b1")
+    model.att_leaves, model.compat_format, model.value_fold = "per_launch", "f32", 1
+    batch = synthetic.make_batch(bs, n, seed=255, inlier_ratio=0.3)
+    both = _run(model, batch)
+    assert torch.isfinite(both["final_trans"]).all()
+    for i in range(bs):
+        one = _run(model, {k: v[i:i + 1] for k, v in batch.items()})
+        assert torch.equal(one["final_trans"].view(torch.int32), both["final_trans"][i:i + 1].view(torch.int32)), i
+        assert torch.equal(one["final_labels"], both["final_labels"][i:i + 1]), i
+
+
+@pytest.mark.gpu
 def test_fold_leaves_calls_beyond_its_size_bound_on_the_128_channel_path():
     """N = 20000 > PDSC_VALUE_FOLD_MAX_N: value_fold 1 and 0 give the same bits."""
     model = _bench("multiway_n20000_b1")
