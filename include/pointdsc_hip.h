@@ -12,7 +12,7 @@
  *     pdsc_forward_validation; the weight packers pdsc_wpack_floats / _offset, pdsc_wsplit_bytes / _offset / _build; the workspace
  *     queries pdsc_workspace_bytes / _offset; pdsc_encoder_range_probe; pdsc_version / pdsc_last_error; and, for the callers either
  *     side of the path (SURVEY.md section 8 f-2 .. f-4), pdsc_match_* / pdsc_select_correspondences / pdsc_build_corr_pos,
- *     pdsc_sm_baseline*, pdsc_pmc_*, pdsc_cal_confidence, pdsc_eval_stats, pdsc_*_loss*, pdsc_icp_*, pdsc_information_*, pdsc_voxel_*, pdsc_cloud_*.
+ *     pdsc_sm_baseline*, pdsc_pmc_*, pdsc_cal_confidence, pdsc_eval_stats, pdsc_*_loss*, pdsc_pointwise_train_*, pdsc_icp_*, pdsc_information_*, pdsc_voxel_*, pdsc_cloud_*.
  *   STAGE LEVEL -- one entry point per reference stage (sections a-1 .. a-11 below), the plan / size queries that go with them,
  *     pdsc_selftest_* and the diagnostic hooks.  The forward does not go through them (it calls the same launchers directly); they
  *     exist so that every stage can be parity-checked on its own (tests/test_gpu_parity.py), for the tools, and for a maintainer
@@ -1057,6 +1057,40 @@ int pdsc_seed_solve_backward(const float* normed, const float* src, const float*
  *   over the batch included; a pair with no probs > 0 gets exact zeros.  fp64 sums in a fixed order; workspace as the losses'. */
 int pdsc_transformation_loss_grad(const float* trans, const float* src, const float* tgt, const float* probs, double* dtrans,
                                   void* ws, size_t ws_bytes, int bs, int N, void* stream);
+
+/* ---- train-mode point-wise layer: Conv1d(k=1) -> BatchNorm1d (batch statistics) -> ReLU, forward and backward (DESIGN.md
+ *      section 8 f-15; reference models/PointDSC.py:12-23,54-61 under model.train()) ------------------------------------------
+ * Channel-last rows: X [M][Cin], W [Cout][Cin], b, gamma, beta, running_mean, running_var [Cout], all fp32 and contiguous.
+ * Supported (Cin, Cout): (128,128) PointCN_layer_i, (128,64) fc_message.0-2, (64,64) fc_message.3-5; M >= 2, any value.
+ * pdsc_pointwise_train_forward:
+ *   Y = X W^T + b;   mean_c, var_c = mean and BIASED variance of Y[:, c] over the M rows;   invstd = 1 / sqrt(var + eps);
+ *   Z = relu(gamma (Y - mean) invstd + beta);
+ *   running_mean <- (1 - momentum) running_mean + momentum mean;
+ *   running_var  <- (1 - momentum) running_var  + momentum var M / (M - 1)      (the unbiased variance, as F.batch_norm(training=True))
+ *   Outputs Z [M][Cout], and for the backward Y [M][Cout], mean [Cout], invstd [Cout] -- the two statistics in FP64 (Z is computed
+ *   from their fp32 roundings, in fp32); both running statistics are updated IN PLACE.
+ *   The variance is mean-centred throughout (per 64-row tile in fp64, tiles merged as sum M2_t + n_t (mean_t - mean)^2 in fp64):
+ *   a channel offset many times its spread costs nothing.
+ * pdsc_pointwise_train_backward, given dZ [M][Cout] and Y, mean, invstd of the forward (the ReLU mask is rebuilt from Y with the
+ * forward's own expression: the same bits as Z > 0; behind the mask xh and dY are evaluated in fp64 from the fp64 statistics and
+ * rounded once -- with few rows dY is a small difference of O(1) terms):
+ *   g = dZ [Z > 0];   dbeta = sum_rows g;   dgamma = sum_rows g xh,  xh = (Y - mean) invstd;
+ *   dY = gamma invstd (g - dbeta / M - xh dgamma / M);   db = sum_rows dY (zero in exact arithmetic, computed as autograd does);
+ *   dW [Cout][Cin] = dY^T X;   dX [M][Cin] = dY W.
+ *   Each of dX, dW, db, dgamma, dbeta may be NULL (not wanted; at least one must be asked for); the ones asked for have the bits
+ *   they have when all are.
+ * The three products are exact fp32 on v_mfma_f32_32x32x2_f32.  No floating-point atomics: per-tile and per-workgroup partials in
+ * `ws` (pdsc_pointwise_train_workspace_bytes; 8-byte aligned, the same size serves both calls) added in index order; repeat calls
+ * are bit-identical.  X, W, Y, Z, dZ, dX must be 16-byte aligned.  Asynchronous on `stream`, no allocation, no synchronisation, no
+ * memset.  Returns PDSC_ERR_ARG (null pointer, unsupported (Cin, Cout), M < 2, momentum outside [0,1], eps < 0, misaligned
+ * pointer) or PDSC_ERR_WORKSPACE with nothing enqueued; pdsc_pointwise_train_workspace_bytes returns 0 for unsupported sizes. */
+size_t pdsc_pointwise_train_workspace_bytes(int M, int Cin, int Cout);
+int pdsc_pointwise_train_forward(const float* X, const float* W, const float* b, const float* gamma, const float* beta,
+                                 float* running_mean, float* running_var, float momentum, float eps, float* Y, float* Z,
+                                 double* mean, double* invstd, void* ws, size_t ws_bytes, int M, int Cin, int Cout, void* stream);
+int pdsc_pointwise_train_backward(const float* X, const float* W, const float* gamma, const float* beta, const float* Y,
+                                  const double* mean, const double* invstd, const float* dZ, float* dX, float* dW, float* db,
+                                  float* dgamma, float* dbeta, void* ws, size_t ws_bytes, int M, int Cin, int Cout, void* stream);
 
 #ifdef __cplusplus
 }

@@ -145,6 +145,9 @@ SIGNATURES = {
     "pdsc_seed_solve_backward_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "pdsc_seed_solve_backward": (_i, [_vp] * 11 + [_sz, _i, _i, _i, _i, _i, _vp]),
     "pdsc_transformation_loss_grad": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _vp]),
+    "pdsc_pointwise_train_workspace_bytes": (_sz, [_i, _i, _i]),
+    "pdsc_pointwise_train_forward": (_i, [_vp] * 7 + [_f, _f] + [_vp] * 5 + [_sz, _i, _i, _i, _vp]),
+    "pdsc_pointwise_train_backward": (_i, [_vp] * 14 + [_sz, _i, _i, _i, _vp]),
     "pdsc_icp_workspace_bytes": (_sz, [_i, _i, _i]),
     "pdsc_icp_refine": (_i, [_vp, _vp, _vp, _vp, _vp, C.c_double, C.c_double, C.c_double, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                              _sz, _i, _i, _i, _vp]),

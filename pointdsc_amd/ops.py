@@ -647,3 +647,78 @@ def post_refinement(initial_trans, src, tgt, threshold: float, max_iters: int = 
     _lib.check(lib.pdsc_post_refinement(_p(initial_trans), _p(src), _p(tgt), float(threshold), max_iters, _p(final),
                                         _p(solves), bs, n, _stream()), "pdsc_post_refinement")
     return final, solves
+
+
+POINTWISE_TRAIN_SHAPES = ((128, 128), (128, 64), (64, 64))      # (Cin, Cout) of pdsc_pointwise_train_*
+
+
+def _pointwise_train_dims(x: torch.Tensor, weight: torch.Tensor, what: str) -> Tuple[int, int, int]:
+    if x.dim() != 2 or weight.dim() != 2 or weight.shape[1] != x.shape[1]:
+        raise ValueError(f"{what}: x must be [M,Cin] and weight [Cout,Cin], got {tuple(x.shape)} {tuple(weight.shape)}")
+    m, cin, cout = x.shape[0], x.shape[1], weight.shape[0]
+    if (cin, cout) not in POINTWISE_TRAIN_SHAPES:
+        raise ValueError(f"{what}: (Cin, Cout) = ({cin}, {cout}); supported: {POINTWISE_TRAIN_SHAPES}")
+    if m < 2:
+        raise ValueError(f"{what}: M = {m} rows (batch statistics need at least 2 values per channel)")
+    return m, cin, cout
+
+
+def _pointwise_train_workspace(lib, m: int, cin: int, cout: int, device) -> torch.Tensor:
+    nb = int(lib.pdsc_pointwise_train_workspace_bytes(m, cin, cout))
+    return torch.empty(max((nb + 7) // 8, 1), device=device, dtype=torch.float64)
+
+
+@_on_device
+def pointwise_train_forward(x, weight, bias, gamma, beta, running_mean, running_var, momentum: float = 0.1, eps: float = 1e-5):
+    """Conv1d(k=1) -> BatchNorm1d with batch statistics -> ReLU on rows (pdsc_pointwise_train_forward): x [M,Cin], weight [Cout,Cin],
+    bias, gamma, beta, running_mean, running_var [Cout] fp32 -> (z [M,Cout], y [M,Cout], mean [Cout] fp64, invstd [Cout] fp64).
+    running_mean and running_var are updated IN PLACE (they must be contiguous: the kernel writes through their pointers)."""
+    lib = _lib.load()
+    x, weight = _chk(x, "x"), _chk(weight, "weight")
+    m, cin, cout = _pointwise_train_dims(x, weight, "pointwise_train_forward")
+    bias, gamma, beta = _chk(bias, "bias"), _chk(gamma, "gamma"), _chk(beta, "beta")
+    for t, name in ((running_mean, "running_mean"), (running_var, "running_var")):
+        if not _chk(t, name).data_ptr() == t.data_ptr():
+            raise ValueError(f"{name} must be contiguous: it is updated in place")
+    for t, name in ((bias, "bias"), (gamma, "gamma"), (beta, "beta"), (running_mean, "running_mean"), (running_var, "running_var")):
+        if t.shape != (cout,):
+            raise ValueError(f"pointwise_train_forward: {name} must be [{cout}], got {tuple(t.shape)}")
+    y = torch.empty(m, cout, device=x.device, dtype=torch.float32)
+    z = torch.empty_like(y)
+    mean = torch.empty(cout, device=x.device, dtype=torch.float64)
+    invstd = torch.empty_like(mean)
+    ws = _pointwise_train_workspace(lib, m, cin, cout, x.device)
+    _lib.check(lib.pdsc_pointwise_train_forward(_p(x), _p(weight), _p(bias), _p(gamma), _p(beta), _p(running_mean), _p(running_var),
+                                                float(momentum), float(eps), _p(y), _p(z), _p(mean), _p(invstd), _p(ws),
+                                                ws.numel() * 8, m, cin, cout, _stream()), "pdsc_pointwise_train_forward")
+    return z, y, mean, invstd
+
+
+@_on_device
+def pointwise_train_backward(x, weight, gamma, beta, y, mean, invstd, dz, want_dx: bool = True, want_dw: bool = True,
+                             want_db: bool = True, want_dgamma: bool = True, want_dbeta: bool = True):
+    """Backward of pointwise_train_forward (pdsc_pointwise_train_backward): x, weight, gamma, beta as the forward took them, y, mean,
+    invstd as it returned them, dz [M,Cout] -> (dx [M,Cin], dw [Cout,Cin], db, dgamma, dbeta [Cout]); None where not wanted."""
+    if not (want_dx or want_dw or want_db or want_dgamma or want_dbeta):
+        raise ValueError("pointwise_train_backward: ask for at least one gradient")
+    lib = _lib.load()
+    x, weight = _chk(x, "x"), _chk(weight, "weight")
+    m, cin, cout = _pointwise_train_dims(x, weight, "pointwise_train_backward")
+    gamma, beta = _chk(gamma, "gamma"), _chk(beta, "beta")
+    mean, invstd = _chk(mean, "mean", torch.float64), _chk(invstd, "invstd", torch.float64)
+    y, dz = _chk(y, "y"), _chk(dz, "dz")
+    if y.shape != (m, cout) or dz.shape != (m, cout):
+        raise ValueError(f"pointwise_train_backward: y and dz must be [{m},{cout}], got {tuple(y.shape)} {tuple(dz.shape)}")
+    for t, name in ((gamma, "gamma"), (beta, "beta"), (mean, "mean"), (invstd, "invstd")):
+        if t.shape != (cout,):
+            raise ValueError(f"pointwise_train_backward: {name} must be [{cout}], got {tuple(t.shape)}")
+
+    def out(want, *shape):
+        return torch.empty(*shape, device=x.device, dtype=torch.float32) if want else None
+    dx, dw = out(want_dx, m, cin), out(want_dw, cout, cin)
+    db, dgamma, dbeta = out(want_db, cout), out(want_dgamma, cout), out(want_dbeta, cout)
+    ws = _pointwise_train_workspace(lib, m, cin, cout, x.device)
+    _lib.check(lib.pdsc_pointwise_train_backward(_p(x), _p(weight), _p(gamma), _p(beta), _p(y), _p(mean), _p(invstd), _p(dz), _p(dx),
+                                                 _p(dw), _p(db), _p(dgamma), _p(dbeta), _p(ws), ws.numel() * 8, m, cin, cout,
+                                                 _stream()), "pdsc_pointwise_train_backward")
+    return dx, dw, db, dgamma, dbeta

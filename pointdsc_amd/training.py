@@ -6,7 +6,9 @@ per layer) and the feature-similarity matrix M (its gradient for an arbitrary dM
 mask).  ``sc_attention`` is a ``torch.autograd.Function`` over ``ops.sc_attention_lse`` / ``ops.sc_attention_backward``;
 ``feature_similarity`` one over ``ops.feature_compat`` / ``ops.feature_compat_backward``; (f-14) ``seed_solve`` one over the per-seed
 solver (``ops.seed_power_iteration`` + ``ops.seed_transforms`` / ``ops.seed_solve_backward``), which gives ``final_trans`` a
-gradient.  The 1x1 convolutions, batch-norms and ReLUs around them are operations torch differentiates well and stay torch's.  ``NonLocalBlock`` is the reference block
+gradient.  The 1x1 convolutions, batch-norms and ReLUs around them are torch's by default; (f-15) ``conv_bn_relu`` is the fused
+train-mode Conv1d(k=1) + BatchNorm1d + ReLU over ``ops.pointwise_train_forward`` / ``ops.pointwise_train_backward``, which
+``TrainablePointDSC(fused_layers=True)`` uses for the blocks' three such groups.  ``NonLocalBlock`` is the reference block
 (models/PointDSC.py:9-45) for a trainer that swaps layer by layer; ``train_forward`` is the reference's whole forward without the
 'testing' key (models/PointDSC.py:143-197) on a ``PointDSC`` module's own parameters, and ``TrainablePointDSC`` the module that
 calls it in ``train()`` mode.  ``PointDSC.forward`` itself keeps refusing ``train()`` mode.
@@ -231,30 +233,107 @@ def seed_solve(normed: torch.Tensor, src: torch.Tensor, tgt: torch.Tensor, knn_i
                             int(num_iterations))
 
 
+# ---------------------------------------------------------------------------------------------------------------------------
+# f-15: the fused train-mode point-wise layer
+# ---------------------------------------------------------------------------------------------------------------------------
+class _ConvBnRelu(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, bias, bn_weight, bn_bias, running_mean, running_var, momentum, eps):
+        z, y, mean, invstd = ops.pointwise_train_forward(x, weight, bias, bn_weight, bn_bias, running_mean, running_var, momentum, eps)
+        ctx.save_for_backward(x, weight, bn_weight, bn_bias, y, mean, invstd)      # z is not kept: the mask is rebuilt from y
+        return z
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dz):
+        x, weight, bn_weight, bn_bias, y, mean, invstd = ctx.saved_tensors
+        need = ctx.needs_input_grad[:5]
+        if not any(need):
+            return (None,) * 9
+        grads = ops.pointwise_train_backward(x, weight, bn_weight, bn_bias, y, mean, invstd, dz.contiguous(), *need)
+        return (*grads, None, None, None, None)
+
+
+def conv_bn_relu(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, bn_weight: torch.Tensor, bn_bias: torch.Tensor,
+                 running_mean: torch.Tensor, running_var: torch.Tensor, momentum: float = 0.1, eps: float = 1e-5) -> torch.Tensor:
+    """relu(batch_norm(x weight^T + bias)) with BATCH statistics, on rows, in three device launches forward and four backward
+    (Conv1d(k=1) -> BatchNorm1d -> ReLU of models/PointDSC.py:12-23,54-61 in train() mode), with gradients for x, weight, bias,
+    bn_weight and bn_bias; only those that require grad are computed.
+    x [M,Cin] fp32, weight [Cout,Cin] or the Conv1d's [Cout,Cin,1], the rest [Cout]; (Cin, Cout) one of (128,128), (128,64),
+    (64,64); M >= 2 -> z [M,Cout].  running_mean and running_var are updated IN PLACE as F.batch_norm(training=True) does
+    (momentum, unbiased variance); they get no gradient: one that requires grad is refused rather than silently given None."""
+    for t, name in ((running_mean, "running_mean"), (running_var, "running_var")):
+        if t.requires_grad:
+            raise ValueError(f"conv_bn_relu: {name} gets no gradient (it is a running statistic, updated in place); detach it")
+    tensors = ((x, "x"), (weight, "weight"), (bias, "bias"), (bn_weight, "bn_weight"), (bn_bias, "bn_bias"),
+               (running_mean, "running_mean"), (running_var, "running_var"))
+    for t, name in tensors:
+        if t.dtype != torch.float32:
+            raise TypeError(f"{name} must be torch.float32, got {t.dtype}")
+    if weight.dim() == 3 and weight.shape[2] == 1:
+        weight = weight[:, :, 0]
+    if x.dim() != 2 or weight.dim() != 2 or weight.shape[1] != x.shape[1]:
+        raise ValueError(f"conv_bn_relu: x must be [M,Cin] and weight [Cout,Cin] or [Cout,Cin,1], got {tuple(x.shape)} {tuple(weight.shape)}")
+    m, cin, cout = x.shape[0], x.shape[1], weight.shape[0]
+    if (cin, cout) not in ops.POINTWISE_TRAIN_SHAPES:
+        raise ValueError(f"conv_bn_relu: (Cin, Cout) = ({cin}, {cout}); supported: {ops.POINTWISE_TRAIN_SHAPES}")
+    if m < 2:
+        raise ValueError(f"conv_bn_relu: M = {m} rows (batch statistics need at least 2 values per channel)")
+    for t, name in tensors[2:]:
+        if t.shape != (cout,):
+            raise ValueError(f"conv_bn_relu: {name} must be [{cout}], got {tuple(t.shape)}")
+    if not (running_mean.is_contiguous() and running_var.is_contiguous()):
+        raise ValueError("conv_bn_relu: running_mean and running_var must be contiguous (they are updated in place)")
+    if not 0.0 <= float(momentum) <= 1.0 or float(eps) < 0.0:
+        raise ValueError(f"conv_bn_relu: momentum = {momentum} (0 .. 1), eps = {eps} (>= 0)")
+    for t, name in tensors:
+        if not t.is_cuda:
+            raise RuntimeError(f"{name} must live on the GPU (pointdsc_amd has no CPU path)")
+    z = _ConvBnRelu.apply(x.contiguous(), weight.contiguous(), bias, bn_weight, bn_bias, running_mean, running_var, float(momentum),
+                          float(eps))
+    # the library wrote through the pointers: tell torch (the eval-mode module keys its packed weights on the version counters)
+    torch.autograd.graph.increment_version(running_mean)
+    torch.autograd.graph.increment_version(running_var)
+    return z
+
+
 def _conv_rows(conv: nn.Conv1d, x: torch.Tensor) -> torch.Tensor:
     """A 1x1 Conv1d on channel-last rows [M, Cin] -> [M, Cout]."""
     return F.linear(x, conv.weight[:, :, 0], conv.bias)
 
 
-def _train_encoder(enc, x: torch.Tensor, compat: torch.Tensor, bs: int, n: int) -> torch.Tensor:
+def _conv_bn_relu_rows(conv: nn.Conv1d, bn: nn.BatchNorm1d, x: torch.Tensor, fused: bool) -> torch.Tensor:
+    """Conv1d(k=1) -> BatchNorm1d -> ReLU on rows.  fused: one ``conv_bn_relu`` on the modules' own parameters and buffers, with
+    num_batches_tracked incremented as BatchNorm1d.forward does; a batch-norm without running statistics or with momentum=None (a
+    cumulative average, which the kernel does not compute) keeps torch's path, as does fused=False."""
+    if not fused or not bn.track_running_stats or bn.momentum is None or bn.running_mean is None or not bn.affine:
+        return F.relu(bn(_conv_rows(conv, x)))
+    if bn.num_batches_tracked is not None:
+        bn.num_batches_tracked.add_(1)
+    return conv_bn_relu(x, conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.momentum, bn.eps)
+
+
+def _train_encoder(enc, x: torch.Tensor, compat: torch.Tensor, bs: int, n: int, fused_layers: bool = False) -> torch.Tensor:
     """NonLocalNet.forward (models/PointDSC.py:65-77) on rows [bs*N, C].  The batch-norms are the modules' own forward on (M, C)
     rows (BatchNorm1d takes that layout: the statistics run over the bs * N rows exactly as over [bs, C, N]): F.batch_norm on
-    the module's buffers with batch statistics, running_mean / running_var / num_batches_tracked updated by torch itself."""
+    the module's buffers with batch statistics, running_mean / running_var / num_batches_tracked updated by torch itself.
+    fused_layers: the three conv + batch-norm + ReLU groups of every block run through ``conv_bn_relu`` instead (f-15); layer0,
+    the q|k|v projection, fc_message.6 with its residual stay torch's."""
     feat = _conv_rows(enc.layer0, x)
     for i in range(enc.num_layers):
         pcn, nl = enc.blocks[f"PointCN_layer_{i}"], enc.blocks[f"NonLocal_layer_{i}"]
-        feat = F.relu(pcn[1](_conv_rows(pcn[0], feat)))
+        feat = _conv_bn_relu_rows(pcn[0], pcn[1], feat, fused_layers)
         w = torch.cat((nl.projection_q.weight[:, :, 0] * Q_SCALE, nl.projection_k.weight[:, :, 0], nl.projection_v.weight[:, :, 0]))
         b = torch.cat((nl.projection_q.bias * Q_SCALE, nl.projection_k.bias, nl.projection_v.bias))
         msg = _SCAttentionRows.apply(F.linear(feat, w, b), compat, bs, n)
         fc = nl.fc_message
-        h = F.relu(fc[1](_conv_rows(fc[0], msg)))
-        h = F.relu(fc[4](_conv_rows(fc[3], h)))
+        h = _conv_bn_relu_rows(fc[0], fc[1], msg, fused_layers)
+        h = _conv_bn_relu_rows(fc[3], fc[4], h, fused_layers)
         feat = feat + _conv_rows(fc[6], h)
     return feat
 
 
-def train_forward(model: PointDSC, data, differentiable_trans: bool = False) -> dict:
+def train_forward(model: PointDSC, data, differentiable_trans: bool = False, fused_layers: bool = False) -> dict:
     """The reference's forward without the 'testing' key (models/PointDSC.py:143-197) in train() mode, on `model`'s own Parameters
     and buffers: batch-statistics batch-norm (running statistics updated as torch's BatchNorm1d does), autograd through the
     encoder, the classification head and M.  data: corr_pos [bs,N,in_dim], src_keypts, tgt_keypts [bs,N,3] on the GPU.
@@ -262,7 +341,9 @@ def train_forward(model: PointDSC, data, differentiable_trans: bool = False) -> 
     The spatial-consistency matrix, the seeds, their neighbours and the vote carry no gradient, as in the reference, and run as the
     library's stage ops.  differentiable_trans=False: neither do the power iteration and the Procrustes -- final_trans has no
     gradient and nothing is kept for one.  True: they run behind ``seed_solve`` and final_trans carries the gradient of the winning
-    seed of each pair into the features and sigma (the reference's cal_seed_trans under autograd); the values are the same."""
+    seed of each pair into the features and sigma (the reference's cal_seed_trans under autograd); the values are the same.
+    fused_layers=True: every Conv1d + BatchNorm1d + ReLU group of the encoder's blocks runs as ``conv_bn_relu`` (device kernels,
+    forward and backward) instead of torch's F.linear / F.batch_norm / F.relu: the same function, other rounding."""
     if not model.training:
         raise RuntimeError("train_forward needs the module in train() mode; in eval() mode call the module (PointDSC.forward)")
     if "testing" in data.keys():
@@ -284,7 +365,7 @@ def train_forward(model: PointDSC, data, differentiable_trans: bool = False) -> 
     with torch.cuda.device(dev):
         with torch.no_grad():
             compat = _pad_compat(ops.spatial_compat(src, tgt, model.sigma_spat), n)
-        feat = _train_encoder(model.encoder, corr_pos.view(bs * n, model.in_dim), compat, bs, n)
+        feat = _train_encoder(model.encoder, corr_pos.view(bs * n, model.in_dim), compat, bs, n, fused_layers=fused_layers)
         normed = F.normalize(feat, p=2, dim=-1).view(bs, n, CHANNELS)
         cls = model.classification
         logits = _conv_rows(cls[4], F.relu(_conv_rows(cls[2], F.relu(_conv_rows(cls[0], feat))))).view(bs, n)
@@ -316,13 +397,15 @@ class TrainablePointDSC(PointDSC):
     In ``train()`` mode ``forward`` is ``train_forward`` (batch statistics, autograd; the reference's Trainer.train_epoch,
     libs/trainer.py:79-136, runs on it unchanged); in ``eval()`` mode it is ``PointDSC.forward``, which sees every optimiser step
     through the weights' version counters.  ``differentiable_trans=True`` (keyword only, not part of the reference's constructor):
-    the train-mode ``final_trans`` carries a gradient (``train_forward``), what a transformation-loss weight above 0 needs."""
+    the train-mode ``final_trans`` carries a gradient (``train_forward``), what a transformation-loss weight above 0 needs.
+    ``fused_layers=True`` (keyword only, likewise): the blocks' conv + batch-norm + ReLU groups run as ``conv_bn_relu``."""
 
-    def __init__(self, *args, differentiable_trans: bool = False, **kwargs):
+    def __init__(self, *args, differentiable_trans: bool = False, fused_layers: bool = False, **kwargs):
         super().__init__(*args, **kwargs)
         self.differentiable_trans = bool(differentiable_trans)
+        self.fused_layers = bool(fused_layers)
 
     def forward(self, data):
         if self.training:
-            return train_forward(self, data, differentiable_trans=self.differentiable_trans)
+            return train_forward(self, data, differentiable_trans=self.differentiable_trans, fused_layers=self.fused_layers)
         return super().forward(data)

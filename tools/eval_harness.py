@@ -128,7 +128,7 @@ def train(a):
     """--train: a few optimiser steps of harness.train_epoch on the synthetic batches --validate uses; the validation meters of
     the same batches before and after."""
     from pointdsc_amd import TrainablePointDSC, synthetic
-    model = TrainablePointDSC(**dict(workloads.BASE_MODEL), differentiable_trans=a.weight_transformation > 0)
+    model = TrainablePointDSC(**dict(workloads.BASE_MODEL), differentiable_trans=a.weight_transformation > 0, fused_layers=a.fused_layers)
     if a.snapshot:
         print(model.load_state_dict(torch.load(a.snapshot, map_location="cpu"), strict=False))
     else:
@@ -185,6 +185,8 @@ def main():
     ap.add_argument("--lr", type=float, default=1e-4, help="with --train (config.py:52)")
     ap.add_argument("--weight-transformation", type=float, default=0.0, help="with --train: config.py:43, the weight of the transformation "
                     "loss in the objective; above 0 the model is built with differentiable_trans=True")
+    ap.add_argument("--fused-layers", action="store_true", help="with --train: the blocks' conv + batch-norm + ReLU groups as device kernels "
+                    "(TrainablePointDSC(fused_layers=True), pointdsc_amd.conv_bn_relu)")
     ap.add_argument("--json", action="store_true")
     a = ap.parse_args()
     if a.train:

@@ -12,6 +12,8 @@ The method of tools/attention_backward_bench.py: device events around a window o
 after `--warmup` calls; the two sides alternate inside one process; the median of `--rounds` windows is printed with the spread.
 These are CALL times, host work included.
 
+    --fused-layers       (f-15) the whole step of TrainablePointDSC(fused_layers=True) next to the default model's instead (same
+                         weights, same batch, same method); with --profile-steps the profiled model is the fused one
     --profile-steps K    run K device steps and exit: the program of the one `rocprofv3 --kernel-trace --stats` run
     --breakdown FILE     group the per-kernel table tools/rocpd_kernel_stats.py made of that run into the step's six parts"""
 import argparse
@@ -29,6 +31,7 @@ GROUPS = [      # first match wins
     ("attention backward", r"att_bwd_"),
     ("M forward + backward", r"gram_rows_kernel<2|feature_compat_backward"),
     ("losses", r"pdsc::(cls_|sm_loss_|trans_partial|trans_finish)"),
+    ("fused point-wise layers (conv + BN + ReLU)", r"pdsc::pwt_"),
     ("tail and compat (the library's other kernels)", r"pdsc::"),
     ("torch (GEMMs, batch-norm, point-wise, optimiser)", r"."),
 ]
@@ -61,6 +64,7 @@ def main():
     ap.add_argument("--layers", type=int, default=12)
     ap.add_argument("--profile-steps", type=int, default=0)
     ap.add_argument("--breakdown", default=None)
+    ap.add_argument("--fused-layers", action="store_true")
     a = ap.parse_args()
     if a.breakdown:
         return breakdown(a.breakdown)
@@ -88,19 +92,23 @@ def main():
     batch = {k: v.to(dev) for k, v in synthetic.make_batch(bs, n, seed=100, inlier_ratio=0.3).items()}
     data = {k: batch[k] for k in ("corr_pos", "src_keypts", "tgt_keypts")}
     gt = batch["gt_labels"]
-    model = training.TrainablePointDSC(num_layers=a.layers)
-    model.load_state_dict(state, strict=True)
-    model = model.to(dev).train()
-    opt = torch.optim.Adam(model.parameters(), lr=1e-4, weight_decay=1e-6)
     cls_fn, sm_fn = ClassificationLoss(False), SpectralMatchingLoss(False)
 
-    def device_step():
-        opt.zero_grad()
-        res = model(data)
-        loss = cls_fn(res["final_labels"], gt, device_stats=True)["loss"] + sm_fn(res["M"], gt)
-        loss.backward()
-        opt.step()
-        return loss
+    def make_step(fused):
+        model = training.TrainablePointDSC(num_layers=a.layers, fused_layers=fused)
+        model.load_state_dict({k: v.clone() for k, v in state.items()}, strict=True)
+        model = model.to(dev).train()
+        opt = torch.optim.Adam(model.parameters(), lr=1e-4, weight_decay=1e-6)
+
+        def step():
+            opt.zero_grad()
+            res = model(data)
+            loss = cls_fn(res["final_labels"], gt, device_stats=True)["loss"] + sm_fn(res["M"], gt)
+            loss.backward()
+            opt.step()
+            return loss
+        return step
+    device_step = make_step(a.fused_layers)
 
     if a.profile_steps:
         for _ in range(a.profile_steps):
@@ -109,6 +117,16 @@ def main():
         return
 
     print(f"bs={bs} N={n} layers={a.layers}: microseconds per call, median of {a.rounds} windows of {a.window} s (min .. max)")
+    if a.fused_layers:
+        torch_layers_step = make_step(False)
+        t_fused, t_plain = [], []
+        for _ in range(a.rounds):                         # alternate the two models
+            t_fused.append(timed(device_step, a.warmup, a.window)[0])
+            t_plain.append(timed(torch_layers_step, a.warmup, a.window)[0])
+        mf, mp = statistics.median(t_fused), statistics.median(t_plain)
+        print(f"  {'training step (forward, 2 losses, backward, Adam)':42s} fused_layers=True {spread(t_fused)}   "
+              f"fused_layers=False {spread(t_plain)}   False / True {mp / mf:6.2f}")
+        return
     gen = torch.Generator().manual_seed(bs * n)
     normed = F.normalize(torch.randn(bs, n, 128, generator=gen), dim=-1).to(dev).requires_grad_(True)
     sigma = torch.tensor([1.0], device=dev, requires_grad=True)
