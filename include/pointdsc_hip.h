@@ -1092,6 +1092,52 @@ int pdsc_pointwise_train_backward(const float* X, const float* W, const float* g
                                   const double* mean, const double* invstd, const float* dZ, float* dX, float* dW, float* db,
                                   float* dgamma, float* dbeta, void* ws, size_t ws_bytes, int M, int Cin, int Cout, void* stream);
 
+/* ---- train-mode plain linears: layer0, fc_message.6 with its residual, the q|k|v projection, the classification head, forward
+ *      and backward (reference models/PointDSC.py:36-45,65-77,171 under model.train()) ----------------
+ * Channel-last rows, all fp32 and contiguous, any M >= 1.  Every product is exact fp32 on v_mfma_f32_32x32x2_f32 over 64-row
+ * tiles.  No floating-point atomics: the backward's parameter gradients are one partial per persistent workgroup in `ws`, added in
+ * index order; repeat calls are bit-identical.  Every output of a backward may be NULL (not wanted; at least one must be asked
+ * for); the ones asked for have the bits they have when all are.  The forwards need no workspace; a backward's `ws` is always
+ * required (pdsc_*_train_workspace_bytes; 16-byte aligned).  Matrices (X, W*, R, Y, qkv, dY, dqkv, dX) must be 16-byte aligned.
+ * Asynchronous on `stream`, no allocation, no synchronisation, no memset.  Returns PDSC_ERR_ARG (null pointer, unsupported
+ * (Cin, Cout), M < 1, misaligned pointer) or PDSC_ERR_WORKSPACE with nothing enqueued; the workspace queries return 0 for
+ * unsupported sizes.
+ *
+ * pdsc_linear_train_forward:   Y [M][Cout] = X [M][Cin] W^T + b (+ R [M][Cout]; NULL: no residual).
+ * pdsc_linear_train_backward:  dX [M][Cin] = dY W;  dW [Cout][Cin] = dY^T X;  db [Cout] = sum_rows dY.  (dR is dY itself.)
+ *   dX and dW / db come from two independent launches: an output that is not wanted costs neither staging nor matrix instructions.
+ *   Supported (Cin, Cout): (1 .. 16, 128) layer0 (Cin padded with zeros in LDS), (64, 128) fc_message.6.
+ *
+ * pdsc_qkv_train_forward:   qkv [M][384] = (q_scale (X Wq^T + bq) | X Wk^T + bk | X Wv^T + bv), X [M][128], W* [128][128]: the
+ *   layout pdsc_sc_attention_lse takes.  The scale is applied to the PRODUCT, after the bias (one more rounding of q), not to the
+ *   weights.
+ * pdsc_qkv_train_backward:  with g = (q_scale dq | dk | dv) of dqkv [M][384], rounded once:  dX [M][128] = g_q Wq + g_k Wk + g_v Wv
+ *   (one accumulator, parts in this order);  dW* = g_*^T X;  db* = sum_rows g_*: the gradients of the UN-scaled parameters.
+ *
+ * pdsc_head_train_forward:   logits [M] = relu(relu(X W0^T + b0) W1^T + b1) . w2 + b2, X [M][128], W0 [32][128], W1 [32][32],
+ *   W2 [1][32], in one launch.  pre [M][64] (may be NULL: the training path passes NULL) receives the two pre-activations
+ *   (X W0^T + b0 | relu(.) W1^T + b1) as the kernel holds them, for tests that need the kernel's own ReLU masks.
+ * pdsc_head_train_backward:  from dlogits [M]: dX [M][128], dW0, db0, dW1, db1, dW2, db2.  Both pre-activations are recomputed per
+ *   tile by the forward's own code and the two ReLU masks taken from them: the forward's bits, no mask tensor.  One launch computes
+ *   all parameter gradients when any is wanted (and dX when it is), then the merge. */
+size_t pdsc_linear_train_workspace_bytes(int M, int Cin, int Cout);
+int pdsc_linear_train_forward(const float* X, const float* W, const float* b, const float* R, float* Y, int M, int Cin, int Cout,
+                              void* stream);
+int pdsc_linear_train_backward(const float* X, const float* W, const float* dY, float* dX, float* dW, float* db, void* ws,
+                               size_t ws_bytes, int M, int Cin, int Cout, void* stream);
+size_t pdsc_qkv_train_workspace_bytes(int M);
+int pdsc_qkv_train_forward(const float* X, const float* Wq, const float* bq, const float* Wk, const float* bk, const float* Wv,
+                           const float* bv, float q_scale, float* qkv, int M, void* stream);
+int pdsc_qkv_train_backward(const float* X, const float* Wq, const float* Wk, const float* Wv, float q_scale, const float* dqkv,
+                            float* dX, float* dWq, float* dbq, float* dWk, float* dbk, float* dWv, float* dbv, void* ws,
+                            size_t ws_bytes, int M, void* stream);
+size_t pdsc_head_train_workspace_bytes(int M);
+int pdsc_head_train_forward(const float* X, const float* W0, const float* b0, const float* W1, const float* b1, const float* W2,
+                            const float* b2, float* logits, float* pre, int M, void* stream);
+int pdsc_head_train_backward(const float* X, const float* W0, const float* b0, const float* W1, const float* b1, const float* W2,
+                             const float* dlogits, float* dX, float* dW0, float* db0, float* dW1, float* db1, float* dW2, float* db2,
+                             void* ws, size_t ws_bytes, int M, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

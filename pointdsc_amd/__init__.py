@@ -13,7 +13,8 @@ Only what the path needs lives here:
   training.py  the differentiable spatial-consistency attention (``sc_attention``: device forward and backward behind a
                ``torch.autograd.Function``), the reference's ``NonLocalBlock`` built on it, the differentiable feature-similarity
                matrix (``feature_similarity``), the differentiable per-seed solver (``seed_solve``), the fused train-mode point-wise
-               layer (``conv_bn_relu``), the train()-mode forward (``train_forward``) and ``TrainablePointDSC``
+               layer (``conv_bn_relu``), the train path's plain linears (``linear_rows``, ``qkv_projection``,
+               ``classification_head``), the train()-mode forward (``train_forward``) and ``TrainablePointDSC``
   multiway.py  the multiway driver's edge step (information matrix + overlap gate, voxel down-sampling, multi-scale ICP) and its
                pose-graph optimisation (node chain, LM with line process, edge pruning) on the device
   sharding.py  one-process-per-GPU sharding of pair batches + the single RCCL pose gather
@@ -24,8 +25,8 @@ from .features import (compute_fpfh_feature, estimate_normals, extract_fpfh_feat
 from .icp import icp_refine, registration_icp  # noqa: F401
 from .losses import ClassificationLoss, SpectralMatchingLoss, TransformationLoss  # noqa: F401
 from .model import PointDSC  # noqa: F401
-from .training import (NonLocalBlock, TrainablePointDSC, conv_bn_relu, feature_similarity, sc_attention, seed_solve,  # noqa: F401
-                       train_forward)
+from .training import (NonLocalBlock, TrainablePointDSC, classification_head, conv_bn_relu, feature_similarity,  # noqa: F401
+                       linear_rows, qkv_projection, sc_attention, seed_solve, train_forward)
 from .multiway import (align, global_optimization, information_matrix, local_refinement, loop_closure_edge,  # noqa: F401
                        multi_scale_icp, pose_graph_nodes, voxel_down_sample)
 
@@ -33,4 +34,5 @@ __all__ = ["PointDSC", "icp_refine", "registration_icp", "information_matrix", "
            "multi_scale_icp", "local_refinement", "align", "hybrid_neighbours", "estimate_normals", "compute_fpfh_feature",
            "fpfh_descriptors", "voxel_down_sample_with_normals", "extract_fpfh_features", "pose_graph_nodes", "global_optimization",
            "ClassificationLoss", "SpectralMatchingLoss", "TransformationLoss", "NonLocalBlock", "sc_attention",
-           "TrainablePointDSC", "train_forward", "feature_similarity", "seed_solve", "conv_bn_relu"]
+           "TrainablePointDSC", "train_forward", "feature_similarity", "seed_solve", "conv_bn_relu",
+           "linear_rows", "qkv_projection", "classification_head"]

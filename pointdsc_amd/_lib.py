@@ -148,6 +148,15 @@ SIGNATURES = {
     "pdsc_pointwise_train_workspace_bytes": (_sz, [_i, _i, _i]),
     "pdsc_pointwise_train_forward": (_i, [_vp] * 7 + [_f, _f] + [_vp] * 5 + [_sz, _i, _i, _i, _vp]),
     "pdsc_pointwise_train_backward": (_i, [_vp] * 14 + [_sz, _i, _i, _i, _vp]),
+    "pdsc_linear_train_workspace_bytes": (_sz, [_i, _i, _i]),
+    "pdsc_linear_train_forward": (_i, [_vp] * 5 + [_i, _i, _i, _vp]),
+    "pdsc_linear_train_backward": (_i, [_vp] * 7 + [_sz, _i, _i, _i, _vp]),
+    "pdsc_qkv_train_workspace_bytes": (_sz, [_i]),
+    "pdsc_qkv_train_forward": (_i, [_vp] * 7 + [_f, _vp, _i, _vp]),
+    "pdsc_qkv_train_backward": (_i, [_vp] * 4 + [_f] + [_vp] * 9 + [_sz, _i, _vp]),
+    "pdsc_head_train_workspace_bytes": (_sz, [_i]),
+    "pdsc_head_train_forward": (_i, [_vp] * 9 + [_i, _vp]),
+    "pdsc_head_train_backward": (_i, [_vp] * 15 + [_sz, _i, _vp]),
     "pdsc_icp_workspace_bytes": (_sz, [_i, _i, _i]),
     "pdsc_icp_refine": (_i, [_vp, _vp, _vp, _vp, _vp, C.c_double, C.c_double, C.c_double, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                              _sz, _i, _i, _i, _vp]),

@@ -722,3 +722,168 @@ def pointwise_train_backward(x, weight, gamma, beta, y, mean, invstd, dz, want_d
                                                  _p(dw), _p(db), _p(dgamma), _p(dbeta), _p(ws), ws.numel() * 8, m, cin, cout,
                                                  _stream()), "pdsc_pointwise_train_backward")
     return dx, dw, db, dgamma, dbeta
+
+
+LINEAR_TRAIN_COUT = 128
+HEAD_HIDDEN = 32
+
+
+def linear_train_shape_ok(cin: int, cout: int) -> bool:
+    """(Cin, Cout) of pdsc_linear_train_*: (1 .. 16, 128) layer0, (64, 128) fc_message.6."""
+    return cout == LINEAR_TRAIN_COUT and (1 <= cin <= 16 or cin == 64)
+
+
+def _train_workspace(nbytes: int, device) -> torch.Tensor:
+    return torch.empty(max((int(nbytes) + 7) // 8, 1), device=device, dtype=torch.float64)
+
+
+def _linear_train_dims(x: torch.Tensor, weight: torch.Tensor, what: str) -> Tuple[int, int, int]:
+    if x.dim() != 2 or weight.dim() != 2 or weight.shape[1] != x.shape[1]:
+        raise ValueError(f"{what}: x must be [M,Cin] and weight [Cout,Cin], got {tuple(x.shape)} {tuple(weight.shape)}")
+    m, cin, cout = x.shape[0], x.shape[1], weight.shape[0]
+    if not linear_train_shape_ok(cin, cout):
+        raise ValueError(f"{what}: (Cin, Cout) = ({cin}, {cout}); supported: (1..16, 128), (64, 128)")
+    if m < 1:
+        raise ValueError(f"{what}: M = {m} rows")
+    return m, cin, cout
+
+
+def _out(want: bool, device, *shape):
+    return torch.empty(*shape, device=device, dtype=torch.float32) if want else None
+
+
+@_on_device
+def linear_train_forward(x, weight, bias, residual=None):
+    """y = x weight^T + bias (+ residual) on rows (pdsc_linear_train_forward): x [M,Cin], weight [128,Cin], bias [128],
+    residual [M,128] or None -> y [M,128]."""
+    lib = _lib.load()
+    x, weight, bias = _chk(x, "x"), _chk(weight, "weight"), _chk(bias, "bias")
+    m, cin, cout = _linear_train_dims(x, weight, "linear_train_forward")
+    if bias.shape != (cout,):
+        raise ValueError(f"linear_train_forward: bias must be [{cout}], got {tuple(bias.shape)}")
+    if residual is not None:
+        residual = _chk(residual, "residual")
+        if residual.shape != (m, cout):
+            raise ValueError(f"linear_train_forward: residual must be [{m},{cout}], got {tuple(residual.shape)}")
+    y = torch.empty(m, cout, device=x.device, dtype=torch.float32)
+    _lib.check(lib.pdsc_linear_train_forward(_p(x), _p(weight), _p(bias), _p(residual), _p(y), m, cin, cout, _stream()),
+               "pdsc_linear_train_forward")
+    return y
+
+
+@_on_device
+def linear_train_backward(x, weight, dy, want_dx: bool = True, want_dw: bool = True, want_db: bool = True):
+    """Backward of linear_train_forward (pdsc_linear_train_backward): dy [M,128] -> (dx [M,Cin], dw [128,Cin], db [128]); None where
+    not wanted.  The residual's gradient is dy itself."""
+    if not (want_dx or want_dw or want_db):
+        raise ValueError("linear_train_backward: ask for at least one gradient")
+    lib = _lib.load()
+    x, weight, dy = _chk(x, "x"), _chk(weight, "weight"), _chk(dy, "dy")
+    m, cin, cout = _linear_train_dims(x, weight, "linear_train_backward")
+    if dy.shape != (m, cout):
+        raise ValueError(f"linear_train_backward: dy must be [{m},{cout}], got {tuple(dy.shape)}")
+    dx, dw, db = _out(want_dx, x.device, m, cin), _out(want_dw, x.device, cout, cin), _out(want_db, x.device, cout)
+    ws = _train_workspace(lib.pdsc_linear_train_workspace_bytes(m, cin, cout), x.device)
+    _lib.check(lib.pdsc_linear_train_backward(_p(x), _p(weight), _p(dy), _p(dx), _p(dw), _p(db), _p(ws), ws.numel() * 8, m, cin, cout,
+                                              _stream()), "pdsc_linear_train_backward")
+    return dx, dw, db
+
+
+def _qkv_train_dims(x, weights, what: str) -> int:
+    c = LINEAR_TRAIN_COUT
+    if x.dim() != 2 or x.shape[1] != c or x.shape[0] < 1:
+        raise ValueError(f"{what}: x must be [M,{c}] with M >= 1, got {tuple(x.shape)}")
+    for w in weights:
+        if w.shape != (c, c):
+            raise ValueError(f"{what}: the three weights must be [{c},{c}], got {tuple(w.shape)}")
+    return x.shape[0]
+
+
+@_on_device
+def qkv_train_forward(x, wq, bq, wk, bk, wv, bv, q_scale: float):
+    """qkv [M,384] = (q_scale (x wq^T + bq) | x wk^T + bk | x wv^T + bv) in one launch (pdsc_qkv_train_forward): the rows
+    sc_attention_lse takes; x [M,128], weights [128,128], biases [128]."""
+    lib = _lib.load()
+    x = _chk(x, "x")
+    wq, wk, wv = _chk(wq, "wq"), _chk(wk, "wk"), _chk(wv, "wv")
+    bq, bk, bv = _chk(bq, "bq"), _chk(bk, "bk"), _chk(bv, "bv")
+    m = _qkv_train_dims(x, (wq, wk, wv), "qkv_train_forward")
+    for b in (bq, bk, bv):
+        if b.shape != (LINEAR_TRAIN_COUT,):
+            raise ValueError(f"qkv_train_forward: the three biases must be [{LINEAR_TRAIN_COUT}], got {tuple(b.shape)}")
+    qkv = torch.empty(m, 3 * LINEAR_TRAIN_COUT, device=x.device, dtype=torch.float32)
+    _lib.check(lib.pdsc_qkv_train_forward(_p(x), _p(wq), _p(bq), _p(wk), _p(bk), _p(wv), _p(bv), float(q_scale), _p(qkv), m, _stream()),
+               "pdsc_qkv_train_forward")
+    return qkv
+
+
+@_on_device
+def qkv_train_backward(x, wq, wk, wv, q_scale: float, dqkv, want=(True,) * 7):
+    """Backward of qkv_train_forward (pdsc_qkv_train_backward): dqkv [M,384] -> (dx [M,128], dwq, dbq, dwk, dbk, dwv, dbv) of the
+    UN-scaled parameters; `want`: seven flags in that order, None where not wanted."""
+    want = tuple(bool(w) for w in want)
+    if len(want) != 7 or not any(want):
+        raise ValueError("qkv_train_backward: `want` takes seven flags, at least one of them set")
+    lib = _lib.load()
+    x, dqkv = _chk(x, "x"), _chk(dqkv, "dqkv")
+    wq, wk, wv = _chk(wq, "wq"), _chk(wk, "wk"), _chk(wv, "wv")
+    m = _qkv_train_dims(x, (wq, wk, wv), "qkv_train_backward")
+    c = LINEAR_TRAIN_COUT
+    if dqkv.shape != (m, 3 * c):
+        raise ValueError(f"qkv_train_backward: dqkv must be [{m},{3 * c}], got {tuple(dqkv.shape)}")
+    shapes = ((m, c), (c, c), (c,), (c, c), (c,), (c, c), (c,))
+    outs = [_out(w, x.device, *s) for w, s in zip(want, shapes)]
+    ws = _train_workspace(lib.pdsc_qkv_train_workspace_bytes(m), x.device)
+    _lib.check(lib.pdsc_qkv_train_backward(_p(x), _p(wq), _p(wk), _p(wv), float(q_scale), _p(dqkv), *(_p(o) for o in outs), _p(ws),
+                                           ws.numel() * 8, m, _stream()), "pdsc_qkv_train_backward")
+    return tuple(outs)
+
+
+def _head_train_dims(x, w0, b0, w1, b1, w2, what: str) -> int:
+    c, hd = LINEAR_TRAIN_COUT, HEAD_HIDDEN
+    if x.dim() != 2 or x.shape[1] != c or x.shape[0] < 1:
+        raise ValueError(f"{what}: feat must be [M,{c}] with M >= 1, got {tuple(x.shape)}")
+    for t, shape, name in ((w0, (hd, c), "w0"), (b0, (hd,), "b0"), (w1, (hd, hd), "w1"), (b1, (hd,), "b1"), (w2, (1, hd), "w2")):
+        if t.shape != shape:
+            raise ValueError(f"{what}: {name} must be {list(shape)}, got {tuple(t.shape)}")
+    return x.shape[0]
+
+
+@_on_device
+def head_train_forward(x, w0, b0, w1, b1, w2, b2, want_pre: bool = False):
+    """logits [M] = relu(relu(x w0^T + b0) w1^T + b1) . w2 + b2 in one launch (pdsc_head_train_forward): x [M,128], w0 [32,128],
+    w1 [32,32], w2 [1,32], b0, b1 [32], b2 [1].  want_pre: -> (logits, pre [M,64]), the kernel's two pre-activations side by side
+    (what its ReLU masks, and the backward's, are taken from); the training path does not ask for them."""
+    lib = _lib.load()
+    x, w0, b0, w1, b1, w2, b2 = (_chk(t, n) for t, n in ((x, "feat"), (w0, "w0"), (b0, "b0"), (w1, "w1"), (b1, "b1"), (w2, "w2"),
+                                                         (b2, "b2")))
+    m = _head_train_dims(x, w0, b0, w1, b1, w2, "head_train_forward")
+    if b2.shape != (1,):
+        raise ValueError(f"head_train_forward: b2 must be [1], got {tuple(b2.shape)}")
+    logits = torch.empty(m, device=x.device, dtype=torch.float32)
+    pre = _out(want_pre, x.device, m, 2 * HEAD_HIDDEN)
+    _lib.check(lib.pdsc_head_train_forward(_p(x), _p(w0), _p(b0), _p(w1), _p(b1), _p(w2), _p(b2), _p(logits), _p(pre), m, _stream()),
+               "pdsc_head_train_forward")
+    return (logits, pre) if want_pre else logits
+
+
+@_on_device
+def head_train_backward(x, w0, b0, w1, b1, w2, dlogits, want=(True,) * 7):
+    """Backward of head_train_forward (pdsc_head_train_backward): dlogits [M] -> (dfeat [M,128], dw0, db0, dw1, db1, dw2, db2);
+    `want`: seven flags in that order, None where not wanted.  The hidden layers are recomputed, nothing of the forward is kept."""
+    want = tuple(bool(w) for w in want)
+    if len(want) != 7 or not any(want):
+        raise ValueError("head_train_backward: `want` takes seven flags, at least one of them set")
+    lib = _lib.load()
+    x, w0, b0, w1, b1, w2, dlogits = (_chk(t, n) for t, n in ((x, "feat"), (w0, "w0"), (b0, "b0"), (w1, "w1"), (b1, "b1"), (w2, "w2"),
+                                                              (dlogits, "dlogits")))
+    m = _head_train_dims(x, w0, b0, w1, b1, w2, "head_train_backward")
+    if dlogits.shape != (m,):
+        raise ValueError(f"head_train_backward: dlogits must be [{m}], got {tuple(dlogits.shape)}")
+    c, hd = LINEAR_TRAIN_COUT, HEAD_HIDDEN
+    shapes = ((m, c), (hd, c), (hd,), (hd, hd), (hd,), (1, hd), (1,))
+    outs = [_out(w, x.device, *s) for w, s in zip(want, shapes)]
+    ws = _train_workspace(lib.pdsc_head_train_workspace_bytes(m), x.device)
+    _lib.check(lib.pdsc_head_train_backward(_p(x), _p(w0), _p(b0), _p(w1), _p(b1), _p(w2), _p(dlogits), *(_p(o) for o in outs), _p(ws),
+                                            ws.numel() * 8, m, _stream()), "pdsc_head_train_backward")
+    return tuple(outs)

@@ -6,7 +6,10 @@ per layer) and the feature-similarity matrix M (its gradient for an arbitrary dM
 mask).  ``sc_attention`` is a ``torch.autograd.Function`` over ``ops.sc_attention_lse`` / ``ops.sc_attention_backward``;
 ``feature_similarity`` one over ``ops.feature_compat`` / ``ops.feature_compat_backward``; (f-14) ``seed_solve`` one over the per-seed
 solver (``ops.seed_power_iteration`` + ``ops.seed_transforms`` / ``ops.seed_solve_backward``), which gives ``final_trans`` a
-gradient.  The 1x1 convolutions, batch-norms and ReLUs around them are torch's by default; (f-15) ``conv_bn_relu`` is the fused
+gradient.  The 1x1 convolutions, batch-norms and ReLUs around them are torch's by default; (f-16) ``linear_rows``,
+``qkv_projection`` and ``classification_head`` are the plain linears of the train path (layer0, fc_message.6 with its residual,
+the three projections in one launch, the head in one launch) over ``ops.linear_train_*`` / ``ops.qkv_train_*`` /
+``ops.head_train_*``, which ``TrainablePointDSC(fused_linears=True)`` uses; (f-15) ``conv_bn_relu`` is the fused
 train-mode Conv1d(k=1) + BatchNorm1d + ReLU over ``ops.pointwise_train_forward`` / ``ops.pointwise_train_backward``, which
 ``TrainablePointDSC(fused_layers=True)`` uses for the blocks' three such groups.  ``NonLocalBlock`` is the reference block
 (models/PointDSC.py:9-45) for a trainer that swaps layer by layer; ``train_forward`` is the reference's whole forward without the
@@ -297,6 +300,138 @@ def conv_bn_relu(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, bn_w
     return z
 
 
+# ---------------------------------------------------------------------------------------------------------------------------
+# f-16: the train path's plain linears
+# ---------------------------------------------------------------------------------------------------------------------------
+def _weight2d(weight: torch.Tensor) -> torch.Tensor:
+    """A Conv1d(k=1)'s [Cout,Cin,1] as [Cout,Cin] (a view: autograd hands the gradient back in the module's shape)."""
+    return weight[:, :, 0] if weight.dim() == 3 and weight.shape[2] == 1 else weight
+
+
+class _LinearRows(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, bias, residual):
+        ctx.save_for_backward(x, weight)
+        return ops.linear_train_forward(x, weight, bias, residual)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        x, weight = ctx.saved_tensors
+        need_x, need_w, need_b, need_r = ctx.needs_input_grad
+        dy = dy.contiguous()
+        dx = dw = db = None
+        if need_x or need_w or need_b:
+            dx, dw, db = ops.linear_train_backward(x, weight, dy, need_x, need_w, need_b)
+        return dx, dw, db, (dy if need_r else None)
+
+
+def linear_rows(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, residual: torch.Tensor = None) -> torch.Tensor:
+    """x weight^T + bias (+ residual) on rows, one device launch forward and up to three backward (a Conv1d(k=1) without a
+    batch-norm: the encoder's layer0, and fc_message.6 with the block's ``feat + message``, models/PointDSC.py:45,68), with
+    gradients for x, weight, bias and the residual; only those that require grad are computed.
+    x [M,Cin] fp32, weight [128,Cin] or the Conv1d's [128,Cin,1], bias [128], residual [M,128] or None; Cin in 1 .. 16 or 64;
+    M >= 1 -> [M,128]."""
+    tensors = [(x, "x"), (weight, "weight"), (bias, "bias")] + ([(residual, "residual")] if residual is not None else [])
+    for t, name in tensors:
+        if t.dtype != torch.float32:
+            raise TypeError(f"{name} must be torch.float32, got {t.dtype}")
+    weight = _weight2d(weight)
+    if x.dim() != 2 or weight.dim() != 2 or weight.shape[1] != x.shape[1]:
+        raise ValueError(f"linear_rows: x must be [M,Cin] and weight [Cout,Cin] or [Cout,Cin,1], got {tuple(x.shape)} {tuple(weight.shape)}")
+    m, cin, cout = x.shape[0], x.shape[1], weight.shape[0]
+    if not ops.linear_train_shape_ok(cin, cout):
+        raise ValueError(f"linear_rows: (Cin, Cout) = ({cin}, {cout}); supported: (1..16, 128), (64, 128)")
+    if m < 1:
+        raise ValueError(f"linear_rows: M = {m} rows")
+    if bias.shape != (cout,):
+        raise ValueError(f"linear_rows: bias must be [{cout}], got {tuple(bias.shape)}")
+    if residual is not None and residual.shape != (m, cout):
+        raise ValueError(f"linear_rows: residual must be [{m},{cout}], got {tuple(residual.shape)}")
+    for t, name in tensors:
+        if not t.is_cuda:
+            raise RuntimeError(f"{name} must live on the GPU (pointdsc_amd has no CPU path)")
+    return _LinearRows.apply(x.contiguous(), weight.contiguous(), bias, None if residual is None else residual.contiguous())
+
+
+class _QkvProjection(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, wq, bq, wk, bk, wv, bv):
+        ctx.save_for_backward(x, wq, wk, wv)
+        return ops.qkv_train_forward(x, wq, bq, wk, bk, wv, bv, Q_SCALE)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dqkv):
+        x, wq, wk, wv = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        if not any(need):
+            return (None,) * 7
+        return ops.qkv_train_backward(x, wq, wk, wv, Q_SCALE, dqkv.contiguous(), need)
+
+
+def qkv_projection(x: torch.Tensor, wq: torch.Tensor, bq: torch.Tensor, wk: torch.Tensor, bk: torch.Tensor, wv: torch.Tensor,
+                   bv: torch.Tensor) -> torch.Tensor:
+    """The block's three projections in one launch (models/PointDSC.py:36-38): (Q_SCALE (x wq^T + bq) | x wk^T + bk | x wv^T + bv)
+    as rows [M,384], the layout the attention takes, with gradients for x and the six UN-scaled parameters; no concatenated
+    weight is built.  x [M,128] fp32, weights [128,128] or the Conv1d's [128,128,1], biases [128]."""
+    tensors = ((x, "x"), (wq, "wq"), (bq, "bq"), (wk, "wk"), (bk, "bk"), (wv, "wv"), (bv, "bv"))
+    for t, name in tensors:
+        if t.dtype != torch.float32:
+            raise TypeError(f"{name} must be torch.float32, got {t.dtype}")
+    wq, wk, wv = _weight2d(wq), _weight2d(wk), _weight2d(wv)
+    if x.dim() != 2 or x.shape[1] != CHANNELS or x.shape[0] < 1:
+        raise ValueError(f"qkv_projection: x must be [M,{CHANNELS}] with M >= 1, got {tuple(x.shape)}")
+    for t, name in ((wq, "wq"), (wk, "wk"), (wv, "wv")):
+        if t.shape != (CHANNELS, CHANNELS):
+            raise ValueError(f"qkv_projection: {name} must be [{CHANNELS},{CHANNELS}] or [{CHANNELS},{CHANNELS},1], got {tuple(t.shape)}")
+    for t, name in ((bq, "bq"), (bk, "bk"), (bv, "bv")):
+        if t.shape != (CHANNELS,):
+            raise ValueError(f"qkv_projection: {name} must be [{CHANNELS}], got {tuple(t.shape)}")
+    for t, name in tensors:
+        if not t.is_cuda:
+            raise RuntimeError(f"{name} must live on the GPU (pointdsc_amd has no CPU path)")
+    return _QkvProjection.apply(x.contiguous(), wq.contiguous(), bq, wk.contiguous(), bk, wv.contiguous(), bv)
+
+
+class _ClassificationHead(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, feat, w0, b0, w1, b1, w2, b2):
+        ctx.save_for_backward(feat, w0, b0, w1, b1, w2)          # no hidden layer and no mask is kept: the backward recomputes both
+        return ops.head_train_forward(feat, w0, b0, w1, b1, w2, b2)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dlogits):
+        need = ctx.needs_input_grad
+        if not any(need):
+            return (None,) * 7
+        return ops.head_train_backward(*ctx.saved_tensors, dlogits.contiguous(), need)
+
+
+def classification_head(feat: torch.Tensor, w0: torch.Tensor, b0: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor, w2: torch.Tensor,
+                        b2: torch.Tensor) -> torch.Tensor:
+    """The classification head on rows (models/PointDSC.py:124-130,171): relu(relu(feat w0^T + b0) w1^T + b1) . w2 + b2 in one
+    launch, logits [M], with gradients for feat and the six parameters.  feat [M,128] fp32, w0 [32,128], w1 [32,32], w2 [1,32] (or
+    the Conv1d's three-dimensional weights), b0, b1 [32], b2 [1]."""
+    tensors = ((feat, "feat"), (w0, "w0"), (b0, "b0"), (w1, "w1"), (b1, "b1"), (w2, "w2"), (b2, "b2"))
+    for t, name in tensors:
+        if t.dtype != torch.float32:
+            raise TypeError(f"{name} must be torch.float32, got {t.dtype}")
+    w0, w1, w2 = _weight2d(w0), _weight2d(w1), _weight2d(w2)
+    hd = ops.HEAD_HIDDEN
+    if feat.dim() != 2 or feat.shape[1] != CHANNELS or feat.shape[0] < 1:
+        raise ValueError(f"classification_head: feat must be [M,{CHANNELS}] with M >= 1, got {tuple(feat.shape)}")
+    for t, shape, name in ((w0, (hd, CHANNELS), "w0"), (b0, (hd,), "b0"), (w1, (hd, hd), "w1"), (b1, (hd,), "b1"), (w2, (1, hd), "w2"),
+                           (b2, (1,), "b2")):
+        if t.shape != shape:
+            raise ValueError(f"classification_head: {name} must be {list(shape)}, got {tuple(t.shape)}")
+    for t, name in tensors:
+        if not t.is_cuda:
+            raise RuntimeError(f"{name} must live on the GPU (pointdsc_amd has no CPU path)")
+    return _ClassificationHead.apply(feat.contiguous(), w0.contiguous(), b0, w1.contiguous(), b1, w2.contiguous(), b2)
+
+
 def _conv_rows(conv: nn.Conv1d, x: torch.Tensor) -> torch.Tensor:
     """A 1x1 Conv1d on channel-last rows [M, Cin] -> [M, Cout]."""
     return F.linear(x, conv.weight[:, :, 0], conv.bias)
@@ -313,27 +448,60 @@ def _conv_bn_relu_rows(conv: nn.Conv1d, bn: nn.BatchNorm1d, x: torch.Tensor, fus
     return conv_bn_relu(x, conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.momentum, bn.eps)
 
 
-def _train_encoder(enc, x: torch.Tensor, compat: torch.Tensor, bs: int, n: int, fused_layers: bool = False) -> torch.Tensor:
+def _linear_rows_fusable(conv: nn.Conv1d) -> bool:
+    """A convolution the device linears take: it has a bias and its (Cin, Cout) is one of ``linear_rows``'."""
+    return conv.bias is not None and ops.linear_train_shape_ok(conv.in_channels, conv.out_channels)
+
+
+def _qkv_rows(nl, feat: torch.Tensor, fused: bool) -> torch.Tensor:
+    """The block's q | k | v rows [M,384], q pre-scaled.  fused: ``qkv_projection`` on the three modules' own parameters; torch's
+    path (one F.linear on concatenated weights) otherwise, and when a projection has no bias."""
+    q, k, v = nl.projection_q, nl.projection_k, nl.projection_v
+    if fused and q.bias is not None and k.bias is not None and v.bias is not None:
+        return qkv_projection(feat, q.weight, q.bias, k.weight, k.bias, v.weight, v.bias)
+    w = torch.cat((q.weight[:, :, 0] * Q_SCALE, k.weight[:, :, 0], v.weight[:, :, 0]))
+    b = torch.cat((q.bias * Q_SCALE, k.bias, v.bias))
+    return F.linear(feat, w, b)
+
+
+def _head_rows(cls, feat: torch.Tensor, fused: bool) -> torch.Tensor:
+    """The classification head's logits [M].  fused: ``classification_head``; torch's three F.linear otherwise, and when one of
+    its convolutions has no bias."""
+    if fused and all(cls[i].bias is not None for i in (0, 2, 4)):
+        return classification_head(feat, cls[0].weight, cls[0].bias, cls[2].weight, cls[2].bias, cls[4].weight, cls[4].bias)
+    return _conv_rows(cls[4], F.relu(_conv_rows(cls[2], F.relu(_conv_rows(cls[0], feat))))).reshape(-1)
+
+
+def _train_encoder(enc, x: torch.Tensor, compat: torch.Tensor, bs: int, n: int, fused_layers: bool = False,
+                   fused_linears: bool = False) -> torch.Tensor:
     """NonLocalNet.forward (models/PointDSC.py:65-77) on rows [bs*N, C].  The batch-norms are the modules' own forward on (M, C)
     rows (BatchNorm1d takes that layout: the statistics run over the bs * N rows exactly as over [bs, C, N]): F.batch_norm on
     the module's buffers with batch statistics, running_mean / running_var / num_batches_tracked updated by torch itself.
     fused_layers: the three conv + batch-norm + ReLU groups of every block run through ``conv_bn_relu`` instead (f-15); layer0,
-    the q|k|v projection, fc_message.6 with its residual stay torch's."""
-    feat = _conv_rows(enc.layer0, x)
+    the q|k|v projection, fc_message.6 with its residual stay torch's unless
+    fused_linears (f-16): layer0 and fc_message.6 + residual run through ``linear_rows``, the projection through
+    ``qkv_projection`` (no cat of weights).  A convolution without a bias, or a layer0 whose in_dim is outside 1 .. 16, keeps
+    torch's path."""
+    if fused_linears and _linear_rows_fusable(enc.layer0):
+        feat = linear_rows(x, enc.layer0.weight, enc.layer0.bias)
+    else:
+        feat = _conv_rows(enc.layer0, x)
     for i in range(enc.num_layers):
         pcn, nl = enc.blocks[f"PointCN_layer_{i}"], enc.blocks[f"NonLocal_layer_{i}"]
         feat = _conv_bn_relu_rows(pcn[0], pcn[1], feat, fused_layers)
-        w = torch.cat((nl.projection_q.weight[:, :, 0] * Q_SCALE, nl.projection_k.weight[:, :, 0], nl.projection_v.weight[:, :, 0]))
-        b = torch.cat((nl.projection_q.bias * Q_SCALE, nl.projection_k.bias, nl.projection_v.bias))
-        msg = _SCAttentionRows.apply(F.linear(feat, w, b), compat, bs, n)
+        msg = _SCAttentionRows.apply(_qkv_rows(nl, feat, fused_linears), compat, bs, n)
         fc = nl.fc_message
         h = _conv_bn_relu_rows(fc[0], fc[1], msg, fused_layers)
         h = _conv_bn_relu_rows(fc[3], fc[4], h, fused_layers)
-        feat = feat + _conv_rows(fc[6], h)
+        if fused_linears and _linear_rows_fusable(fc[6]):
+            feat = linear_rows(h, fc[6].weight, fc[6].bias, feat)
+        else:
+            feat = feat + _conv_rows(fc[6], h)
     return feat
 
 
-def train_forward(model: PointDSC, data, differentiable_trans: bool = False, fused_layers: bool = False) -> dict:
+def train_forward(model: PointDSC, data, differentiable_trans: bool = False, fused_layers: bool = False, *,
+                  fused_linears: bool = False) -> dict:
     """The reference's forward without the 'testing' key (models/PointDSC.py:143-197) in train() mode, on `model`'s own Parameters
     and buffers: batch-statistics batch-norm (running statistics updated as torch's BatchNorm1d does), autograd through the
     encoder, the classification head and M.  data: corr_pos [bs,N,in_dim], src_keypts, tgt_keypts [bs,N,3] on the GPU.
@@ -343,7 +511,10 @@ def train_forward(model: PointDSC, data, differentiable_trans: bool = False, fus
     gradient and nothing is kept for one.  True: they run behind ``seed_solve`` and final_trans carries the gradient of the winning
     seed of each pair into the features and sigma (the reference's cal_seed_trans under autograd); the values are the same.
     fused_layers=True: every Conv1d + BatchNorm1d + ReLU group of the encoder's blocks runs as ``conv_bn_relu`` (device kernels,
-    forward and backward) instead of torch's F.linear / F.batch_norm / F.relu: the same function, other rounding."""
+    forward and backward) instead of torch's F.linear / F.batch_norm / F.relu: the same function, other rounding.
+    fused_linears=True (keyword only, independent of fused_layers): the remaining plain linears -- layer0, every block's q|k|v
+    projection and fc_message.6 with its residual, the classification head -- run as ``linear_rows``, ``qkv_projection`` and
+    ``classification_head`` (device kernels, forward and backward) instead of F.linear / cat / relu: likewise."""
     if not model.training:
         raise RuntimeError("train_forward needs the module in train() mode; in eval() mode call the module (PointDSC.forward)")
     if "testing" in data.keys():
@@ -365,10 +536,11 @@ def train_forward(model: PointDSC, data, differentiable_trans: bool = False, fus
     with torch.cuda.device(dev):
         with torch.no_grad():
             compat = _pad_compat(ops.spatial_compat(src, tgt, model.sigma_spat), n)
-        feat = _train_encoder(model.encoder, corr_pos.view(bs * n, model.in_dim), compat, bs, n, fused_layers=fused_layers)
+        feat = _train_encoder(model.encoder, corr_pos.view(bs * n, model.in_dim), compat, bs, n, fused_layers=fused_layers,
+                              fused_linears=fused_linears)
         normed = F.normalize(feat, p=2, dim=-1).view(bs, n, CHANNELS)
         cls = model.classification
-        logits = _conv_rows(cls[4], F.relu(_conv_rows(cls[2], F.relu(_conv_rows(cls[0], feat))))).view(bs, n)
+        logits = _head_rows(cls, feat, fused_linears).view(bs, n)
         M = feature_similarity(normed, model.sigma)
         with torch.no_grad():
             nd, sigma = normed.detach(), model.sigma.detach()
@@ -398,14 +570,18 @@ class TrainablePointDSC(PointDSC):
     libs/trainer.py:79-136, runs on it unchanged); in ``eval()`` mode it is ``PointDSC.forward``, which sees every optimiser step
     through the weights' version counters.  ``differentiable_trans=True`` (keyword only, not part of the reference's constructor):
     the train-mode ``final_trans`` carries a gradient (``train_forward``), what a transformation-loss weight above 0 needs.
-    ``fused_layers=True`` (keyword only, likewise): the blocks' conv + batch-norm + ReLU groups run as ``conv_bn_relu``."""
+    ``fused_layers=True`` (keyword only, likewise): the blocks' conv + batch-norm + ReLU groups run as ``conv_bn_relu``.
+    ``fused_linears=True`` (keyword only, likewise, independent of ``fused_layers``): layer0, the q|k|v projections, fc_message.6
+    with its residual and the classification head run as ``linear_rows``, ``qkv_projection`` and ``classification_head``."""
 
-    def __init__(self, *args, differentiable_trans: bool = False, fused_layers: bool = False, **kwargs):
+    def __init__(self, *args, differentiable_trans: bool = False, fused_layers: bool = False, fused_linears: bool = False, **kwargs):
         super().__init__(*args, **kwargs)
         self.differentiable_trans = bool(differentiable_trans)
         self.fused_layers = bool(fused_layers)
+        self.fused_linears = bool(fused_linears)
 
     def forward(self, data):
         if self.training:
-            return train_forward(self, data, differentiable_trans=self.differentiable_trans, fused_layers=self.fused_layers)
+            return train_forward(self, data, differentiable_trans=self.differentiable_trans, fused_layers=self.fused_layers,
+                                 fused_linears=self.fused_linears)
         return super().forward(data)

@@ -128,7 +128,8 @@ def train(a):
     """--train: a few optimiser steps of harness.train_epoch on the synthetic batches --validate uses; the validation meters of
     the same batches before and after."""
     from pointdsc_amd import TrainablePointDSC, synthetic
-    model = TrainablePointDSC(**dict(workloads.BASE_MODEL), differentiable_trans=a.weight_transformation > 0, fused_layers=a.fused_layers)
+    model = TrainablePointDSC(**dict(workloads.BASE_MODEL), differentiable_trans=a.weight_transformation > 0, fused_layers=a.fused_layers,
+                              fused_linears=a.fused_linears)
     if a.snapshot:
         print(model.load_state_dict(torch.load(a.snapshot, map_location="cpu"), strict=False))
     else:
@@ -187,6 +188,9 @@ def main():
                     "loss in the objective; above 0 the model is built with differentiable_trans=True")
     ap.add_argument("--fused-layers", action="store_true", help="with --train: the blocks' conv + batch-norm + ReLU groups as device kernels "
                     "(TrainablePointDSC(fused_layers=True), pointdsc_amd.conv_bn_relu)")
+    ap.add_argument("--fused-linears", action="store_true", help="with --train: layer0, the q|k|v projections, fc_message.6 with its residual "
+                    "and the classification head as device kernels (TrainablePointDSC(fused_linears=True): pointdsc_amd.linear_rows, "
+                    "qkv_projection, classification_head)")
     ap.add_argument("--json", action="store_true")
     a = ap.parse_args()
     if a.train:

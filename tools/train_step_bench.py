@@ -14,6 +14,9 @@ These are CALL times, host work included.
 
     --fused-layers       (f-15) the whole step of TrainablePointDSC(fused_layers=True) next to the default model's instead (same
                          weights, same batch, same method); with --profile-steps the profiled model is the fused one
+    --fused-linears      (f-16) the whole step of TrainablePointDSC(fused_layers=True, fused_linears=True) next to
+                         TrainablePointDSC(fused_layers=True) -- the step as it was before the flag existed -- likewise; with
+                         --profile-steps the profiled model has both flags set
     --profile-steps K    run K device steps and exit: the program of the one `rocprofv3 --kernel-trace --stats` run
     --breakdown FILE     group the per-kernel table tools/rocpd_kernel_stats.py made of that run into the step's six parts"""
 import argparse
@@ -31,6 +34,7 @@ GROUPS = [      # first match wins
     ("attention backward", r"att_bwd_"),
     ("M forward + backward", r"gram_rows_kernel<2|feature_compat_backward"),
     ("losses", r"pdsc::(cls_|sm_loss_|trans_partial|trans_finish)"),
+    ("plain linears (layer0, q|k|v, fc_message.6, head)", r"pdsc::lth?_"),
     ("fused point-wise layers (conv + BN + ReLU)", r"pdsc::pwt_"),
     ("tail and compat (the library's other kernels)", r"pdsc::"),
     ("torch (GEMMs, batch-norm, point-wise, optimiser)", r"."),
@@ -65,6 +69,7 @@ def main():
     ap.add_argument("--profile-steps", type=int, default=0)
     ap.add_argument("--breakdown", default=None)
     ap.add_argument("--fused-layers", action="store_true")
+    ap.add_argument("--fused-linears", action="store_true")
     a = ap.parse_args()
     if a.breakdown:
         return breakdown(a.breakdown)
@@ -94,8 +99,8 @@ def main():
     gt = batch["gt_labels"]
     cls_fn, sm_fn = ClassificationLoss(False), SpectralMatchingLoss(False)
 
-    def make_step(fused):
-        model = training.TrainablePointDSC(num_layers=a.layers, fused_layers=fused)
+    def make_step(fused, fused_linears=False):
+        model = training.TrainablePointDSC(num_layers=a.layers, fused_layers=fused, fused_linears=fused_linears)
         model.load_state_dict({k: v.clone() for k, v in state.items()}, strict=True)
         model = model.to(dev).train()
         opt = torch.optim.Adam(model.parameters(), lr=1e-4, weight_decay=1e-6)
@@ -108,7 +113,7 @@ def main():
             opt.step()
             return loss
         return step
-    device_step = make_step(a.fused_layers)
+    device_step = make_step(a.fused_layers or a.fused_linears, a.fused_linears)
 
     if a.profile_steps:
         for _ in range(a.profile_steps):
@@ -117,6 +122,16 @@ def main():
         return
 
     print(f"bs={bs} N={n} layers={a.layers}: microseconds per call, median of {a.rounds} windows of {a.window} s (min .. max)")
+    if a.fused_linears:
+        layers_step = make_step(True)
+        t_both, t_layers = [], []
+        for _ in range(a.rounds):                         # alternate the two models
+            t_both.append(timed(device_step, a.warmup, a.window)[0])
+            t_layers.append(timed(layers_step, a.warmup, a.window)[0])
+        mb, ml = statistics.median(t_both), statistics.median(t_layers)
+        print(f"  {'training step (forward, 2 losses, backward, Adam)':42s} fused_layers=True, fused_linears=True {spread(t_both)}   "
+              f"fused_layers=True {spread(t_layers)}   without / with fused_linears {ml / mb:6.2f}")
+        return
     if a.fused_layers:
         torch_layers_step = make_step(False)
         t_fused, t_plain = [], []
