@@ -6,10 +6,7 @@
 //   backward  g = dZ [Z > 0];  dbeta = sum g;  dgamma = sum g xh;  dY = gamma invstd (g - dbeta / M - xh dgamma / M);
 //             db = sum dY;  dW = dY^T X;  dX = dY W.
 //
-// All three products run on v_mfma_f32_32x32x2_f32 (exact fp32 products, one rounding per accumulate).  Operand convention of
-// linear.hip wherever a lane's four k values are contiguous in LDS: k-slot (step 4q+e, half h = lane>>5) <-> channel 8q+4h+e.
-//
-// Launch sequences (no atomics, no memset, nothing allocated; every sum has a fixed order, so repeat calls give the same bits):
+// The three products, the staging, the dW / db partials and their merge are train_tile.h's.  Launch sequences:
 //   forward   1. pwt_forward_gemm_kernel   one workgroup per 64-row tile: Y, and the tile's (mean, M2) per channel in fp64
 //             2. pwt_stats_merge_kernel    16 channels per workgroup: mean = sum n_t mean_t / M, M2 = sum M2_t + n_t (mean_t - mean)^2 in fp64
 //                                          (mean-centred throughout: no E[y^2] - E[y]^2), invstd, running statistics in place
@@ -19,16 +16,14 @@
 //             3. pwt_backward_gemm_kernel    persistent workgroups (at most one per compute unit) walk the tiles: dY rebuilt per
 //                                            tile in LDS, dX tile written, dW accumulated in registers over the workgroup's tiles;
 //                                            one [Cout][Cin] (+ db [Cout]) partial per workgroup
-//             4. pwt_merge_dw_kernel         the workgroups' partials in index order -> dW, db
+//             4. tt_merge_kernel             the workgroups' partials in index order -> dW, db
 // The ReLU mask of the backward is recomputed from Y with the forward's own expression (pwt_preact): the same bits as Z > 0,
 // and Z is not read again.
-#include "pdsc_common.h"
+#include "train_tile.h"
 
 namespace pdsc {
 
-constexpr int PWT_BM = 64;                 // rows per tile
-constexpr int PWT_MAX_GROUPS = 256;        // persistent workgroups of the backward: one per compute unit
-constexpr int PWT_MERGE_THREADS = 1024;
+constexpr int PWT_MERGE_THREADS = TT_MERGE_THREADS;
 constexpr int PWT_MERGE_COLS = 16;         // channels per workgroup of the two statistics merges (64 slices of tiles each)
 
 __device__ __forceinline__ float pwt_xhat(float y, float mean, float invstd) { return (y - mean) * invstd; }
@@ -38,15 +33,13 @@ __device__ __forceinline__ float pwt_preact(float xh, float gamma, float beta) {
 // from the forward to the backward in fp64; the forward's Z and the backward's mask use their fp32 roundings, both alike.
 __device__ __forceinline__ double pwt_xhat_f64(float y, double mean, double invstd) { return ((double)y - mean) * invstd; }
 
-static int pwt_tiles(int M) { return ceil_div(M, PWT_BM); }
-static int pwt_groups(int M) { const int t = pwt_tiles(M); return t < PWT_MAX_GROUPS ? t : PWT_MAX_GROUPS; }
 static bool pwt_shape_ok(int Cin, int Cout) { return (Cin == 128 && (Cout == 128 || Cout == 64)) || (Cin == 64 && Cout == 64); }
 
 // workspace: [tiles][2][Cout] fp64 (forward: mean_t, M2_t; backward: dbeta_t, dgamma_t) | [2][Cout] fp64 (dbeta / M, dgamma / M) |
 //            [groups][Cout * Cin + Cout] fp32 (dW, db partials)
-static size_t pwt_part_bytes(int M, int Cout) { return (size_t)pwt_tiles(M) * 2 * Cout * sizeof(double); }
+static size_t pwt_part_bytes(int M, int Cout) { return (size_t)tt_tiles(M) * 2 * Cout * sizeof(double); }
 static size_t pwt_sums_bytes(int Cout) { return (size_t)2 * Cout * sizeof(double); }
-static size_t pwt_dw_bytes(int M, int Cin, int Cout) { return (size_t)pwt_groups(M) * ((size_t)Cout * Cin + Cout) * sizeof(float); }
+static size_t pwt_dw_bytes(int M, int Cin, int Cout) { return (size_t)tt_groups(M) * ((size_t)Cout * Cin + Cout) * sizeof(float); }
 
 struct PwtFwdArgs {
     const float* X; const float* W; const float* b;
@@ -57,48 +50,24 @@ struct PwtFwdArgs {
 // ---- forward 1: Y tile on the matrix cores, the tile's mean and M2 per channel -------------------------------------------
 template <int CIN, int COUT>
 __global__ __launch_bounds__(256) void pwt_forward_gemm_kernel(PwtFwdArgs a) {
-    constexpr int KP = CIN + 4, K4 = CIN / 4, NT = COUT / 64, LDY = COUT + 1;
+    constexpr int KP = CIN + TT_PAD, NT = COUT / 64, LDY = COUT + 1;
     static_assert(LDY <= KP, "the Y tile reuses the X stage");
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float* Xs = lds;                       // [64][KP], then the Y tile [64][LDY]
-    float* Ws = lds + PWT_BM * KP;         // [COUT][KP]
+    float* Ws = lds + TT_BM * KP;         // [COUT][KP]
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int m0 = blockIdx.x * PWT_BM;
-    const int nrows = min(PWT_BM, a.M - m0);
+    const int m0 = blockIdx.x * TT_BM;
+    const int nrows = min(TT_BM, a.M - m0);
 
-    for (int idx = t; idx < PWT_BM * K4; idx += 256) {
-        const int row = idx / K4, c = idx - row * K4;
-        f32x4 v = {0.f, 0.f, 0.f, 0.f};
-        if (row < nrows) v = *reinterpret_cast<const f32x4*>(a.X + (size_t)(m0 + row) * CIN + c * 4);
-        *reinterpret_cast<f32x4*>(Xs + row * KP + c * 4) = v;
-    }
-    for (int idx = t; idx < COUT * K4; idx += 256) {
-        const int row = idx / K4, c = idx - row * K4;
-        *reinterpret_cast<f32x4*>(Ws + row * KP + c * 4) = *reinterpret_cast<const f32x4*>(a.W + (size_t)row * CIN + c * 4);
-    }
+    tt_stage_rows16<CIN>(a.X, m0, Xs, TT_BM, nrows);
+    tt_stage_rows16<CIN>(a.W, 0, Ws, COUT, COUT);
     __syncthreads();
 
     const int wm = wave & 1, wn = wave >> 1;
     const int l31 = lane & 31, h = lane >> 5;
     f32x16 acc[NT];
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[nt][r] = 0.f;
-    const float* xa = Xs + (wm * 32 + l31) * KP + 4 * h;
-    const float* wb = Ws + ((wn * NT) * 32 + l31) * KP + 4 * h;
-#pragma unroll 4
-    for (int q = 0; q < CIN / 8; ++q) {
-        const f32x4 av = *reinterpret_cast<const f32x4*>(xa + 8 * q);
-        f32x4 bv[NT];
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) bv[nt] = *reinterpret_cast<const f32x4*>(wb + nt * 32 * KP + 8 * q);
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt)
-                acc[nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[e], bv[nt][e], acc[nt], 0, 0, 0);
-    }
+    tt_zero(acc);
+    tt_mma_rows_rows<CIN, NT, 4>(Xs + wm * 32 * KP, KP, Ws + wn * NT * 32 * KP, KP, acc);
     __syncthreads();                       // every wave has read its X rows: the stage becomes the Y tile
 
     float* Ys = Xs;
@@ -108,7 +77,7 @@ __global__ __launch_bounds__(256) void pwt_forward_gemm_kernel(PwtFwdArgs a) {
         const float bval = a.b[n];
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int i = wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+            const int i = wm * 32 + tt_acc_row(r, h);
             const float v = acc[nt][r] + bval;
             Ys[i * LDY + n] = v;
             if (i < nrows) a.Y[(size_t)(m0 + i) * COUT + n] = v;
@@ -143,7 +112,7 @@ __global__ __launch_bounds__(PWT_MERGE_THREADS) void pwt_stats_merge_kernel(cons
     const int t = threadIdx.x, cl = t % PWT_MERGE_COLS, s = t / PWT_MERGE_COLS, c = blockIdx.x * PWT_MERGE_COLS + cl;
     double acc = 0.0;
     for (int tile = s; tile < tiles; tile += S) {
-        const double n = (double)min(PWT_BM, M - tile * PWT_BM);
+        const double n = (double)min(TT_BM, M - tile * TT_BM);
         acc = fma(n, part[((size_t)tile * 2) * Cout + c], acc);
     }
     red[t] = acc;
@@ -155,7 +124,7 @@ __global__ __launch_bounds__(PWT_MERGE_THREADS) void pwt_stats_merge_kernel(cons
     __syncthreads();
     acc = 0.0;
     for (int tile = s; tile < tiles; tile += S) {
-        const double n = (double)min(PWT_BM, M - tile * PWT_BM);
+        const double n = (double)min(TT_BM, M - tile * TT_BM);
         const double d = part[((size_t)tile * 2) * Cout + c] - mean;
         acc += part[((size_t)tile * 2 + 1) * Cout + c] + n * d * d;
     }
@@ -201,8 +170,8 @@ __global__ __launch_bounds__(256) void pwt_backward_reduce_kernel(const float* _
     constexpr int C4N = COUT / 4, RL = 256 / C4N;
     __shared__ double red[RL * 2 * COUT];
     const int t = threadIdx.x, c4 = (t % C4N) * 4, rl = t / C4N;
-    const int m0 = blockIdx.x * PWT_BM;
-    const int nrows = min(PWT_BM, M - m0);
+    const int m0 = blockIdx.x * TT_BM;
+    const int nrows = min(TT_BM, M - m0);
     float mu[4], is[4], ga[4], be[4];
     double mud[4], isd[4];
 #pragma unroll
@@ -270,16 +239,16 @@ struct PwtBwdArgs {
 // ---- backward 3: dY per tile, dX = dY W, dW += dY^T X, db += sum dY ---------------------------------------------------------
 template <int CIN, int COUT, bool DX, bool DW>
 __global__ __launch_bounds__(256) void pwt_backward_gemm_kernel(PwtBwdArgs a) {
-    constexpr int LDO = COUT + 4, LDI = CIN + 4, C4N = COUT / 4, RL = 256 / C4N, K4 = CIN / 4;
+    constexpr int LDO = COUT + TT_PAD, LDI = CIN + TT_PAD, C4N = COUT / 4, RL = 256 / C4N;
     constexpr int NTI = CIN / 64;                            // dX: 32-column blocks per wave
     constexpr int CIB = CIN / 32, TPW = (COUT / 32) * CIB / 4;   // dW: 32 x 32 blocks per wave
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float* dYs = lds;                                        // [64][LDO]
-    float* Xs = dYs + PWT_BM * LDO;                          // [64][LDI]    (DW)
-    float* Ws = Xs + (DW ? PWT_BM * LDI : 0);                // [COUT][LDI]  (DX)
+    float* Xs = dYs + TT_BM * LDO;                          // [64][LDI]    (DW)
+    float* Ws = Xs + (DW ? TT_BM * LDI : 0);                // [COUT][LDI]  (DX)
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6, l31 = lane & 31, h = lane >> 5;
     const int c4 = (t % C4N) * 4, rl = t / C4N;
-    const int tiles = ceil_div_dev(a.M, PWT_BM);
+    const int tiles = ceil_div_dev(a.M, TT_BM);
 
     float mu[4], is[4], ga[4], be[4], dbs[4];
     double mud[4], isd[4], k1[4], mb[4], mg[4];
@@ -292,24 +261,16 @@ __global__ __launch_bounds__(256) void pwt_backward_gemm_kernel(PwtBwdArgs a) {
         mg[e] = a.means[COUT + c4 + e];
         dbs[e] = 0.f;
     }
-    if (DX) {
-        for (int idx = t; idx < COUT * K4; idx += 256) {
-            const int row = idx / K4, c = idx - row * K4;
-            *reinterpret_cast<f32x4*>(Ws + row * LDI + c * 4) = *reinterpret_cast<const f32x4*>(a.W + (size_t)row * CIN + c * 4);
-        }
-    }
-    f32x16 accw[DW ? TPW : 1];
-#pragma unroll
-    for (int i = 0; i < (DW ? TPW : 1); ++i)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) accw[i][r] = 0.f;
+    if (DX) tt_stage_rows16<CIN>(a.W, 0, Ws, COUT, COUT);
+    f32x16 accw[TPW];
+    tt_zero(accw);
 
     for (int tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-        const int m0 = tile * PWT_BM;
-        const int nrows = min(PWT_BM, a.M - m0);
+        const int m0 = tile * TT_BM;
+        const int nrows = min(TT_BM, a.M - m0);
         __syncthreads();                                     // the previous tile's readers are done
 #pragma unroll
-        for (int i = 0; i < PWT_BM / RL; ++i) {
+        for (int i = 0; i < TT_BM / RL; ++i) {
             const int r = rl + RL * i;
             f32x4 dy = {0.f, 0.f, 0.f, 0.f};
             if (r < nrows) {
@@ -325,126 +286,48 @@ __global__ __launch_bounds__(256) void pwt_backward_gemm_kernel(PwtBwdArgs a) {
             }
             *reinterpret_cast<f32x4*>(dYs + r * LDO + c4) = dy;
         }
-        if (DW) {
-            for (int idx = t; idx < PWT_BM * K4; idx += 256) {
-                const int row = idx / K4, c = idx - row * K4;
-                f32x4 v = {0.f, 0.f, 0.f, 0.f};
-                if (row < nrows) v = *reinterpret_cast<const f32x4*>(a.X + (size_t)(m0 + row) * CIN + c * 4);
-                *reinterpret_cast<f32x4*>(Xs + row * LDI + c * 4) = v;
-            }
-        }
+        if (DW) tt_stage_rows16<CIN>(a.X, m0, Xs, TT_BM, nrows);
         __syncthreads();
 
         if (DX) {
-            // dX[m][ci] = sum_co dY[m][co] W[co][ci]: A = dY rows (one 16-byte read per four steps), B = W rows (k = co)
+            // dX[m][ci] = sum_co dY[m][co] W[co][ci]
             const int wm = wave & 1, wn = wave >> 1;
             f32x16 acc[NTI];
-#pragma unroll
-            for (int nt = 0; nt < NTI; ++nt)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[nt][r] = 0.f;
-            const float* ya = dYs + (wm * 32 + l31) * LDO + 4 * h;
-            const float* wb = Ws + (4 * h) * LDI + wn * NTI * 32 + l31;
-#pragma unroll 2
-            for (int q = 0; q < COUT / 8; ++q) {
-                const f32x4 av = *reinterpret_cast<const f32x4*>(ya + 8 * q);
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-#pragma unroll
-                    for (int nt = 0; nt < NTI; ++nt)
-                        acc[nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[e], wb[(8 * q + e) * LDI + nt * 32], acc[nt], 0, 0, 0);
-            }
+            tt_zero(acc);
+            tt_mma_rows_cols<COUT, NTI, 2>(dYs + wm * 32 * LDO, LDO, Ws + wn * NTI * 32, LDI, acc);
 #pragma unroll
             for (int nt = 0; nt < NTI; ++nt) {
                 const int n = (wn * NTI + nt) * 32 + l31;
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int i = wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+                    const int i = wm * 32 + tt_acc_row(r, h);
                     if (i < nrows) a.dX[(size_t)(m0 + i) * CIN + n] = acc[nt][r];
                 }
             }
         }
-        if (DW) {
-            // dW[co][ci] += sum_rows dY[row][co] X[row][ci]: k = row 2 step + h, both operands one 4-byte read per step
-#pragma unroll 4
-            for (int st = 0; st < PWT_BM / 2; ++st) {
-                const float* yr = dYs + (2 * st + h) * LDO + l31;
-                const float* xr = Xs + (2 * st + h) * LDI + l31;
-#pragma unroll
-                for (int i = 0; i < TPW; ++i) {
-                    const int j = wave * TPW + i;            // block (co, ci) = (j / CIB, j % CIB)
-                    accw[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(yr[(j / CIB) * 32], xr[(j % CIB) * 32], accw[i], 0, 0, 0);
-                }
-            }
-        }
+        // dW[co][ci] += sum_rows dY[row][co] X[row][ci]: block (co, ci) = (j / CIB, j % CIB)
+        if (DW) tt_mma_cols_cols<TT_BM, TPW, CIB, 4>(dYs, LDO, Xs, LDI, wave * TPW, accw);
     }
 
     if (DW) {
         float* P = a.dwpart + (size_t)blockIdx.x * (COUT * CIN + COUT);
-#pragma unroll
-        for (int i = 0; i < TPW; ++i) {
-            const int j = wave * TPW + i;
-            const int ci = (j % CIB) * 32 + l31;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int co = (j / CIB) * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-                P[(size_t)co * CIN + ci] = accw[i][r];
-            }
-        }
-        // db: the row lanes of a channel in order
-        __syncthreads();
-        float* red = dYs;                                    // [RL][COUT]
-#pragma unroll
-        for (int e = 0; e < 4; ++e) red[rl * COUT + c4 + e] = dbs[e];
-        __syncthreads();
-        if (t < COUT) {
-            float s = 0.f;
-#pragma unroll
-            for (int j = 0; j < RL; ++j) s += red[j * COUT + t];
-            P[COUT * CIN + t] = s;
-        }
-    }
-}
-
-// ---- backward 4: the workgroups' partials in index order -> dW, db; thread = (slice, element), 16 slices x 64 elements -----
-__global__ __launch_bounds__(PWT_MERGE_THREADS) void pwt_merge_dw_kernel(const float* __restrict__ part, int groups, int nw, int nb,
-                                                                        float* __restrict__ dW, float* __restrict__ db) {
-    __shared__ float red[PWT_MERGE_THREADS];
-    const int t = threadIdx.x, el = blockIdx.x * 64 + (t & 63), s = t >> 6;
-    const int total = nw + nb;
-    float acc = 0.f;
-    if (el < total)
-        for (int p = s; p < groups; p += 16) acc += part[(size_t)p * total + el];
-    red[t] = acc;
-    __syncthreads();
-    if (s == 0 && el < total) {
-        float tot = 0.f;
-#pragma unroll
-        for (int j = 0; j < 16; ++j) tot += red[j * 64 + (t & 63)];
-        if (el < nw) { if (dW) dW[el] = tot; }
-        else if (db) db[el - nw] = tot;
+        tt_write_dw_blocks<TPW, CIB>(P, CIN, CIN, wave * TPW, accw);
+        const float s = tt_column_sums<RL, COUT>(dYs, dbs, rl, c4, 1);      // db; the dY tile has no readers left
+        if (t < COUT) P[COUT * CIN + t] = s;
     }
 }
 
 template <int CIN, int COUT>
 static int pwt_launch_forward_gemm(const PwtFwdArgs& a, hipStream_t st) {
-    const size_t lds_bytes = (size_t)(PWT_BM + COUT) * (CIN + 4) * sizeof(float);
-    const int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(&pwt_forward_gemm_kernel<CIN, COUT>), lds_bytes,
-                                      "pdsc_pointwise_train_forward(dynamic LDS)");
-    if (rc != PDSC_OK) return rc;
-    hipLaunchKernelGGL((pwt_forward_gemm_kernel<CIN, COUT>), dim3(pwt_tiles(a.M)), dim3(256), lds_bytes, st, a);
-    return check_launch("pdsc_pointwise_train_forward");
+    return launch_with_dynamic_lds(pwt_forward_gemm_kernel<CIN, COUT>, dim3(tt_tiles(a.M)), (size_t)(TT_BM + COUT) * (CIN + TT_PAD) * sizeof(float),
+                                   st, "pdsc_pointwise_train_forward", a);
 }
 
 template <int CIN, int COUT, bool DX, bool DW>
 static int pwt_launch_backward_gemm(const PwtBwdArgs& a, hipStream_t st) {
-    const size_t lds_bytes = ((size_t)PWT_BM * (COUT + 4) + (DW ? (size_t)PWT_BM * (CIN + 4) : 0) + (DX ? (size_t)COUT * (CIN + 4) : 0)) *
-                             sizeof(float);
-    const int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(&pwt_backward_gemm_kernel<CIN, COUT, DX, DW>), lds_bytes,
-                                      "pdsc_pointwise_train_backward(dynamic LDS)");
-    if (rc != PDSC_OK) return rc;
-    hipLaunchKernelGGL((pwt_backward_gemm_kernel<CIN, COUT, DX, DW>), dim3(pwt_groups(a.M)), dim3(256), lds_bytes, st, a);
-    return check_launch("pdsc_pointwise_train_backward");
+    const size_t lds_floats = (size_t)TT_BM * (COUT + TT_PAD) + (DW ? TT_BM * (CIN + TT_PAD) : 0) + (DX ? COUT * (CIN + TT_PAD) : 0);
+    return launch_with_dynamic_lds(pwt_backward_gemm_kernel<CIN, COUT, DX, DW>, dim3(tt_groups(a.M)), lds_floats * sizeof(float), st,
+                                   "pdsc_pointwise_train_backward", a);
 }
 
 template <int CIN, int COUT>
@@ -461,7 +344,7 @@ extern "C" size_t pdsc_pointwise_train_workspace_bytes(int M, int Cin, int Cout)
     return pdsc::pwt_part_bytes(M, Cout) + pdsc::pwt_sums_bytes(Cout) + pdsc::pwt_dw_bytes(M, Cin, Cout);
 }
 
-#define PWT_ALIGNED16(p) (((uintptr_t)(p) & 15) == 0)
+using pdsc::aligned16;
 
 extern "C" int pdsc_pointwise_train_forward(const float* X, const float* W, const float* b, const float* gamma, const float* beta,
                                             float* running_mean, float* running_var, float momentum, float eps, float* Y, float* Z,
@@ -474,24 +357,20 @@ extern "C" int pdsc_pointwise_train_forward(const float* X, const float* W, cons
     PDSC_REQUIRE(M >= 2, "pdsc_pointwise_train_forward: M=%d (batch statistics need at least 2 rows)", M);
     PDSC_REQUIRE(momentum >= 0.f && momentum <= 1.f && eps >= 0.f, "pdsc_pointwise_train_forward: momentum=%g eps=%g", (double)momentum,
                  (double)eps);
-    PDSC_REQUIRE(PWT_ALIGNED16(X) && PWT_ALIGNED16(W) && PWT_ALIGNED16(Y) && PWT_ALIGNED16(Z),
+    PDSC_REQUIRE(aligned16(X) && aligned16(W) && aligned16(Y) && aligned16(Z),
                  "pdsc_pointwise_train_forward: X, W, Y, Z must be 16-byte aligned");
     PDSC_REQUIRE(ws && (((uintptr_t)ws | (uintptr_t)mean | (uintptr_t)invstd) & 7) == 0,
                  "pdsc_pointwise_train_forward: workspace, mean and invstd must be 8-byte aligned");
-    const size_t need = pdsc_pointwise_train_workspace_bytes(M, Cin, Cout);
-    if (ws_bytes < need) {
-        pdsc::set_error("pdsc_pointwise_train_forward: workspace of %zu bytes, needs %zu", ws_bytes, need);
-        return PDSC_ERR_WORKSPACE;
-    }
+    int rc = pdsc::check_workspace("pdsc_pointwise_train_forward", ws_bytes, pdsc_pointwise_train_workspace_bytes(M, Cin, Cout));
+    if (rc != PDSC_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
     pdsc::PwtFwdArgs a{};
     a.X = X; a.W = W; a.b = b; a.Y = Y; a.part = (double*)ws; a.M = M;
-    int rc;
     if (Cin == 128 && Cout == 128) rc = pdsc::pwt_launch_forward_gemm<128, 128>(a, st);
     else if (Cin == 128) rc = pdsc::pwt_launch_forward_gemm<128, 64>(a, st);
     else rc = pdsc::pwt_launch_forward_gemm<64, 64>(a, st);
     if (rc != PDSC_OK) return rc;
-    hipLaunchKernelGGL(pdsc::pwt_stats_merge_kernel, dim3(Cout / pdsc::PWT_MERGE_COLS), dim3(pdsc::PWT_MERGE_THREADS), 0, st, a.part, pdsc::pwt_tiles(M), M, Cout,
+    hipLaunchKernelGGL(pdsc::pwt_stats_merge_kernel, dim3(Cout / pdsc::PWT_MERGE_COLS), dim3(pdsc::PWT_MERGE_THREADS), 0, st, a.part, pdsc::tt_tiles(M), M, Cout,
                        momentum, eps, running_mean, running_var, mean, invstd);
     const int rows_per_block = 256 / (Cout / 4);
     int blocks = pdsc::ceil_div(M, rows_per_block * 4);
@@ -509,27 +388,24 @@ extern "C" int pdsc_pointwise_train_backward(const float* X, const float* W, con
     PDSC_REQUIRE(pdsc::pwt_shape_ok(Cin, Cout), "pdsc_pointwise_train_backward: (Cin, Cout) = (%d, %d); supported: (128,128) (128,64) (64,64)",
                  Cin, Cout);
     PDSC_REQUIRE(M >= 2, "pdsc_pointwise_train_backward: M=%d (batch statistics need at least 2 rows)", M);
-    PDSC_REQUIRE(PWT_ALIGNED16(X) && PWT_ALIGNED16(W) && PWT_ALIGNED16(Y) && PWT_ALIGNED16(dZ) && PWT_ALIGNED16(dX),
+    PDSC_REQUIRE(aligned16(X) && aligned16(W) && aligned16(Y) && aligned16(dZ) && aligned16(dX),
                  "pdsc_pointwise_train_backward: X, W, Y, dZ, dX must be 16-byte aligned");
     PDSC_REQUIRE(ws && (((uintptr_t)ws | (uintptr_t)mean | (uintptr_t)invstd) & 7) == 0,
                  "pdsc_pointwise_train_backward: workspace, mean and invstd must be 8-byte aligned");
-    const size_t need = pdsc_pointwise_train_workspace_bytes(M, Cin, Cout);
-    if (ws_bytes < need) {
-        pdsc::set_error("pdsc_pointwise_train_backward: workspace of %zu bytes, needs %zu", ws_bytes, need);
-        return PDSC_ERR_WORKSPACE;
-    }
+    int rc = pdsc::check_workspace("pdsc_pointwise_train_backward", ws_bytes, pdsc_pointwise_train_workspace_bytes(M, Cin, Cout));
+    if (rc != PDSC_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
     double* part = (double*)ws;
     double* sums = (double*)((char*)ws + pdsc::pwt_part_bytes(M, Cout));
     float* dwpart = (float*)((char*)sums + pdsc::pwt_sums_bytes(Cout));
-    const int tiles = pdsc::pwt_tiles(M);
+    const int tiles = pdsc::tt_tiles(M);
     if (Cout == 128)
         hipLaunchKernelGGL(pdsc::pwt_backward_reduce_kernel<128>, dim3(tiles), dim3(256), 0, st, Y, dZ, mean, invstd, gamma, beta, part, M);
     else
         hipLaunchKernelGGL(pdsc::pwt_backward_reduce_kernel<64>, dim3(tiles), dim3(256), 0, st, Y, dZ, mean, invstd, gamma, beta, part, M);
     hipLaunchKernelGGL(pdsc::pwt_sum_partials_kernel, dim3(2 * Cout / pdsc::PWT_MERGE_COLS), dim3(pdsc::PWT_MERGE_THREADS), 0, st, part, tiles, 2 * Cout, M, sums, dbeta,
                        dgamma);
-    int rc = pdsc::check_launch("pdsc_pointwise_train_backward(dbeta, dgamma)");
+    rc = pdsc::check_launch("pdsc_pointwise_train_backward(dbeta, dgamma)");
     if (rc != PDSC_OK) return rc;
     const bool want_dw = dW || db;
     if (!dX && !want_dw) return PDSC_OK;
@@ -540,8 +416,8 @@ extern "C" int pdsc_pointwise_train_backward(const float* X, const float* W, con
     else if (Cin == 128) rc = pdsc::pwt_launch_backward_gemm_select<128, 64>(a, dX != nullptr, want_dw, st);
     else rc = pdsc::pwt_launch_backward_gemm_select<64, 64>(a, dX != nullptr, want_dw, st);
     if (rc != PDSC_OK || !want_dw) return rc;
-    const int total = Cout * Cin + Cout;
-    hipLaunchKernelGGL(pdsc::pwt_merge_dw_kernel, dim3(pdsc::ceil_div(total, 64)), dim3(pdsc::PWT_MERGE_THREADS), 0, st, dwpart,
-                       pdsc::pwt_groups(M), Cout * Cin, Cout, dW, db);
-    return pdsc::check_launch("pdsc_pointwise_train_backward(dW merge)");
+    pdsc::TtMergeSegs sg{};
+    sg.add(0, 0, Cout * Cin, dW);
+    sg.add(0, Cout * Cin, Cout * Cin + Cout, db);
+    return pdsc::tt_launch_merge(dwpart, pdsc::tt_groups(M), Cout * Cin + Cout, 1, sg, st, "pdsc_pointwise_train_backward(dW merge)");
 }

@@ -652,20 +652,27 @@ def post_refinement(initial_trans, src, tgt, threshold: float, max_iters: int = 
 POINTWISE_TRAIN_SHAPES = ((128, 128), (128, 64), (64, 64))      # (Cin, Cout) of pdsc_pointwise_train_*
 
 
-def _pointwise_train_dims(x: torch.Tensor, weight: torch.Tensor, what: str) -> Tuple[int, int, int]:
+def _train_dims(x: torch.Tensor, weight: torch.Tensor, what: str) -> Tuple[int, int, int]:
     if x.dim() != 2 or weight.dim() != 2 or weight.shape[1] != x.shape[1]:
         raise ValueError(f"{what}: x must be [M,Cin] and weight [Cout,Cin], got {tuple(x.shape)} {tuple(weight.shape)}")
-    m, cin, cout = x.shape[0], x.shape[1], weight.shape[0]
+    return x.shape[0], x.shape[1], weight.shape[0]
+
+
+def _train_workspace(nbytes: int, device) -> torch.Tensor:
+    return torch.empty(max((int(nbytes) + 7) // 8, 1), device=device, dtype=torch.float64)
+
+
+def _out(want: bool, device, *shape):
+    return torch.empty(*shape, device=device, dtype=torch.float32) if want else None
+
+
+def _pointwise_train_dims(x: torch.Tensor, weight: torch.Tensor, what: str) -> Tuple[int, int, int]:
+    m, cin, cout = _train_dims(x, weight, what)
     if (cin, cout) not in POINTWISE_TRAIN_SHAPES:
         raise ValueError(f"{what}: (Cin, Cout) = ({cin}, {cout}); supported: {POINTWISE_TRAIN_SHAPES}")
     if m < 2:
         raise ValueError(f"{what}: M = {m} rows (batch statistics need at least 2 values per channel)")
     return m, cin, cout
-
-
-def _pointwise_train_workspace(lib, m: int, cin: int, cout: int, device) -> torch.Tensor:
-    nb = int(lib.pdsc_pointwise_train_workspace_bytes(m, cin, cout))
-    return torch.empty(max((nb + 7) // 8, 1), device=device, dtype=torch.float64)
 
 
 @_on_device
@@ -687,7 +694,7 @@ def pointwise_train_forward(x, weight, bias, gamma, beta, running_mean, running_
     z = torch.empty_like(y)
     mean = torch.empty(cout, device=x.device, dtype=torch.float64)
     invstd = torch.empty_like(mean)
-    ws = _pointwise_train_workspace(lib, m, cin, cout, x.device)
+    ws = _train_workspace(lib.pdsc_pointwise_train_workspace_bytes(m, cin, cout), x.device)
     _lib.check(lib.pdsc_pointwise_train_forward(_p(x), _p(weight), _p(bias), _p(gamma), _p(beta), _p(running_mean), _p(running_var),
                                                 float(momentum), float(eps), _p(y), _p(z), _p(mean), _p(invstd), _p(ws),
                                                 ws.numel() * 8, m, cin, cout, _stream()), "pdsc_pointwise_train_forward")
@@ -712,12 +719,9 @@ def pointwise_train_backward(x, weight, gamma, beta, y, mean, invstd, dz, want_d
     for t, name in ((gamma, "gamma"), (beta, "beta"), (mean, "mean"), (invstd, "invstd")):
         if t.shape != (cout,):
             raise ValueError(f"pointwise_train_backward: {name} must be [{cout}], got {tuple(t.shape)}")
-
-    def out(want, *shape):
-        return torch.empty(*shape, device=x.device, dtype=torch.float32) if want else None
-    dx, dw = out(want_dx, m, cin), out(want_dw, cout, cin)
-    db, dgamma, dbeta = out(want_db, cout), out(want_dgamma, cout), out(want_dbeta, cout)
-    ws = _pointwise_train_workspace(lib, m, cin, cout, x.device)
+    dx, dw = _out(want_dx, x.device, m, cin), _out(want_dw, x.device, cout, cin)
+    db, dgamma, dbeta = _out(want_db, x.device, cout), _out(want_dgamma, x.device, cout), _out(want_dbeta, x.device, cout)
+    ws = _train_workspace(lib.pdsc_pointwise_train_workspace_bytes(m, cin, cout), x.device)
     _lib.check(lib.pdsc_pointwise_train_backward(_p(x), _p(weight), _p(gamma), _p(beta), _p(y), _p(mean), _p(invstd), _p(dz), _p(dx),
                                                  _p(dw), _p(db), _p(dgamma), _p(dbeta), _p(ws), ws.numel() * 8, m, cin, cout,
                                                  _stream()), "pdsc_pointwise_train_backward")
@@ -733,23 +737,13 @@ def linear_train_shape_ok(cin: int, cout: int) -> bool:
     return cout == LINEAR_TRAIN_COUT and (1 <= cin <= 16 or cin == 64)
 
 
-def _train_workspace(nbytes: int, device) -> torch.Tensor:
-    return torch.empty(max((int(nbytes) + 7) // 8, 1), device=device, dtype=torch.float64)
-
-
 def _linear_train_dims(x: torch.Tensor, weight: torch.Tensor, what: str) -> Tuple[int, int, int]:
-    if x.dim() != 2 or weight.dim() != 2 or weight.shape[1] != x.shape[1]:
-        raise ValueError(f"{what}: x must be [M,Cin] and weight [Cout,Cin], got {tuple(x.shape)} {tuple(weight.shape)}")
-    m, cin, cout = x.shape[0], x.shape[1], weight.shape[0]
+    m, cin, cout = _train_dims(x, weight, what)
     if not linear_train_shape_ok(cin, cout):
         raise ValueError(f"{what}: (Cin, Cout) = ({cin}, {cout}); supported: (1..16, 128), (64, 128)")
     if m < 1:
         raise ValueError(f"{what}: M = {m} rows")
     return m, cin, cout
-
-
-def _out(want: bool, device, *shape):
-    return torch.empty(*shape, device=device, dtype=torch.float32) if want else None
 
 
 @_on_device

@@ -18,7 +18,7 @@ These are CALL times, host work included.
                          TrainablePointDSC(fused_layers=True) -- the step as it was before the flag existed -- likewise; with
                          --profile-steps the profiled model has both flags set
     --profile-steps K    run K device steps and exit: the program of the one `rocprofv3 --kernel-trace --stats` run
-    --breakdown FILE     group the per-kernel table tools/rocpd_kernel_stats.py made of that run into the step's six parts"""
+    --breakdown FILE     group the per-kernel table tools/rocpd_kernel_stats.py made of that run into the step's parts (GROUPS)"""
 import argparse
 import re
 import statistics
@@ -34,6 +34,7 @@ GROUPS = [      # first match wins
     ("attention backward", r"att_bwd_"),
     ("M forward + backward", r"gram_rows_kernel<2|feature_compat_backward"),
     ("losses", r"pdsc::(cls_|sm_loss_|trans_partial|trans_finish)"),
+    ("parameter-gradient merge (train_tile.h, both below)", r"pdsc::tt_merge_"),
     ("plain linears (layer0, q|k|v, fc_message.6, head)", r"pdsc::lth?_"),
     ("fused point-wise layers (conv + BN + ReLU)", r"pdsc::pwt_"),
     ("tail and compat (the library's other kernels)", r"pdsc::"),
