@@ -269,44 +269,12 @@ __global__ __launch_bounds__(FPFH_WAVE) void nb_search_kernel(const float* __res
 __device__ __forceinline__ int list_row(int id, int n) { return id < 0 ? 0 : (id >= n ? n - 1 : id); }
 
 // ---- b. normals -------------------------------------------------------------------------------------------------------------
-// Unit eigenvector of the smallest eigenvalue of the symmetric matrix {c00 c01 c02; c01 c11 c12; c02 c12 c22}: cyclic Jacobi, the
-// rotation formulas of kabsch_from_covariance (pdsc_common.h).
+// Unit eigenvector of the smallest eigenvalue of the symmetric matrix {c00 c01 c02; c01 c11 c12; c02 c12 c22}: the cyclic Jacobi of
+// kabsch3.h, 16 sweeps to 1e-18.
 __device__ inline void smallest_eigenvector(double c00, double c01, double c02, double c11, double c12, double c22, double (&nv)[3]) {
     double A[3][3] = {{c00, c01, c02}, {c01, c11, c12}, {c02, c12, c22}};
-    double V[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
-    for (int sweep = 0; sweep < 16; ++sweep) {
-        const double off = fabs(A[0][1]) + fabs(A[0][2]) + fabs(A[1][2]);
-        const double diag = fabs(A[0][0]) + fabs(A[1][1]) + fabs(A[2][2]);
-        if (off <= 1e-300 || off <= 1e-18 * diag) break;
-#pragma unroll
-        for (int pq = 0; pq < 3; ++pq) {
-            const int p = (pq == 2) ? 1 : 0;
-            const int q = (pq == 0) ? 1 : 2;
-            const double apq = A[p][q];
-            if (fabs(apq) < 1e-300) continue;
-            const double theta = (A[q][q] - A[p][p]) / (2.0 * apq);
-            const double tt = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-            const double c = 1.0 / sqrt(tt * tt + 1.0), s = tt * c;
-#pragma unroll
-            for (int r = 0; r < 3; ++r) {  // A <- A J
-                const double arp = A[r][p], arq = A[r][q];
-                A[r][p] = c * arp - s * arq;
-                A[r][q] = s * arp + c * arq;
-            }
-#pragma unroll
-            for (int r = 0; r < 3; ++r) {  // A <- J^T A
-                const double apr = A[p][r], aqr = A[q][r];
-                A[p][r] = c * apr - s * aqr;
-                A[q][r] = s * apr + c * aqr;
-            }
-#pragma unroll
-            for (int r = 0; r < 3; ++r) {  // V <- V J
-                const double vrp = V[r][p], vrq = V[r][q];
-                V[r][p] = c * vrp - s * vrq;
-                V[r][q] = s * vrp + c * vrq;
-            }
-        }
-    }
+    double V[3][3];
+    jacobi_eig3<16>(A, V, 1e-18);
     const double e0 = A[0][0], e1 = A[1][1], e2 = A[2][2];
     const int m = (e0 <= e1 && e0 <= e2) ? 0 : (e1 <= e2 ? 1 : 2);
     // select the column with compares (runtime-indexed local arrays would go to scratch memory)

@@ -25,18 +25,9 @@
 // dsigma terms in a fixed tree.  An entry of knn_idx outside [0, N) is never used as an address: it poisons that seed's block and
 // dsigma term with NaN.  A seed whose u_t is the zero vector yields NaN (0 / 0), as torch's autograd does.
 #include "pdsc_common.h"
+#include "solver_common.h"
 
 namespace pdsc {
-
-__device__ __forceinline__ int ssb_chosen_iterate(unsigned int mask, int num_iter) {      // solver.hip: chosen_iterate
-    const unsigned int m = num_iter >= 32 ? mask : (mask & ((1u << num_iter) - 1u));
-    return m ? (__ffs((int)m) - 1) : (num_iter - 1);
-}
-__device__ __forceinline__ void ssb_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // The spatial term max(1 - (|a_i - a_j| - |b_i - b_j|)^2 / sigma_d^2, 0) with the reference's roundings (models/PointDSC.py:268-272 on
 // fp32 tensors): each distance is the correctly rounded fp32 square root (fp64 sum of squares, fp64 sqrt, one rounding), their
@@ -49,95 +40,6 @@ __device__ __forceinline__ double ssb_spatial(float ax, float ay, float az, floa
     const float dt = (float)sqrt((ex * ex + ey * ey) + ez * ez);
     const float df = ds - dt;
     return fmax(1.0 - (double)(df * df) / sd2, 0.0);
-}
-
-// kabsch_from_covariance (pdsc_common.h) returning what its backward needs: R, U = (u1 u2 u3) as columns, s' = (s1, s2, u3 . H v3).
-// A copy of that body (which stays as it is: the forward's code objects do not change).
-__device__ inline void ssb_kabsch(const double (&H)[3][3], double (&R)[3][3], double (&U)[3][3], double (&sp)[3]) {
-    double A[3][3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) A[i][j] = H[0][i] * H[0][j] + H[1][i] * H[1][j] + H[2][i] * H[2][j];
-    double V[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
-    for (int sweep = 0; sweep < 12; ++sweep) {
-        const double off = fabs(A[0][1]) + fabs(A[0][2]) + fabs(A[1][2]);
-        const double diag = fabs(A[0][0]) + fabs(A[1][1]) + fabs(A[2][2]);
-        if (off <= 1e-300 || off <= 1e-17 * diag) break;
-#pragma unroll
-        for (int pq = 0; pq < 3; ++pq) {
-            const int p = (pq == 2) ? 1 : 0;
-            const int q = (pq == 0) ? 1 : 2;
-            const double apq = A[p][q];
-            if (fabs(apq) < 1e-300) continue;
-            const double theta = (A[q][q] - A[p][p]) / (2.0 * apq);
-            const double tt = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-            const double c = 1.0 / sqrt(tt * tt + 1.0), s = tt * c;
-#pragma unroll
-            for (int r = 0; r < 3; ++r) {
-                const double arp = A[r][p], arq = A[r][q];
-                A[r][p] = c * arp - s * arq;
-                A[r][q] = s * arp + c * arq;
-            }
-#pragma unroll
-            for (int r = 0; r < 3; ++r) {
-                const double apr = A[p][r], aqr = A[q][r];
-                A[p][r] = c * apr - s * aqr;
-                A[q][r] = s * apr + c * aqr;
-            }
-#pragma unroll
-            for (int r = 0; r < 3; ++r) {
-                const double vrp = V[r][p], vrq = V[r][q];
-                V[r][p] = c * vrp - s * vrq;
-                V[r][q] = s * vrp + c * vrq;
-            }
-        }
-    }
-    int i0 = 0, i1 = 1, i2 = 2;
-    double e0 = A[0][0], e1 = A[1][1], e2 = A[2][2];
-    if (e0 < e1) { double t = e0; e0 = e1; e1 = t; int ti = i0; i0 = i1; i1 = ti; }
-    if (e0 < e2) { double t = e0; e0 = e2; e2 = t; int ti = i0; i0 = i2; i2 = ti; }
-    if (e1 < e2) { double t = e1; e1 = e2; e2 = t; int ti = i1; i1 = i2; i2 = ti; }
-    (void)i2;
-#define PDSC_SEL3(r, i) ((i) == 0 ? V[r][0] : ((i) == 1 ? V[r][1] : V[r][2]))
-    double v1[3] = {PDSC_SEL3(0, i0), PDSC_SEL3(1, i0), PDSC_SEL3(2, i0)};
-    double v2[3] = {PDSC_SEL3(0, i1), PDSC_SEL3(1, i1), PDSC_SEL3(2, i1)};
-#undef PDSC_SEL3
-    double v3[3] = {v1[1] * v2[2] - v1[2] * v2[1], v1[2] * v2[0] - v1[0] * v2[2], v1[0] * v2[1] - v1[1] * v2[0]};
-    double u1[3], u2[3], u3[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) u1[i] = H[i][0] * v1[0] + H[i][1] * v1[1] + H[i][2] * v1[2];
-    double n1 = sqrt(u1[0] * u1[0] + u1[1] * u1[1] + u1[2] * u1[2]);
-    if (n1 > 1e-150) { u1[0] /= n1; u1[1] /= n1; u1[2] /= n1; }
-    else { u1[0] = 1; u1[1] = 0; u1[2] = 0; }
-#pragma unroll
-    for (int i = 0; i < 3; ++i) u2[i] = H[i][0] * v2[0] + H[i][1] * v2[1] + H[i][2] * v2[2];
-    double dp = u2[0] * u1[0] + u2[1] * u1[1] + u2[2] * u1[2];
-    u2[0] -= dp * u1[0]; u2[1] -= dp * u1[1]; u2[2] -= dp * u1[2];
-    double n2 = sqrt(u2[0] * u2[0] + u2[1] * u2[1] + u2[2] * u2[2]);
-    if (n2 > 1e-12 * (n1 > 1e-150 ? n1 : 1.0) && n2 > 1e-150) { u2[0] /= n2; u2[1] /= n2; u2[2] /= n2; }
-    else {
-        int m = (fabs(u1[0]) <= fabs(u1[1]) && fabs(u1[0]) <= fabs(u1[2])) ? 0 : (fabs(u1[1]) <= fabs(u1[2]) ? 1 : 2);
-        const double e[3] = {m == 0 ? 1.0 : 0.0, m == 1 ? 1.0 : 0.0, m == 2 ? 1.0 : 0.0};
-        double d2 = e[0] * u1[0] + e[1] * u1[1] + e[2] * u1[2];
-        u2[0] = e[0] - d2 * u1[0]; u2[1] = e[1] - d2 * u1[1]; u2[2] = e[2] - d2 * u1[2];
-        n2 = sqrt(u2[0] * u2[0] + u2[1] * u2[1] + u2[2] * u2[2]);
-        u2[0] /= n2; u2[1] /= n2; u2[2] /= n2;
-        n2 = 0.0;                                            // rank <= 1: the second singular value
-    }
-    u3[0] = u1[1] * u2[2] - u1[2] * u2[1];
-    u3[1] = u1[2] * u2[0] - u1[0] * u2[2];
-    u3[2] = u1[0] * u2[1] - u1[1] * u2[0];
-    double hv3[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) hv3[i] = H[i][0] * v3[0] + H[i][1] * v3[1] + H[i][2] * v3[2];
-    sp[0] = n1; sp[1] = n2; sp[2] = u3[0] * hv3[0] + u3[1] * hv3[1] + u3[2] * hv3[2];      // signed: det(V U^T) s3
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        U[i][0] = u1[i]; U[i][1] = u2[i]; U[i][2] = u3[i];
-#pragma unroll
-        for (int j = 0; j < 3; ++j) R[i][j] = v1[i] * u1[j] + v2[i] * u2[j] + v3[i] * u3[j];
-    }
 }
 
 template <int NB>
@@ -175,7 +77,7 @@ __global__ __launch_bounds__(64) void seed_solve_backward_kernel(SsbArgs a) {
         if (lane == 0) a.active[seed] = 0;
         return;
     }
-    const int T = ssb_chosen_iterate(a.conv_mask[b], a.num_iter) + 1;          // 1 .. num_iter
+    const int T = chosen_iterate(a.conv_mask[b], a.num_iter) + 1;          // 1 .. num_iter
     const bool valid = lane < k;
     int idx = a.knn_idx[seed * k + (valid ? lane : 0)];
     const bool oob = (unsigned int)idx >= (unsigned int)N;
@@ -192,7 +94,7 @@ __global__ __launch_bounds__(64) void seed_solve_backward_kernel(SsbArgs a) {
     }
     const float sg = a.sigma[0], rsig2 = 1.0f / (sg * sg);
     const double sg2d = (double)sg * (double)sg, sd2d = (double)a.sigma_spat[0] * (double)a.sigma_spat[0];
-    ssb_wave_sync();
+    wave_lds_sync();
     {   // ---- 1 - G and M, row by row: lane = column j holds its own feature row as 128 doubles, row i's features arrive as wave-
         // uniform loads; G_ij is the fp64 chain over the channels in order, so G (and M) are symmetric bit for bit
         double fj[PDSC_CHANNELS];
@@ -221,7 +123,7 @@ __global__ __launch_bounds__(64) void seed_solve_backward_kernel(SsbArgs a) {
             if (lane < KP) { sh.M[i * MLD + lane] = m; sh.G[i * MLD + lane] = omg; }
         }
     }
-    ssb_wave_sync();
+    wave_lds_sync();
     const int rowl = min(lane, KP - 1);
     float mrow[KP];
 #pragma unroll
@@ -230,7 +132,7 @@ __global__ __launch_bounds__(64) void seed_solve_backward_kernel(SsbArgs a) {
     float v = valid ? 1.0f : 0.0f;
     if (lane < KP) sh.V[0][lane] = v;
     for (int t = 1; t <= T; ++t) {
-        ssb_wave_sync();
+        wave_lds_sync();
         float nv = 0.f;
 #pragma unroll
         for (int j4 = 0; j4 < KP / 4; ++j4) {
@@ -329,9 +231,9 @@ __global__ __launch_bounds__(64) void seed_solve_backward_kernel(SsbArgs a) {
         const float dot = wave_sum_dpp(gv * vt);
         float gu = (gv - dot * (ut / nrm)) / e;                   // nrm == 0: 0 / 0 = NaN, as autograd's
         gu = valid ? gu : 0.f;
-        ssb_wave_sync();                                          // the previous round's readers of sh.x are done
+        wave_lds_sync();                                          // the previous round's readers of sh.x are done
         if (lane < KP) sh.x[lane] = gu;
-        ssb_wave_sync();
+        wave_lds_sync();
         float ngv = 0.f;
 #pragma unroll
         for (int j4 = 0; j4 < KP / 4; ++j4) {
@@ -346,7 +248,7 @@ __global__ __launch_bounds__(64) void seed_solve_backward_kernel(SsbArgs a) {
         gv = valid ? ngv : 0.f;
     }
     // ---- dM -> dMf (product, zero diagonal, clamp), the dsigma term
-    ssb_wave_sync();
+    wave_lds_sync();
     double dsg = 0.0;
 #pragma unroll
     for (int j = 0; j < KP; ++j) {
@@ -360,12 +262,12 @@ __global__ __launch_bounds__(64) void seed_solve_backward_kernel(SsbArgs a) {
         dsg = fma((double)dmf, (double)omg, dsg);
         if (lane < KP) sh.M[lane * MLD + j] = dmf;
     }
-    ssb_wave_sync();
+    wave_lds_sync();
     if (lane < KP) {
 #pragma unroll
         for (int j = 0; j < KP; ++j) sh.G[lane * MLD + j] = sh.M[lane * MLD + j] + sh.M[j * MLD + lane];
     }
-    ssb_wave_sync();
+    wave_lds_sync();
     // ---- dF_knn = (1 / sigma^2) (dMf + dMf^T) F_knn: lane = channels (lane, lane + 64), the k rows in registers
     float f0[KP], f1[KP];
 #pragma unroll

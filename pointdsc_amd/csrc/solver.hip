@@ -6,15 +6,9 @@
 // One WAVEFRONT per seed (seed_solve_kernel below), lane i owns neighbour i (k <= 64).  Zero host round trips (the reference
 // pays one D2H+H2D per SVD batch and one sync per power iteration); k x k never leaves the CU.
 #include "pdsc_common.h"
+#include "solver_common.h"      // chosen_iterate, wave_lds_sync
 
 namespace pdsc {
-
-// chosen iterate = first iteration at which EVERY seed of the pair passed allclose (the reference breaks
-// there), else the last one.
-__device__ __forceinline__ int chosen_iterate(unsigned int mask, int num_iter) {
-    const unsigned int m = num_iter >= 32 ? mask : (mask & ((1u << num_iter) - 1u));
-    return m ? (__ffs((int)m) - 1) : (num_iter - 1);
-}
 
 // weighted Procrustes of one seed, part 1: lane = neighbour, v = its eigenvector entry (0 for lanes >= k).
 // models/PointDSC.py:282 (weight normalisation), models/common.py:17-33.  Lane 0 leaves the 3x3 covariance H and the two
@@ -100,11 +94,6 @@ struct SolveLds {
     float pts[KP][8];
     float v[KP];
 };
-__device__ __forceinline__ void wave_lds_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 template <int NB>
 __global__ __launch_bounds__(64 * SV_WAVES) void seed_solve_kernel(const float* __restrict__ normed, const float* __restrict__ src,
