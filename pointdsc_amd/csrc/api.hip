@@ -625,15 +625,16 @@ static int run_fused_layer(const ForwardCtx& x, int i, bool last, const float* c
         }
     }
     if (plan.pf) c.io_flags = (tail ? PDSC_IO_PARTIALS_PF | PDSC_IO_RES_PF : 0) | (head ? PDSC_IO_FEATB_PF : 0);
-    // the forward's own fields: the point-fragment route reports to the range sentinel and takes no trace (layer_args.h)
+    // the forward's own fields: EVERY launch reports to the range sentinel (NULL in exact fp32 and in the probe: bind_workspace);
+    // the point-fragment route takes no trace (layer_args.h)
     LayerArgs a = layer_args_from_call(c);
     a.nvalid = split ? x.c.nvalid : nullptr;
+    a.range_flag = x.range_flag;
     if (tail) a.part_slots = slots;
-    if (plan.pf) {
+    if (plan.pf)
         a.value_fold = plan.fold;
-        a.range_flag = x.range_flag;
-    } else
-        a.trace = pdsc_layer_trace_buffer();      // range_flag stays NULL here: wiring these routes is a follow-up of its own
+    else
+        a.trace = pdsc_layer_trace_buffer();
     PDSC_TRY(validate_layer_args(a, plan.kernel, "pdsc_forward_testing(layer)"));
     return dispatch_layer(a, plan.kernel, x.st);
 }
@@ -664,7 +665,7 @@ static int run_encoder_fused(const ForwardCtx& x) {
 }
 
 // One launch per conv, every intermediate in the workspace: the probe (which records |max| of each kind), num_layers == 0 and
-// the tuning knob PDSC_FUSED_LAYERS = 0
+// the tuning knob PDSC_FUSED_LAYERS = 0 (experiments builds; NO range sentinel on this path: pdsc_pack_qkv_split does not note)
 static int run_encoder_per_conv(const ForwardCtx& x) {
     const int C = PDSC_CHANNELS, H = C / 2, M = x.M;
     float *t64a = x.L.at<float>(x.c.workspace, WS_T64A), *t64b = x.L.at<float>(x.c.workspace, WS_T64B);
@@ -773,11 +774,14 @@ static int finish_testing(const ForwardCtx& x) {
                                     L.at<int>(ws, WS_SOLVES), c.bs, c.N, x.S, c.nvalid, x.st, L.at<int>(ws, WS_REFINE_TRACE), x.range_flag,
                                     range_report_slot());
 }
-// best hypothesis is the result (:186 is skipped); the labels of the call are the logits (:190-191); range_flag is not read here
+// best hypothesis is the result (:186 is skipped); the labels of the call are the logits (:190-191).  pdsc_select_best does not know
+// the range sentinel: a launch of its own behind it turns the pose of every flagged pair into NaN, as the refinement launch of the
+// testing forward does
 static int finish_validation(const ForwardCtx& x) {
     const ForwardCall& c = x.c;
     PDSC_TRY(pdsc_select_best(x.counts, x.seed_trans, c.src, c.tgt, c.cfg->inlier_threshold, x.L.at<int>(c.workspace, WS_BEST), c.final_trans,
                               x.keys /* scratch */, c.bs, c.N, x.S, x.st));
+    if (x.range_flag) PDSC_TRY(launch_poison_flagged(c.final_trans, x.range_flag, c.bs, x.st));
     return launch_copy_u32((unsigned int*)c.final_labels, (const unsigned int*)x.conf, (size_t)x.M, x.st);
 }
 

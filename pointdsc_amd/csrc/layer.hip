@@ -137,6 +137,7 @@ __global__ __launch_bounds__(256, 3) void layer_fused_kernel(LayerArgs a) {
     if (m0 >= M) return;                                         // (ragged batches: tile past the pair's own rows; workgroup-uniform)
 
     LF_STAMP(0)
+    float rmax = 0.f;                                                // fp16 range sentinel (pdsc_common.h): what this thread converts to fp16 pairs (QKV_X3)
     f32x4 wpre[16];                                                  // PointCN weight tile of this wave (prefetched early)
     if (HAS_TAIL) {
         f32x4 w128[16], w64[8];
@@ -206,7 +207,7 @@ __global__ __launch_bounds__(256, 3) void layer_fused_kernel(LayerArgs a) {
             store_tile<false, false>(acc, a.bq, n0, Xb, 32 * wave, l31, h, nullptr);
             __syncthreads();
             if (a.qkv_out) tile_to_global<LF_LD>(Xb, a.qkv_out + 128 * c, 3 * PDSC_CHANNELS, m0, M, t);
-            if (a.qs) {
+            if (a.qs) {      // (stage-level calls only: a forward's split attention comes with wq_split, the form below, which carries the sentinel)
                 unsigned char* img = a.kv + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * SPL_TILE_STRIDE;
                 const int valid = min(LF_ROWS, M - m0);
                 if (c == 0) tile_to_split<0, LF_LD>(Xb, a.qs + (size_t)m0 * SPL_Q_LD, img, valid, t);
@@ -245,10 +246,10 @@ __global__ __launch_bounds__(256, 3) void layer_fused_kernel(LayerArgs a) {
                 f32x4 v;
                 sp16x4 hi, lo;
 #pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    v[e] = fmaxf(acc[4 * g + e] + bv[e], 0.f);
-                    sp16 xh, xl; split_sp16(v[e], xh, xl); hi[e] = xh; lo[e] = xl;
-                }
+                for (int e = 0; e < 4; ++e) v[e] = fmaxf(acc[4 * g + e] + bv[e], 0.f);
+                range_note(rmax, v);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) { sp16 xh, xl; split_sp16(v[e], xh, xl); hi[e] = xh; lo[e] = xl; }
                 *reinterpret_cast<f32x4*>(Xa + l31 * LF_LD + col) = v;
                 *reinterpret_cast<sp16x4*>(Xh + l31 * LF_XLD16 + col) = hi;
                 *reinterpret_cast<sp16x4*>(Xl + l31 * LF_XLD16 + col) = lo;
@@ -290,14 +291,15 @@ __global__ __launch_bounds__(256, 3) void layer_fused_kernel(LayerArgs a) {
             if (c == 0) { LF_STAMP(11) }
             if (a.qkv_out) tile_to_global<LF_LD>(Xa, a.qkv_out + 128 * c, 3 * PDSC_CHANNELS, m0, M, t);
             if (a.qs) {
-                if (c == 0) tile_to_split<0, LF_LD>(Xa, a.qs + (size_t)m0 * SPL_Q_LD, img, valid, t);
-                else if (c == 1) tile_to_split<1, LF_LD>(Xa, nullptr, img, valid, t);
-                else tile_to_split<2, LF_LD>(Xa, nullptr, img, valid, t);
+                if (c == 0) tile_to_split<0, LF_LD>(Xa, a.qs + (size_t)m0 * SPL_Q_LD, img, valid, t, rmax);
+                else if (c == 1) tile_to_split<1, LF_LD>(Xa, nullptr, img, valid, t, rmax);
+                else tile_to_split<2, LF_LD>(Xa, nullptr, img, valid, t, rmax);
             }
             if (c == 0) { LF_STAMP(12) }
         }
         LF_STAMP(13)
     }
+    if (HAS_HEAD && QKV_X3) range_report(a.range_flag, blockIdx.y, rmax);      // once per wavefront
 }
 
 template <bool T, bool H>

@@ -57,8 +57,12 @@ constexpr int layer_merge_limit(LayerKernel k) {
 
 // The one mapping from the public call (include/pointdsc_hip.h) to the kernels' argument.  What the struct does not expose stays
 // zero: nvalid, range_flag and value_fold are the forward's own, trace is set by whoever launches (launch_layer_h3 leaves the
-// few-tile kernel of layer_coop.hip when it is set, and the product build's launch_layer_wave rejects a launch with it; only
-// the point-fragment route reports to the fp16 range sentinel so far).
+// few-tile kernel of layer_coop.hip when it is set, and the product build's launch_layer_wave rejects a launch with it).
+// Every kernel a forward can launch reports to the fp16 range sentinel when range_flag is given: layer_h3.hip, layer_coop.hip,
+// the fp32-GEMM forms of layer_wave.hip and layer.hip.  Three paths carry NO sentinel, and no product forward runs them: the generic
+// H3 form of layer_wave_kernel (stage tests; experiments knob PDSC_LAYER_H3_VARIANT = 0), layer_split.hip (experiments builds), and
+// the one-launch-per-conv encoder under the split attention (experiments knob PDSC_FUSED_LAYERS = 0; api.hip:run_encoder_per_conv),
+// whose pdsc_pack_qkv_split converts q, k, v without a note: range_flag is zeroed and never set there.
 inline LayerArgs layer_args_from_call(const pdsc_layer_call& c) {
     LayerArgs a{};
     a.msg = c.msg; a.part_o = c.part_o; a.part_ml = c.part_ml; a.nsplit = c.nsplit; a.part_slots = c.nsplit; a.Npad = c.Npad;

@@ -113,6 +113,10 @@ __global__ __launch_bounds__(64 * LW_WAVES, 2) void layer_wave_kernel(LayerArgs 
 
     unsigned char* img = (H && a.kv) ? a.kv + (size_t)gw * SPL_TILE_STRIDE : nullptr;
     f32x16 acc, cross;
+    // fp16 range sentinel (pdsc_common.h) of the fp32-GEMM forms: what they convert to fp16 pairs is the PointCN output (operand of the
+    // split q|k|v projection) and q, k, v (the attention's streams).  The generic H3 form (HX) carries none: no forward runs it
+    constexpr bool RANGE = H && X3 && !HX;
+    float rmax = 0.f;
 
     static_for<0, NCH>([&](auto ic) {
         constexpr int i = decltype(ic)::value;
@@ -200,7 +204,10 @@ __global__ __launch_bounds__(64 * LW_WAVES, 2) void layer_wave_kernel(LayerArgs 
                 if constexpr (X3 && d.tile == 3) {
                     // featB -> fp16 hi / lo operands of the 16-wide k-steps: step kk, lane-half h <- channels 16kk+8h..+7
 #pragma unroll
-                    for (int kk = 0; kk < 8; ++kk) make_kstep<false>(x4[2 * kk], x4[2 * kk + 1], xh[kk], xl[kk]);
+                    for (int kk = 0; kk < 8; ++kk) {
+                        if constexpr (RANGE) make_kstep<false>(x4[2 * kk], x4[2 * kk + 1], xh[kk], xl[kk], rmax);
+                        else make_kstep<false>(x4[2 * kk], x4[2 * kk + 1], xh[kk], xl[kk]);
+                    }
                 }
             } else {
                 // q | k | v, output tile d.tile of 12: tiles 0..3 = q, 4..7 = k, 8..11 = v
@@ -218,6 +225,7 @@ __global__ __launch_bounds__(64 * LW_WAVES, 2) void layer_wave_kernel(LayerArgs 
 #pragma unroll
                         for (int g = 0; g < 4; ++g) {
                             unsigned hi[2], lo[2];
+                            if constexpr (RANGE) range_note(rmax, v[g]);
                             split4(v[g], hi, lo);
                             *reinterpret_cast<u32x4*>(patch + l31 * LW_PROW + 64 * h + 16 * g) = chunk_for_store(hi, lo);
                         }
@@ -239,6 +247,7 @@ __global__ __launch_bounds__(64 * LW_WAVES, 2) void layer_wave_kernel(LayerArgs 
                                 for (int e = 0; e < 4; ++e) z[e] = live ? z[e] : 0.f;            // keys beyond N are zero
                             }
                             unsigned hi[2], lo[2];
+                            if constexpr (RANGE) range_note(rmax, z);
                             split4(z, hi, lo);
                             *reinterpret_cast<u32x4*>(patch + l31 * LW_PROW + 64 * h + 16 * g) = chunk_for_store(hi, lo);
                         }
@@ -259,6 +268,7 @@ __global__ __launch_bounds__(64 * LW_WAVES, 2) void layer_wave_kernel(LayerArgs 
 #pragma unroll
                                 for (int e = 0; e < 4; ++e) z[e] = live ? z[e] : 0.f;
                             }
+                            if constexpr (RANGE) range_note(rmax, z);      // (noted before the transpose: split2 below sees the same values)
                             *reinterpret_cast<f32x4*>(Vs + l31 * LW_VLD + 8 * g + 4 * h) = z;
                         }
                         wave_lds_sync();
@@ -283,6 +293,7 @@ __global__ __launch_bounds__(64 * LW_WAVES, 2) void layer_wave_kernel(LayerArgs 
         __builtin_amdgcn_sched_barrier(0);      // chunks are the unit of the software pipeline: no code motion across them
     });
 
+    if constexpr (RANGE) range_report(a.range_flag, td.b, rmax);
     LW_STAMP(63)
 }
 

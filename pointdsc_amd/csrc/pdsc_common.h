@@ -48,8 +48,10 @@ int launch_classifier_hidden(const float* X, const float* W1, const float* b1, c
 // Every site that converts an activation notes its magnitude (range_note: one v_max3_f32 per two values); a wavefront whose maximum
 // reaches the bound sets the word of its pair in `range_flag` ([bs] u32, workspace entry "range_flag": zeroed by the forward's first
 // launch, read by its last one, which turns the pose of such a pair into NaN -- a result that is wrong is never returned silently).
-// run_forward passes the array to the layer kernels in LayerArgs.range_flag (layer_args.h); stage-level calls outside a forward
-// leave it NULL and the kernels skip the report.
+// run_forward passes the array to EVERY fused-layer launch in LayerArgs.range_flag (layer_args.h: which kernels note what, and the
+// three experiments-only paths that carry no sentinel: generic H3 wave form, layer_split.hip, PDSC_FUSED_LAYERS = 0), and the
+// validation forward, which has no refinement launch, turns the flagged poses into NaN in a launch of its own; stage-level calls
+// outside a forward leave it NULL and the kernels skip the report.
 constexpr float PDSC_F16_RANGE = 65504.0f;
 
 // opt-in event timing of the roofline kernels (api.hip); no-ops unless pdsc_profile_enable() was called

@@ -46,6 +46,8 @@ int launch_select_best(const int* counts, const float* seed_trans, const float* 
 int launch_post_refinement(const float* initial_trans, const float* src, const float* tgt, float threshold, int max_iters,
                            float* final_trans, int* solves, int bs, int N, const int* nvalid, hipStream_t st, int* trace = nullptr,
                            const unsigned int* range_flag = nullptr);
+// score.hip: final_trans [bs][4][4] of every pair whose word in range_flag is set := NaN (the validation forward, which has no refinement launch)
+int launch_poison_flagged(float* final_trans, const unsigned int* range_flag, int bs, hipStream_t st);
 // linear.hip: encoder.layer0; range_flag != NULL: its first bs words are zeroed by this launch (the forward's first encoder launch)
 int launch_layer0(const float* corr_pos, int in_dim, const float* W0, const float* b0, float* feat, int M, unsigned int* range_flag, int bs,
                   hipStream_t st);

@@ -171,6 +171,12 @@ __global__ __launch_bounds__(512) void select_refine_kernel(const int* __restric
     refine_body(initial_trans, src, tgt, refine_thr, max_iters, final_trans, solves, NS, nvalid, trace, range_flag, b, Tb);
 }
 
+// validation forward (no refinement launch): the pose of every pair whose range word is set := NaN, as refine_body does it
+__global__ __launch_bounds__(256) void poison_flagged_kernel(float* __restrict__ final_trans, const unsigned int* __restrict__ range_flag, int bs) {
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    if (idx < bs * 16 && range_flag[idx >> 4] != 0u) final_trans[idx] = __builtin_nanf("");
+}
+
 }  // namespace pdsc
 
 namespace pdsc {
@@ -218,6 +224,12 @@ int launch_post_refinement(const float* initial_trans, const float* src, const f
     PDSC_REQUIRE(bs > 0 && N > 0 && max_iters >= 0, "pdsc_post_refinement: bs=%d N=%d iters=%d", bs, N, max_iters);
     hipLaunchKernelGGL(refine_kernel, dim3(bs), dim3(512), 0, st, initial_trans, src, tgt, threshold, max_iters, final_trans, solves, N, nvalid, trace, range_flag);
     return check_launch("pdsc_post_refinement");
+}
+
+int launch_poison_flagged(float* final_trans, const unsigned int* range_flag, int bs, hipStream_t st) {
+    PDSC_REQUIRE(final_trans && range_flag && bs > 0, "pdsc_forward_validation(range sentinel): null pointer or bs=%d", bs);
+    hipLaunchKernelGGL(poison_flagged_kernel, dim3(ceil_div(bs * 16, 256)), dim3(256), 0, st, final_trans, range_flag, bs);
+    return check_launch("pdsc_forward_validation(range sentinel)");
 }
 
 }  // namespace pdsc
