@@ -600,14 +600,19 @@ int pdsc_build_corr_pos(const float* src_keypts, const float* tgt_keypts, const 
  * entries by ascending index);  pred_trans = rigid_transform_3d(src_keypts, tgt_keypts, v * pred_labels).
  * corr_pos [bs][N][6] (the centred coordinates the reference passes as `corr`), src/tgt [bs][N][3];
  * pred_trans [bs][16], pred_labels [bs][N], leading_eig (optional) [bs][N]; workspace: pdsc_sm_workspace_bytes
- * (holds M: 4 N ld bytes per pair).  bs > 1 = independent pairs (the reference asserts bs == 1). */
+ * (holds M: 4 N ld bytes per pair).  bs > 1 = independent pairs (the reference asserts bs == 1).
+ * Non-finite coordinates behave as in the reference: an entry of M whose d is NaN is NaN (torch.clamp(min=0) keeps it), so
+ * leading_eig and pred_trans of that pair are NaN; the selection ranks NaN as the largest value (torch.sort's order), NaNs among
+ * themselves by ascending index -- an all-NaN vector labels the indices 0 .. num_top - 1.  Other pairs of the batch are untouched.
+ * 2 <= N <= 40 896 (see the forms below), 0 <= num_top <= N, num_iterations >= 1; else PDSC_ERR_ARG. */
 size_t pdsc_sm_workspace_bytes(int bs, int N);
 int pdsc_sm_baseline(const float* corr_pos, const float* src_keypts, const float* tgt_keypts, float inlier_threshold,
                      int num_top, int num_iterations, float* pred_trans, float* pred_labels, float* leading_eig,
                      void* workspace, size_t workspace_bytes, int bs, int N, void* stream);
 /* Two forms, bit-identical results (same arithmetic in the same order):
  *   streaming (form 1): the 4 N^2-byte matrix is written to the workspace once and streamed from HBM per iteration, the pairs of a
- *                       batch in one launch; any N up to 65 536;
+ *                       batch in one launch; any N up to 40 896 (v sits in the mat-vec's dynamic LDS, round_up(N, 64) floats of
+ *                       160 KiB - 64 bytes; a larger N returns PDSC_ERR_ARG before anything is enqueued);
  *   register-resident (form 2): ONE persistent launch per pair computes the matrix straight into the chip's vector registers
  *                       (100 MB at N = 5000 of the 128 MiB the 256 compute units hold) and runs every power iteration from there;
  *                       per iteration only y crosses the chip, behind a grid barrier.  N <= 5120, 20 rows per compute unit.
@@ -683,7 +688,9 @@ int pdsc_cal_confidence(const float* M, long long ld, const float* leading_eig, 
  * host) and the stats row of evaluation/test_3DMatch.py:90-98, per pair, without a device -> host copy:
  *   stats[b][0..8] = success (RE < re_thre && TE < te_thre), RE [deg], TE [cm], #gt inliers, gt inlier ratio,
  *                    #gt inliers among the predicted inliers, precision, recall, F1       (pred > 0 is "predicted inlier")
- * trans, gt_trans [bs][16]; pred_labels, gt_labels [bs][N]; stats [bs][9]. */
+ * trans, gt_trans [bs][16]; pred_labels, gt_labels [bs][N]; stats [bs][9].
+ * A NaN pose (what the range sentinel returns for a flagged pair) stays NaN: RE = acos(clamp((trace - 1) / 2, -1, 1)) with
+ * torch.clamp's NaN-keeping clamp, TE likewise, and success is 0 (both comparisons are strict and false for NaN). */
 int pdsc_eval_stats(const float* trans, const float* gt_trans, const float* pred_labels, const float* gt_labels,
                     float re_thre, float te_thre, float* stats, int bs, int N, void* stream);
 

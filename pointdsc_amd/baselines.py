@@ -17,7 +17,9 @@ def SM(corr: torch.Tensor, src_keypts: torch.Tensor, tgt_keypts: torch.Tensor, i
        num_iterations: int = 10, return_eig: bool = False, form: str = "auto"):
     """corr [N,6] (or [bs,N,6]) centred correspondence coordinates, src/tgt_keypts [bs,N,3] ->
     (pred_trans [bs,4,4], pred_labels [bs,N]) like the reference's SM(corr, src_keypts, tgt_keypts, args, top_ratio)
-    with ``args.inlier_threshold`` passed explicitly; bs > 1 = independent pairs.  ``form``: "streaming" (matrix in HBM, any N),
+    with ``args.inlier_threshold`` passed explicitly; bs > 1 = independent pairs.  A NaN distance difference (a NaN or
+    inf coordinate) makes that pair's eigenvector and pose NaN, as in the reference.
+    ``form``: "streaming" (matrix in HBM, N <= 40 896),
     "resident" (opt-in: the matrix stays in the chip's vector registers, N <= 5120; needs the GPU to itself -- cooperative launch,
     refused under graph capture) or "auto" (= "streaming", always); same bits either way."""
     forms = {"auto": 0, "streaming": 1, "resident": 2}

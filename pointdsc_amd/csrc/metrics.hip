@@ -34,7 +34,8 @@ __global__ __launch_bounds__(256) void eval_stats_kernel(const float* __restrict
     for (int i = 0; i < 3; ++i)
 #pragma unroll
         for (int j = 0; j < 3; ++j) tr = fmaf(T[i * 4 + j], G[i * 4 + j], tr);
-    const float c = fminf(fmaxf((tr - 1.0f) / 2.0f, -1.0f), 1.0f);
+    float c = fminf(fmaxf((tr - 1.0f) / 2.0f, -1.0f), 1.0f);
+    if (tr != tr) c = tr;                            // torch.clamp keeps a NaN (a flagged pair's pose), fminf / fmaxf drop it
     const float re = acosf(c) * 180.0f / 3.14159265358979323846f;
     const float dx = T[3] - G[3], dy = T[7] - G[7], dz = T[11] - G[11];
     const float te = sqrtf((dx * dx + dy * dy) + dz * dz) * 100.0f;

@@ -23,6 +23,9 @@ namespace pdsc {
 
 constexpr int SMV_ROWS = 16;             // rows per workgroup in the mat-vec (4 waves x 4 rows)
 constexpr int SMV_MAX_BLOCKS = 4096;     // partial-sum slots
+constexpr size_t SMV_MAX_LDS = 160 * 1024 - 64;      // dynamic LDS of sm_matvec_kernel: v, ld floats
+constexpr int SM_MAX_N = 40896;          // largest N whose ld = round_up(N, 64) floats fit SMV_MAX_LDS
+static_assert((size_t)SM_MAX_N * 4 <= SMV_MAX_LDS && (size_t)(SM_MAX_N + 64) * 4 > SMV_MAX_LDS && SM_MAX_N % 64 == 0, "SM_MAX_N");
 
 __global__ __launch_bounds__(256) void sm_matrix_kernel(const float* __restrict__ corr, float sigma2, float* __restrict__ M,
                                                         long long ld, int N) {
@@ -55,6 +58,7 @@ __global__ __launch_bounds__(256) void sm_matrix_kernel(const float* __restrict_
             const float dt = sqrtf((bx * bx + by * by) + bz * bz);
             const float d = ds - dt;
             float m = fmaxf(0.0f, 4.5f - ((d * d) / 2.0f) / sigma2);  // 4.5 - M**2 / 2 / sigma**2
+            if (d != d) m = d;                                        // torch.clamp(min=0) keeps a NaN, fmaxf drops it
             if (j4 + e == i || j4 + e >= N) m = 0.0f;
             out[e] = m;
         }
@@ -291,6 +295,7 @@ __global__ __launch_bounds__(256, 1) void sm_resident_kernel(SmResidentArgs a) {
                 const float dt = sqrtf((bx * bx + by * by) + bz * bz);
                 const float d = ds - dt;
                 float mm = fmaxf(0.0f, 4.5f - ((d * d) / 2.0f) / a.sigma2);
+                if (d != d) mm = d;                      // as sm_matrix_kernel: a NaN distance stays NaN
                 if (j4 + e == i || j4 + e >= N) mm = 0.0f;
                 m[r][g][e] = mm;
             });
@@ -387,7 +392,7 @@ __global__ __launch_bounds__(256, 1) void sm_resident_kernel(SmResidentArgs a) {
 }
 
 // final normalisation + selection mask: eig = y * scale; weights = eig * [rank(eig) < num_top]  (stable descending
-// rank by counting, ties by ascending index -- torch.argsort is unspecified there)
+// rank by counting, ties by ascending index -- torch.argsort is unspecified there; NaN entries rank first, equal among themselves)
 __global__ __launch_bounds__(256) void sm_finish_kernel(const float* __restrict__ y, const float* __restrict__ partial_in,
                                                         int n_partial_in, int num_top, float* __restrict__ eig,
                                                         float* __restrict__ labels, float* __restrict__ weights, int N) {
@@ -411,12 +416,14 @@ __global__ __launch_bounds__(256) void sm_finish_kernel(const float* __restrict_
     const float scale = 1.0f / (sqrtf(s) + 1e-6f);
     const float* yb = y + (size_t)b * N;
     const float ei = yb[i] * scale;
+    const bool ni = ei != ei;
     int cnt = 0;
     for (int j0 = 0; j0 < N; j0 += 64) {
         const int j = j0 + lane;
         if (j < N) {
             const float ej = yb[j] * scale;
-            cnt += (ej > ei) || (ej == ei && j < i);
+            const bool nj = ej != ej;                                // NaN ranks as the largest value, as torch.sort orders it
+            cnt += nj ? (!ni || j < i) : (!ni && ((ej > ei) || (ej == ei && j < i)));
         }
     }
     cnt = wave_sum(cnt);
@@ -578,7 +585,9 @@ static int sm_baseline_impl(const float* corr_pos, const float* src_keypts, cons
     PDSC_REQUIRE(corr_pos && src_keypts && tgt_keypts && pred_trans && pred_labels && workspace, "%s: null pointer", who);
     PDSC_REQUIRE(bs > 0 && N > 1 && num_top >= 0 && num_top <= N && num_iterations >= 1, "%s: bs=%d N=%d top=%d iters=%d", who,
                  bs, N, num_top, num_iterations);
-    PDSC_REQUIRE(ceil_div(N, SMV_ROWS) <= SMV_MAX_BLOCKS, "%s: N=%d too large (max %d)", who, N, SMV_ROWS * SMV_MAX_BLOCKS);
+    // v lives in the mat-vec's dynamic LDS (ld floats): past that the launch itself would fail
+    PDSC_REQUIRE(ceil_div(N, SMV_ROWS) <= SMV_MAX_BLOCKS && (size_t)pdsc_compat_ld(N) * sizeof(float) <= SMV_MAX_LDS,
+                 "%s: N=%d too large (max %d)", who, N, SM_MAX_N);
     if (workspace_bytes < pdsc_sm_workspace_bytes(bs, N)) {
         set_error("%s: workspace %zu < %zu bytes", who, workspace_bytes, pdsc_sm_workspace_bytes(bs, N));
         return PDSC_ERR_WORKSPACE;
@@ -658,7 +667,7 @@ static int sm_baseline_impl(const float* corr_pos, const float* src_keypts, cons
         // v0 = 1 (bit pattern of 1.0f)
         rc = launch_fill_u32((unsigned int*)va, 0x3f800000u, (size_t)bs * N, st);      // a kernel, like every other fill of the library (no hipMemsetAsync)
         if (rc != PDSC_OK) return rc;
-        rc = ensure_dynamic_lds(reinterpret_cast<const void*>(&sm_matvec_kernel), 160 * 1024 - 64, "pdsc_sm_baseline(dynamic LDS)");
+        rc = ensure_dynamic_lds(reinterpret_cast<const void*>(&sm_matvec_kernel), SMV_MAX_LDS, "pdsc_sm_baseline(dynamic LDS)");
         if (rc != PDSC_OK) return rc;
         float* pout = pa;
         vin = va; vout = vb; pin = nullptr;
@@ -704,7 +713,7 @@ extern "C" int pdsc_cal_confidence(const float* M, long long ld, const float* le
     PDSC_REQUIRE(M && leading_eig && confidence && workspace, "pdsc_cal_confidence: null pointer");
     PDSC_REQUIRE(bs > 0 && N > 0 && ld >= N && ld % 4 == 0, "pdsc_cal_confidence: bs=%d N=%d ld=%lld (ld >= N, multiple of 4)", bs, N, ld);
     PDSC_REQUIRE(method >= 0 && method <= 2 && num_iterations >= 0, "pdsc_cal_confidence: method=%d iterations=%d", method, num_iterations);
-    PDSC_REQUIRE(ceil_div(N, SMV_ROWS) <= SMV_MAX_BLOCKS && (size_t)ld * sizeof(float) <= 160 * 1024 - 64,
+    PDSC_REQUIRE(ceil_div(N, SMV_ROWS) <= SMV_MAX_BLOCKS && (size_t)ld * sizeof(float) <= SMV_MAX_LDS,
                  "pdsc_cal_confidence: N=%d too large", N);
     if (workspace_bytes < pdsc_cal_confidence_workspace_bytes(bs, N)) {
         set_error("pdsc_cal_confidence: workspace %zu < %zu bytes", workspace_bytes, pdsc_cal_confidence_workspace_bytes(bs, N));
@@ -716,7 +725,7 @@ extern "C" int pdsc_cal_confidence(const float* M, long long ld, const float* le
     float* part = x + (size_t)bs * N;
     float* lam = part + (size_t)bs * SMV_MAX_BLOCKS;
     {
-        const int rc_lds = ensure_dynamic_lds(reinterpret_cast<const void*>(&sm_matvec_kernel), 160 * 1024 - 64, "pdsc_cal_confidence(dynamic LDS)");
+        const int rc_lds = ensure_dynamic_lds(reinterpret_cast<const void*>(&sm_matvec_kernel), SMV_MAX_LDS, "pdsc_cal_confidence(dynamic LDS)");
         if (rc_lds != PDSC_OK) return rc_lds;
     }
     const int nblocks = ceil_div(N, SMV_ROWS);
