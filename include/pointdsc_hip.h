@@ -593,6 +593,47 @@ int pdsc_select_correspondences(const int* src2tgt, const int* tgt2src, int Ns, 
 int pdsc_build_corr_pos(const float* src_keypts, const float* tgt_keypts, const int* corr, const int* count,
                         float* corr_pos, float* src_sel, float* tgt_sel, void* stream);
 
+/* ---- correspondence construction for a batch of pairs over a pool of clouds ----------------
+ * replaces, for P pairs in one call, what Dataset.__getitem__ runs once per pair on the host: datasets/ThreeDMatch.py:283-290
+ * (distance, argmin, mutual check), :293-297 (the ground-truth label), :300-308 (gather, corr_pos = concat - column mean), the
+ * same lines of datasets/KITTI.py:80-105, and with metric 1 the matching of evaluation/test_3DLoMatch.py:45-48.
+ *
+ * POOL: desc [total][D] and keypts [total][3] fp32 hold the clouds one after the other.  TABLE [W][5] int32 on the device, one row
+ * per work item: { source offset, source count, target offset, target count, first source tile } -- offsets and counts in rows of
+ * the pool, counts >= 1; the first tile of item w is the sum of ceil(source count / 128) over the items before it, and total_tiles
+ * that sum over all of them.  mutual = 0: W = P, item p is pair p.  mutual = 1: W = 2 P, item 2p is pair p (source -> target) and
+ * item 2p + 1 the same pair with the roles swapped.  A cloud may serve any number of pairs, as source and as target, also of
+ * itself.  max_tgt = the largest target count of the table, cap = the row capacity of the outputs (LIMIT: cap >= the largest
+ * source count of the pairs; the caller builds the table from shapes it knows and answers for its consistency -- the call reads
+ * nothing back).
+ *
+ * OUTPUTS, pair p at row p * cap:  corr [P][cap][2] int32 = (i, nearest target of i) for the kept source rows i ascending (all of
+ * them, or with mutual = 1 those whose target's nearest source is i), num_corr [P] int32 = rows kept, written on the device;
+ * src_sel / tgt_sel [P][cap][3] the two endpoints, corr_pos [P][cap][6] = (src_sel | tgt_sel) - column mean over the num_corr rows
+ * (fp64 column sums, added in a fixed order).  Rows from num_corr[p] up to cap are ZERO in every output.
+ * TIES AND NaN are those of pdsc_match_descriptors / _ip: the distance (inner product) of a (source, target) row pair is the same
+ * bits as there (one tile body, csrc/match_tile.h), the first index wins among equal values, NaN orders first.
+ * LABEL (gt_trans != NULL, then gt_labels != NULL too): gt_trans [P][4][4] fp64 row-major, x = src_sel, y = tgt_sel taken to fp64,
+ *   gt_labels[p][c] = sqrt(sum_d (R_p x + t_p - y)_d^2) < inlier_threshold ? 1 : 0      fp64 throughout, as numpy promotes
+ * ThreeDMatch.py:295-297 (np.linalg.inv hands over a float64 gt_trans); gt_labels [P][cap] fp32.
+ * Launches only (key fill, matcher, select, gather, centre) on `stream`: nothing is read on the host or allocated.
+ * The target range is split over workgroups by pdsc_match_descriptors' rule applied to total_tiles (about 1024 workgroups, whole
+ * 128-row target tiles per split): a large batch runs with one split.  _ex: splits = 0 keeps that rule, 1 .. ceil(max_tgt / 128)
+ * overrides it (tests; the outputs do not depend on it).
+ * workspace: pdsc_corr_batch_workspace_bytes(P, total_tiles, cap) (0 for a non-positive argument).
+ * ERRORS, nothing enqueued: PDSC_ERR_ARG with the text "pdsc_build_correspondences_batch: ..." for a null pointer, P outside
+ * 1 .. 65535, D outside 1 .. 64, mutual or metric not 0 / 1, total_tiles < W, max_tgt < 1 or > 65535 * 128, cap < 1, gt_trans
+ * without gt_labels or the reverse, a NaN threshold, splits out of range; PDSC_ERR_WORKSPACE for a short workspace. */
+size_t pdsc_corr_batch_workspace_bytes(int P, int total_tiles, int cap);
+int pdsc_build_correspondences_batch(const float* desc, const float* keypts, const int* table, int P, int D, int mutual, int metric,
+                                     int total_tiles, int max_tgt, int cap, const double* gt_trans, double inlier_threshold,
+                                     float* corr_pos, float* src_sel, float* tgt_sel, int* corr, int* num_corr, float* gt_labels,
+                                     void* workspace, size_t workspace_bytes, void* stream);
+int pdsc_build_correspondences_batch_ex(const float* desc, const float* keypts, const int* table, int P, int D, int mutual, int metric,
+                                        int total_tiles, int max_tgt, int cap, const double* gt_trans, double inlier_threshold,
+                                        float* corr_pos, float* src_sel, float* tgt_sel, int* corr, int* num_corr, float* gt_labels,
+                                        void* workspace, size_t workspace_bytes, int splits, void* stream);
+
 /* ---- spectral-matching baseline: the N x N power iteration ------------------------------
  * replaces SM() of baseline_scripts/baseline_3DMatch.py:19-53:  M = max(0, 4.5 - d^2 / 2 / sigma^2) (zero diagonal,
  * d = |corr_i[0:3] - corr_j[0:3]| - |corr_i[3:6] - corr_j[3:6]|, sigma = inlier_threshold / 3);  v = 1, num_iterations x

@@ -20,6 +20,7 @@ Only what the path needs lives here:
   sharding.py  one-process-per-GPU sharding of pair batches + the single RCCL pose gather
   synthetic.py seeded synthetic correspondence sets / weights (tests + bench)
 """
+from .correspondences import CorrPool, build_correspondences_batch  # noqa: F401
 from .features import (compute_fpfh_feature, estimate_normals, extract_fpfh_features, fpfh_descriptors,  # noqa: F401
                        hybrid_neighbours, voxel_down_sample_with_normals)
 from .icp import icp_refine, registration_icp  # noqa: F401
@@ -35,4 +36,4 @@ __all__ = ["PointDSC", "icp_refine", "registration_icp", "information_matrix", "
            "fpfh_descriptors", "voxel_down_sample_with_normals", "extract_fpfh_features", "pose_graph_nodes", "global_optimization",
            "ClassificationLoss", "SpectralMatchingLoss", "TransformationLoss", "NonLocalBlock", "sc_attention",
            "TrainablePointDSC", "train_forward", "feature_similarity", "seed_solve", "conv_bn_relu",
-           "linear_rows", "qkv_projection", "classification_head"]
+           "linear_rows", "qkv_projection", "classification_head", "build_correspondences_batch", "CorrPool"]

@@ -31,7 +31,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .correspondences import build_correspondences
+from .correspondences import CorrPool, build_correspondences, build_correspondences_batch
 from .features import extract_fpfh_features, fpfh_descriptors
 from .icp import icp_refine
 from .multiway import local_refinement, loop_closure_edge
@@ -164,7 +164,7 @@ class BaselineModel:
 
 def eval_scene(model, pairs: Iterable[Dict[str, np.ndarray]], scene_ind: int = 0, re_thre: float = 15.0, te_thre: float = 30.0,
                inlier_threshold: float = 0.10, use_mutual: bool = False, device: str = "cuda:0", batch_size: int = 1,
-               use_icp: bool = False, icp_distance: float = 0.10) -> np.ndarray:
+               use_icp: bool = False, icp_distance: float = 0.10, corr_batch: bool = False) -> np.ndarray:
     """`pairs`: dicts with src_pts [ns,3], tgt_pts [nt,3], src_desc [ns,D], tgt_desc [nt,D], gt_trans [4,4] (numpy).
     Returns the [num_pair, 12] stats array of the reference's eval_3DMatch_scene.
     batch_size > 1 (r03): the correspondence sets of `batch_size` consecutive pairs -- every pair has its own N, as in the
@@ -172,7 +172,10 @@ def eval_scene(model, pairs: Iterable[Dict[str, np.ndarray]], scene_ind: int = 0
     per-pair tensors); model / data time are then the batch's time divided by its pairs.
     use_icp (test_3DMatch.py:79-80): the predicted poses are refined by point-to-point ICP of the correspondence endpoints
     (benchmark_utils.icp_refine, max_correspondence_distance = icp_distance) -- the group's pairs in one ragged device call,
-    inside the model time as in the reference; the stats rows then use the refined poses."""
+    inside the model time as in the reference; the stats rows then use the refined poses.
+    corr_batch (f-19; with batch_size > 1): the group's correspondences and ground-truth labels come from one
+    `build_correspondences_batch` call (labels in fp64, datasets/ThreeDMatch.py:293-297, where the per-pair path uses
+    `gt_labels_from_trans`' fp32); data time is then the group's time divided by its pairs."""
     rows: List[np.ndarray] = []
     dev = torch.device(device)
     g = lambda a: a.to(dev) if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
@@ -201,8 +204,32 @@ def eval_scene(model, pairs: Iterable[Dict[str, np.ndarray]], scene_ind: int = 0
             row[9], row[10], row[11] = model_time, x["data_time"], scene_ind
             rows.append(row)
 
+    def build_group(raw):
+        """corr_batch: the correspondences and labels of the group's pairs from ONE batched call (pool = the pairs' clouds in turn)."""
+        t0 = time.perf_counter()
+        desc = [g(x[k]) for x in raw for k in ("src_desc", "tgt_desc")]
+        pts = [g(x[k]) for x in raw for k in ("src_pts", "tgt_pts")]
+        gt64 = torch.stack([torch.as_tensor(np.asarray(x["gt_trans"].cpu() if torch.is_tensor(x["gt_trans"]) else x["gt_trans"],
+                                                       dtype=np.float64)) for x in raw])
+        c = build_correspondences_batch(desc, pts, [(2 * i, 2 * i + 1) for i in range(len(raw))], use_mutual=use_mutual,
+                                        gt_trans=gt64, inlier_threshold=inlier_threshold)
+        counts = c["num_corr"].tolist() if use_mutual else c["num_corr_host"]
+        torch.cuda.synchronize(dev)
+        data_time = (time.perf_counter() - t0) / len(raw)
+        return [{"corr": {k: c[k][i:i + 1, :n] for k in ("corr_pos", "src_keypts", "tgt_keypts")}, "gt_trans": g(x["gt_trans"]).float(),
+                 "gt_labels": c["gt_labels"][i:i + 1, :n], "data_time": data_time} for i, (x, n) in enumerate(zip(raw, counts))]
+
     with torch.no_grad():
         group = []
+        if corr_batch and batch_size > 1:
+            for pair in pairs:
+                group.append(pair)
+                if len(group) >= batch_size:
+                    flush(build_group(group))
+                    group = []
+            if group:
+                flush(build_group(group))
+            return np.stack(rows) if rows else np.zeros((0, 12))
         for pair in pairs:
             t0 = time.perf_counter()
             corr = build_correspondences(g(pair["src_desc"]), g(pair["tgt_desc"]), g(pair["src_pts"]), g(pair["tgt_pts"]),
@@ -307,47 +334,75 @@ def demo_views(cloud: np.ndarray, num_views: int, dim: int = 33, cell: float = 0
     return views
 
 
-def multiway_edges(model, views: List[Dict[str, np.ndarray]], use_mutual: bool = False, device: str = "cuda:0"):
+def multiway_edges(model, views: List[Dict[str, np.ndarray]], use_mutual: bool = False, device: str = "cuda:0", batch_pairs: int = 1):
     """The pairwise-registration loop of the multiway driver (multiway/test_multi_ate.py:98-157) over `views` (dicts with pts [n,3],
     desc [n,D] and, for every view but the last, odometry [4,4]; `demo_views` builds them): every pair s < t in the driver's order.
       t == s + 1 (odometry case, :117-135): `local_refinement` of the full clouds from views[s]['odometry'] -> a certain edge;
       otherwise (:136-154): match -> `model(data)` -> `loop_closure_edge`; a pair the gate drops is skipped, the others are
       uncertain edges.
     Everything up to the gate stays on the device; the gates of all pairs are read back once, at the end.
+    batch_pairs > 1: the loop closures run `batch_pairs` at a time through the batched correspondence construction and one ragged
+    forward per group (`_pairwise_registration`); the same edges in the same order.
     Returns the edges as the driver would append them: tuples (s, t, T [4,4] float64 numpy, info [6,6] float64 numpy, uncertain)."""
     dev = torch.device(device)
-    found, _ = _pairwise_registration(model, views, use_mutual, dev)
+    found, _ = _pairwise_registration(model, views, use_mutual, dev, batch_pairs)
     keep = torch.stack([f[4] if f[4] is not None else torch.ones((), dtype=torch.bool, device=dev) for f in found]).cpu().numpy()
     return [(s, t, T.double().cpu().numpy(), info.cpu().numpy(), gate is not None)
             for (s, t, T, info, gate), k in zip(found, keep) if k]
 
 
-def _pairwise_registration(model, views, use_mutual: bool, dev):
+def _pairwise_registration(model, views, use_mutual: bool, dev, batch_pairs: int = 1):
     """The pair loop of `multiway_edges`, everything left on the device: -> ([(s, t, T [4,4] fp32, info [6,6] fp64, gate or None)] in
-    the driver's order -- gate: the overlap gate's 0-d bool tensor of a loop closure, None for an odometry edge --, the views' points)."""
+    the driver's order -- gate: the overlap gate's 0-d bool tensor of a loop closure, None for an odometry edge --, the views' points).
+    batch_pairs > 1 (f-19): the loop-closure candidates are taken `batch_pairs` at a time, in the driver's order: one
+    `build_correspondences_batch` over the views' pool, one forward with `num_corr`, one `loop_closure_edge` per group.  The
+    group's counts are known from the shapes; with the mutual check they are read once per group."""
     g = lambda a: a.to(dev).float() if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)  # noqa: E731
     pts = [g(v["pts"]) for v in views]
     desc = [g(v["desc"]) for v in views]
     found = []
+    pool = CorrPool(desc, pts) if batch_pairs > 1 else None
+    group = []                                       # (position in found, s, t) of the candidates waiting for their group
+
+    def flush():
+        if not group:
+            return
+        c = build_correspondences_batch(pool, None, [(s, t) for _, s, t in group], use_mutual=use_mutual)
+        counts = c["num_corr"].tolist() if use_mutual else c["num_corr_host"]
+        res = model({"corr_pos": c["corr_pos"], "src_keypts": c["src_keypts"], "tgt_keypts": c["tgt_keypts"], "num_corr": counts,
+                     "testing": True})
+        edge = loop_closure_edge([c["src_keypts"][i, :n] for i, n in enumerate(counts)],
+                                 [c["tgt_keypts"][i, :n] for i, n in enumerate(counts)], res["final_trans"])
+        for i, (pos, s, t) in enumerate(group):
+            found[pos] = (s, t, res["final_trans"][i], edge["information"][i], edge["keep"][i])
+        group.clear()
+
     with torch.no_grad():
         for s in range(len(views)):
             for t in range(s + 1, len(views)):
                 if t == s + 1:
                     T, info = local_refinement(pts[s][None], pts[t][None], g(views[s]["odometry"])[None])
                     found.append((s, t, T[0], info[0], None))
+                elif batch_pairs > 1:
+                    group.append((len(found), s, t))
+                    found.append(None)
+                    if len(group) >= batch_pairs:
+                        flush()
                 else:
                     c = build_correspondences(desc[s], desc[t], pts[s], pts[t], use_mutual=use_mutual)
                     res = model({"corr_pos": c["corr_pos"], "src_keypts": c["src_keypts"], "tgt_keypts": c["tgt_keypts"], "testing": True})
                     edge = loop_closure_edge(c["src_keypts"], c["tgt_keypts"], res["final_trans"])
                     found.append((s, t, res["final_trans"][0], edge["information"][0], edge["keep"][0]))
+        flush()
     return found, pts
 
 
 def multiway_trajectory(model, views: List[Dict[str, np.ndarray]], use_icp: bool = False, use_mutual: bool = False,
-                        device: str = "cuda:0", return_graph: bool = False) -> Dict[str, object]:
+                        device: str = "cuda:0", return_graph: bool = False, batch_pairs: int = 1) -> Dict[str, object]:
     """The driver's `eval_redwood_scene` plus its ATE (multiway/test_multi_ate.py:86-227, :262-270) over `views` (as `multiway_edges`
     takes them; `pose` [4,4] is the ground truth: p_view = pose p_scene):
-      1. the edges of `multiway_edges`, with the overlap gates kept on the device and handed to the optimiser as its edge mask;
+      1. the edges of `multiway_edges` (`batch_pairs` as there), with the overlap gates kept on the device and handed to the optimiser
+         as its edge mask;
       2. the node chain over the odometry edges (:129-130);
       3. `global_optimization` (:166-174);
       4. use_icp (:188-224): `multi_scale_icp` of every edge from its transformation on the full clouds (the pruned ones too: which
@@ -360,7 +415,7 @@ def multiway_trajectory(model, views: List[Dict[str, np.ndarray]], use_icp: bool
     from .multiway import align, global_optimization, multi_scale_icp, pose_graph_nodes
     dev = torch.device(device)
     F = len(views)
-    found, pts = _pairwise_registration(model, views, use_mutual, dev)
+    found, pts = _pairwise_registration(model, views, use_mutual, dev, batch_pairs)
     with torch.no_grad():
         edges = {"source": torch.tensor([f[0] for f in found], dtype=torch.int32).to(dev),
                  "target": torch.tensor([f[1] for f in found], dtype=torch.int32).to(dev),

@@ -3,7 +3,7 @@
 
     python tools/eval_harness.py [--pcd1 a.ply] [--num-pairs 8] [--descriptor {standin,fpfh}] [--snapshot model_best.pkl] [--use-icp]
     python tools/eval_harness.py --pcd1 a.ply --pcd2 b.ply --descriptor fpfh [--use-icp]
-    python tools/eval_harness.py --multiway [--num-views 5] [--descriptor {standin,fpfh}]
+    python tools/eval_harness.py --multiway [--num-views 5] [--descriptor {standin,fpfh}] [--batch-pairs 32] [--time 10]
     python tools/eval_harness.py --multiway --posegraph [--use-icp] [--num-views 5]
     python tools/eval_harness.py --baseline {SM,PMC} [--num-pairs 8]
 
@@ -27,6 +27,7 @@ Registration Recall on 3DMatch-FCGF itself needs the released weights and the da
 import argparse
 import json
 import sys
+import time
 from pathlib import Path
 
 import numpy as np
@@ -41,7 +42,17 @@ def multiway(model, cloud, a):
     views = harness.demo_views(cloud, a.num_views, corrupt=min(a.outlier_share, 0.4), descriptor=a.descriptor, voxel=a.voxel)
     if a.posegraph:
         return posegraph(model, views, a)
-    edges = harness.multiway_edges(model, views, use_mutual=a.mutual)
+    edges = harness.multiway_edges(model, views, use_mutual=a.mutual, batch_pairs=a.batch_pairs)
+    if a.time > 0:                            # the pass above was the warm-up
+        ms = []
+        for _ in range(a.time):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            harness.multiway_edges(model, views, use_mutual=a.mutual, batch_pairs=a.batch_pairs)
+            torch.cuda.synchronize()
+            ms.append((time.perf_counter() - t0) * 1e3)
+        print(f"multiway_edges views={a.num_views} batch_pairs={a.batch_pairs} mutual={a.mutual}: median {np.median(ms):.2f} ms "
+              f"(min {min(ms):.2f} max {max(ms):.2f}, {a.time} rounds)")
     if a.json:
         print(json.dumps({"edges": [{"source": s, "target": t, "transformation": T.tolist(), "information": info.tolist(),
                                      "uncertain": bool(u)} for s, t, T, info, u in edges]}))
@@ -58,7 +69,7 @@ def multiway(model, cloud, a):
 
 def posegraph(model, views, a):
     """multiway/test_multi_ate.py:164, :175 (:215, :225 with --use-icp) and :268."""
-    res = harness.multiway_trajectory(model, views, use_icp=a.use_icp, use_mutual=a.mutual)
+    res = harness.multiway_trajectory(model, views, use_icp=a.use_icp, use_mutual=a.mutual, batch_pairs=a.batch_pairs)
     records = [res["first_record"].cpu().numpy()] if a.use_icp else []
     records.append(res["record"].cpu().numpy())
     if a.json:
@@ -172,6 +183,10 @@ def main():
     ap.add_argument("--icp-distance", type=float, default=0.10, help="max_correspondence_distance of the ICP post-step")
     ap.add_argument("--multiway", action="store_true", help="the multiway driver's edge loop over --num-views views (test_multi_ate.py:98-157)")
     ap.add_argument("--num-views", type=int, default=5)
+    ap.add_argument("--batch-pairs", type=int, default=1, help="with --multiway: loop-closure candidates per batched correspondence "
+                    "construction and ragged forward (harness.multiway_edges batch_pairs); 1 = one pair per call")
+    ap.add_argument("--time", type=int, default=0, help="with --multiway: repeat the edge loop this many times after the first pass and "
+                    "print the median wall time")
     ap.add_argument("--posegraph", action="store_true", help="with --multiway: node chain, pose-graph optimisation on the device and the ATE "
                     "(test_multi_ate.py:159-227, :268); --use-icp adds the ICP refinement of the edges and the second optimisation")
     ap.add_argument("--baseline", choices=harness.BaselineModel.METHODS, default=None,
