@@ -756,6 +756,58 @@ int pdsc_icp_refine(const float* src, const float* tgt, const float* init_trans,
                     double* out_trans_f64, double* fitness, double* inlier_rmse, int* num_corr, int* iterations, void* workspace,
                     size_t workspace_bytes, int bs, int Ns, int Nt, void* stream);
 
+/* ---- correspondence RANSAC ---------------------------------------------------------------------
+ * replaces open3d registration_ransac_based_on_correspondence as baseline_scripts/baseline_3DMatch.py:80-98 (--method RANSAC:
+ * ransac_n 4, 1000 iterations, all correspondences) and evaluation/test_3DMatch.py:59-77, test_KITTI.py:59-77 (--solver RANSAC:
+ * ransac_n 3, 5000 iterations, the correspondences the model labelled inliers) call it.  The contract is this project's, modelled
+ * on open3d 0.9 RegistrationRANSACBasedOnCorrespondence as recalled; what cannot be checked without open3d is a named rule.
+ * Per pair b: src, tgt [N][3] fp32 (row i = correspondence i; widened exactly); the candidate list L = the ascending indices
+ * i < N_b with mask[i] > 0 (mask NULL: all of them), M = |L|; r = the distance threshold; I = max_iteration hypotheses.
+ *   DRAW_RULE      position j < ransac_n of iteration i uses the counter c = ((pair_offset + b) * I + i) * 8 + j (64-bit, wrapping):
+ *                  z = splitmix64's output for the state seed + (c + 1) * 0x9E3779B97F4A7C15, i.e. z ^= z >> 30,
+ *                  z *= 0xBF58476D1CE4E5B9, z ^= z >> 27, z *= 0x94D049BB133111EB, z ^= z >> 31; position in L = (hi32(z) * M) >> 32.
+ *                  Draws are with replacement (as 0.9's loop): a sample may repeat an index.  pair_offset makes a pair's draws
+ *                  independent of how a driver groups pairs.  samples != NULL ([bs][I][ransac_n] int32 positions into L) replaces
+ *                  the draws; a position < 0 or >= M makes that hypothesis invalid.
+ *   hypothesis     Eigen's umeyama without scaling on the sample, fp64: means = sum * (1 / n), Sigma = (1 / n) sum (q - mB)(p - mA)^T,
+ *                  pose from the library's one fp64 Kabsch entry (the one pdsc_icp_refine uses; its rank <= 1 fallback covers repeated
+ *                  indices).  A non-finite pose is an invalid hypothesis: NaN pose, count 0, sumsq 0, never wins.
+ *   SCORE_RULE     over every l in L (not the sample only): d2 = |R src_l + t - tgt_l|^2 in fp64; l is an inlier iff d2 < r * r, r * r
+ *                  in fp64 (open3d compares sqrt(d2) < r: the two differ at the last ulp at most).  count = #inliers, sumsq = sum of
+ *                  d2 over the inliers, DEFINED as the partial sums of the consecutive PDSC_RANSAC_CHUNK-entry chunks of L, each in list
+ *                  order, added in ascending chunk order -- so that a pair's bits do not depend on the batch, the tiling or the run.
+ *                  A NaN or inf coordinate compares false: never an inlier; a sample that contains one is an invalid hypothesis.
+ *   SELECT_RULE    open3d's sequential update (fitness greater, or equal and rmse smaller) as an order: the largest count, then the
+ *                  smallest sumsq (compared on sumsq, not on a rounded rmse), then the lowest iteration; count 0 never wins.
+ *   NO_REFIT_RULE  the winner's pose is returned as solved from its sample: no refit on the inlier set (0.9 has none, as recalled).
+ * Early outs, evaluated on the device where M lives: M < ransac_n, r <= 0 or r NaN: nothing wins.
+ * Outputs: trans [bs][16] fp32 (the winner's pose rounded once; identity if nothing won), labels [bs][N] fp32 (1 at the winner's
+ * inliers, all inside L; 0 elsewhere, padding rows included; labels sum to the winner's count exactly), fitness = count / M and
+ * inlier_rmse = sqrt(sumsq / count) [bs] double (0 if nothing won), best_iter [bs] int32 (-1 if nothing won), num_candidates = M.
+ * Optional (NULL = not wanted), the full hypothesis table: hyp_trans [bs][I][12] double (rows of R | t), hyp_count [bs][I] int32,
+ * hyp_sumsq [bs][I] double.  counts [bs] int32 (DEVICE; NULL = every pair has N rows; rows beyond a pair's count are padding).
+ * Four launches, no allocation, no host synchronisation (graph-capturable).  Limits: 1 <= bs <= PDSC_RANSAC_MAX_PAIRS,
+ * 1 <= N <= PDSC_RANSAC_MAX_N, 1 <= max_iteration <= PDSC_RANSAC_MAX_ITERATIONS, 3 <= ransac_n <= 8; anything else, or a null pointer,
+ * returns PDSC_ERR_ARG, a short workspace PDSC_ERR_WORKSPACE, with nothing enqueued.  workspace: pdsc_ransac_workspace_bytes(bs, N,
+ * max_iteration) (0 for unsupported sizes). */
+#define PDSC_RANSAC_CHUNK 512
+#define PDSC_RANSAC_MAX_PAIRS 65535
+#define PDSC_RANSAC_MAX_N (1 << 22)
+#define PDSC_RANSAC_MAX_ITERATIONS (1 << 22)
+size_t pdsc_ransac_workspace_bytes(int bs, int N, int max_iteration);
+int pdsc_ransac_correspondence(const float* src, const float* tgt, const int* counts, const float* mask, const int* samples, double r,
+                               int ransac_n, int max_iteration, unsigned long long seed, long long pair_offset, float* trans,
+                               float* labels, double* fitness, double* inlier_rmse, int* best_iter, int* num_candidates,
+                               double* hyp_trans, int* hyp_count, double* hyp_sumsq, void* workspace, size_t workspace_bytes, int bs,
+                               int N, void* stream);
+/* The same call for tools/ransac_bench.py: stage_ms [4] (HOST) receives the milliseconds of compact | hypothesise | score | select
+ * between events on the stream.  This entry synchronises the host and cannot be captured. */
+int pdsc_ransac_correspondence_stages(const float* src, const float* tgt, const int* counts, const float* mask, const int* samples,
+                                      double r, int ransac_n, int max_iteration, unsigned long long seed, long long pair_offset,
+                                      float* trans, float* labels, double* fitness, double* inlier_rmse, int* best_iter,
+                                      int* num_candidates, double* hyp_trans, int* hyp_count, double* hyp_sumsq, void* workspace,
+                                      size_t workspace_bytes, int bs, int N, float* stage_ms, void* stream);
+
 /* ---- multiway edge step ------------------------------------------------------------------------
  * pdsc_information_matrix replaces open3d registration.get_information_matrix_from_point_clouds
  * (GetInformationMatrixFromPointClouds) as multiway/test_multi_ate.py:69-72 and :141-146 call it, per pair, fp64 throughout:

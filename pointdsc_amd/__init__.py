@@ -7,6 +7,7 @@ Only what the path needs lives here:
   model.py     ``PointDSC`` nn.Module: reference constructor, state_dict layout and forward contract
   ops.py       stage-level tensor wrappers (``rigid_transform_3d``, ``knn`` ...) over the C-ABI
   icp.py       the evaluation's optional ICP post-step (``icp_refine``, ``registration_icp``) on the device
+  ransac.py    correspondence RANSAC (``ransac_correspondence``: the baseline's and the evaluation's ``--solver RANSAC``) on the device
   features.py  FPFH descriptors of a down-sampled cloud (neighbour lists, normals, SPFH, FPFH) on the device
   losses.py   the reference's training / validation losses (classification, spectral matching, transformation) on the device,
                with their gradients
@@ -24,6 +25,7 @@ from .correspondences import CorrPool, build_correspondences_batch  # noqa: F401
 from .features import (compute_fpfh_feature, estimate_normals, extract_fpfh_features, fpfh_descriptors,  # noqa: F401
                        hybrid_neighbours, voxel_down_sample_with_normals)
 from .icp import icp_refine, registration_icp  # noqa: F401
+from .ransac import ransac_correspondence  # noqa: F401
 from .losses import ClassificationLoss, SpectralMatchingLoss, TransformationLoss  # noqa: F401
 from .model import PointDSC  # noqa: F401
 from .training import (NonLocalBlock, TrainablePointDSC, classification_head, conv_bn_relu, feature_similarity,  # noqa: F401
@@ -36,4 +38,4 @@ __all__ = ["PointDSC", "icp_refine", "registration_icp", "information_matrix", "
            "fpfh_descriptors", "voxel_down_sample_with_normals", "extract_fpfh_features", "pose_graph_nodes", "global_optimization",
            "ClassificationLoss", "SpectralMatchingLoss", "TransformationLoss", "NonLocalBlock", "sc_attention",
            "TrainablePointDSC", "train_forward", "feature_similarity", "seed_solve", "conv_bn_relu",
-           "linear_rows", "qkv_projection", "classification_head", "build_correspondences_batch", "CorrPool"]
+           "linear_rows", "qkv_projection", "classification_head", "build_correspondences_batch", "CorrPool", "ransac_correspondence"]

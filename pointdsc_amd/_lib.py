@@ -163,6 +163,10 @@ SIGNATURES = {
     "pdsc_icp_workspace_bytes": (_sz, [_i, _i, _i]),
     "pdsc_icp_refine": (_i, [_vp, _vp, _vp, _vp, _vp, C.c_double, C.c_double, C.c_double, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                              _sz, _i, _i, _i, _vp]),
+    "pdsc_ransac_workspace_bytes": (_sz, [_i, _i, _i]),
+    "pdsc_ransac_correspondence": (_i, [_vp] * 5 + [C.c_double, _i, _i, C.c_ulonglong, _ll] + [_vp] * 10 + [_sz, _i, _i, _vp]),
+    "pdsc_ransac_correspondence_stages": (_i, [_vp] * 5 + [C.c_double, _i, _i, C.c_ulonglong, _ll] + [_vp] * 10 +
+                                          [_sz, _i, _i, C.POINTER(C.c_float), _vp]),
     "pdsc_information_workspace_bytes": (_sz, [_i, _i, _i]),
     "pdsc_information_matrix": (_i, [_vp, _vp, _vp, _vp, _vp, C.c_double, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _vp]),
     "pdsc_voxel_keys": (_i, [_vp, _vp, C.c_double, _vp, _i, _i, _vp]),

@@ -2,7 +2,9 @@
 
 ``SM`` mirrors ``baseline_scripts/baseline_3DMatch.py:19-53`` (spectral matching: N x N compatibility matrix + 10 power
 iterations + top-10 % selection + weighted Procrustes) with the reference's argument meaning; the arithmetic runs in
-``csrc/spectral.hip`` (matrix written once, one HBM-bound mat-vec launch per iteration).  GPU only.
+``csrc/spectral.hip`` (matrix written once, one HBM-bound mat-vec launch per iteration).  ``PMC`` (:56-77) is the exact maximum
+clique of ``csrc/pmc.hip``; ``RANSAC`` (:80-98) is correspondence RANSAC under the project's own contract (``ransac.py``,
+``csrc/ransac.hip``).  GPU only.
 """
 from __future__ import annotations
 
@@ -153,3 +155,16 @@ def PMC(corr: torch.Tensor, src_keypts: torch.Tensor, tgt_keypts: torch.Tensor, 
     if return_info:
         return r["pred_trans"], r["pred_labels"], r["clique_size"], r["proven"]
     return r["pred_trans"], r["pred_labels"]
+
+
+def RANSAC(corr, src_keypts, tgt_keypts, inlier_threshold: float, max_iteration: int = 1000, max_validation: int = 1000, seed: int = 0,
+           pair_offset: int = 0):
+    """The reference's RANSAC(corr, src_keypts, tgt_keypts, args) (baseline_3DMatch.py:80-98: open3d
+    registration_ransac_based_on_correspondence over all N correspondences, ransac_n = 4, RANSACConvergenceCriteria(max_iteration,
+    max_validation)) with ``args.inlier_threshold`` passed explicitly: src/tgt_keypts [bs,N,3] (or lists of per-pair [N,3] tensors)
+    -> (pred_trans [bs,4,4], pred_labels [bs,N]); ``corr`` is accepted and unused, as in the reference.  The hypotheses number
+    min(max_iteration, max_validation) (:90); ``seed`` and ``pair_offset`` fix the draws (``ransac.ransac_correspondence`` has the
+    contract: it does not reproduce open3d's random draws).  GPU only."""
+    from .ransac import ransac_correspondence
+    return ransac_correspondence(src_keypts, tgt_keypts, inlier_threshold, ransac_n=4, max_iteration=max_iteration,
+                                 max_validation=max_validation, seed=seed, pair_offset=pair_offset)

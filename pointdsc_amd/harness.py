@@ -8,7 +8,7 @@ Replicates, without open3d / easydict (absent here):
   * ``demo_registration.py:37-44,101-117``  cloud -> voxel down-sampling -> descriptors -> nearest-neighbour matching
     -> ``corr_pos`` -> ``model(data)``.
 The arithmetic on the path runs in libpointdsc_hip.so (correspondence construction f-2, forward a-*, stats row f-4, the
-optional ICP post-step f-5, the multiway driver's edge step f-6: ``multiway_edges``, its pose-graph optimisation and ATE f-8:
+optional ICP post-step f-5, the RANSAC solver f-21, the multiway driver's edge step f-6: ``multiway_edges``, its pose-graph optimisation and ATE f-8:
 ``multiway_trajectory``);
 this module is host plumbing: PLY reading (binary little-endian float xyz), open3d-style voxel
 down-sampling in numpy, the pair loop, timers (``utils/timer.py`` semantics: wall clock, here with a device
@@ -35,6 +35,7 @@ from .correspondences import CorrPool, build_correspondences, build_corresponden
 from .features import extract_fpfh_features, fpfh_descriptors
 from .icp import icp_refine
 from .multiway import local_refinement, loop_closure_edge
+from .ransac import ransac_correspondence
 
 STATS_NAMES = ("success", "RE_deg", "TE_cm", "input_inliers", "input_inlier_ratio", "output_true_positives",
                "precision", "recall", "f1", "model_time_s", "data_time_s", "scene_ind")
@@ -162,9 +163,31 @@ class BaselineModel:
         return {"final_trans": torch.cat([o[0] for o in out]), "final_labels": [o[1][0] for o in out]}
 
 
+class RansacModel:
+    """baseline_scripts/baseline_3DMatch.py ``--method RANSAC`` (:80-98, open3d registration_ransac_based_on_correspondence over all
+    correspondences of a pair) behind the calling convention of ``BaselineModel.__call__``: data dict with src_keypts / tgt_keypts
+    ([B,N,3] tensors, or lists of per-pair [N,3] tensors) -> {"final_trans": [B,4,4], "final_labels": per-pair [N] rows}.  A ragged
+    group is ONE batched device call (``ransac.ransac_correspondence``), not a loop.  ``data["pair_offset"]`` (optional; eval_scene
+    passes the index of the group's first pair) keeps a pair's draws independent of the grouping."""
+    wants_pair_offset = True
+
+    def __init__(self, inlier_threshold: float = 0.10, ransac_n: int = 4, max_iteration: int = 1000, seed: int = 0):
+        self.inlier_threshold, self.ransac_n = float(inlier_threshold), int(ransac_n)
+        self.max_iteration, self.seed = int(max_iteration), int(seed)
+
+    def __call__(self, data):
+        trans, labels = ransac_correspondence(data["src_keypts"], data["tgt_keypts"], self.inlier_threshold, ransac_n=self.ransac_n,
+                                              max_iteration=self.max_iteration, seed=self.seed,
+                                              pair_offset=int(data.get("pair_offset", 0)))
+        return {"final_trans": trans, "final_labels": labels}
+
+
+SOLVERS = ("SVD", "RANSAC")
+
+
 def eval_scene(model, pairs: Iterable[Dict[str, np.ndarray]], scene_ind: int = 0, re_thre: float = 15.0, te_thre: float = 30.0,
                inlier_threshold: float = 0.10, use_mutual: bool = False, device: str = "cuda:0", batch_size: int = 1,
-               use_icp: bool = False, icp_distance: float = 0.10, corr_batch: bool = False) -> np.ndarray:
+               use_icp: bool = False, icp_distance: float = 0.10, corr_batch: bool = False, solver: str = "SVD") -> np.ndarray:
     """`pairs`: dicts with src_pts [ns,3], tgt_pts [nt,3], src_desc [ns,D], tgt_desc [nt,D], gt_trans [4,4] (numpy).
     Returns the [num_pair, 12] stats array of the reference's eval_3DMatch_scene.
     batch_size > 1 (r03): the correspondence sets of `batch_size` consecutive pairs -- every pair has its own N, as in the
@@ -175,7 +198,13 @@ def eval_scene(model, pairs: Iterable[Dict[str, np.ndarray]], scene_ind: int = 0
     inside the model time as in the reference; the stats rows then use the refined poses.
     corr_batch (f-19; with batch_size > 1): the group's correspondences and ground-truth labels come from one
     `build_correspondences_batch` call (labels in fp64, datasets/ThreeDMatch.py:293-297, where the per-pair path uses
-    `gt_labels_from_trans`' fp32); data time is then the group's time divided by its pairs."""
+    `gt_labels_from_trans`' fp32); data time is then the group's time divided by its pairs.
+    solver (test_3DMatch.py:59-77 `--solver`): "SVD" keeps the model's pose; "RANSAC" replaces the group's poses and labels by
+    `ransac_correspondence` (ransac_n 3, 5000 iterations) over the correspondences the model labelled as inliers -- one ragged device
+    call after the forward and before use_icp, inside the model time, with no host read.  Its draws are numbered by the pair's index
+    in the scene, so batch_size does not change a pair's result."""
+    if solver not in SOLVERS:
+        raise ValueError(f"solver must be one of {SOLVERS}, got {solver!r}")
     rows: List[np.ndarray] = []
     dev = torch.device(device)
     g = lambda a: a.to(dev) if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
@@ -184,14 +213,21 @@ def eval_scene(model, pairs: Iterable[Dict[str, np.ndarray]], scene_ind: int = 0
         if not group:
             return
         t0 = time.perf_counter()
+        first = len(rows)                                                  # index of the group's first pair in the scene
+        extra = {"pair_offset": first} if getattr(model, "wants_pair_offset", False) else {}
         if len(group) == 1:
             c = group[0]["corr"]
-            res = model({"corr_pos": c["corr_pos"], "src_keypts": c["src_keypts"], "tgt_keypts": c["tgt_keypts"], "testing": True})   # test_3DMatch.py:53
+            res = model({"corr_pos": c["corr_pos"], "src_keypts": c["src_keypts"], "tgt_keypts": c["tgt_keypts"], "testing": True,
+                         **extra})                                                                         # test_3DMatch.py:53
             trans, labels = res["final_trans"], [res["final_labels"][0]]
         else:
             res = model({"corr_pos": [x["corr"]["corr_pos"][0] for x in group], "src_keypts": [x["corr"]["src_keypts"][0] for x in group],
-                         "tgt_keypts": [x["corr"]["tgt_keypts"][0] for x in group], "testing": True})
+                         "tgt_keypts": [x["corr"]["tgt_keypts"][0] for x in group], "testing": True, **extra})
             trans, labels = res["final_trans"], res["final_labels"]
+        if solver == "RANSAC":                                                                             # test_3DMatch.py:59-77
+            trans, labels = ransac_correspondence([x["corr"]["src_keypts"][0] for x in group], [x["corr"]["tgt_keypts"][0] for x in group],
+                                                  inlier_threshold, ransac_n=3, max_iteration=5000, mask=list(labels),
+                                                  pair_offset=first)
         if use_icp:                                                                                        # test_3DMatch.py:79-80
             trans = icp_refine([x["corr"]["src_keypts"][0] for x in group], [x["corr"]["tgt_keypts"][0] for x in group], trans,
                                icp_distance)

@@ -5,7 +5,8 @@
     python tools/eval_harness.py --pcd1 a.ply --pcd2 b.ply --descriptor fpfh [--use-icp]
     python tools/eval_harness.py --multiway [--num-views 5] [--descriptor {standin,fpfh}] [--batch-pairs 32] [--time 10]
     python tools/eval_harness.py --multiway --posegraph [--use-icp] [--num-views 5]
-    python tools/eval_harness.py --baseline {SM,PMC} [--num-pairs 8]
+    python tools/eval_harness.py --baseline {SM,PMC,RANSAC} [--num-pairs 8] [--max-iteration 1000]
+    python tools/eval_harness.py --solver RANSAC [--use-icp]
 
 Without --pcd1 the down-sampled demo cloud of tests/golden/demo_clouds_vox005.npz (reference demo_data/cloud_bin_0.ply at
 0.05 m) is used.  Every pair = the cloud against a seeded second view of it (partial overlap, noise, random rigid motion),
@@ -19,8 +20,9 @@ the device-side information matrix and the overlap gate (uncertain edges); print
 --multiway --posegraph goes on as the driver does (:159-227, harness.multiway_trajectory): node chain, pose-graph optimisation on the
 device (with --use-icp: multi-scale ICP of every edge and a second optimisation), and the driver's lines -- "Before optimization ...
 nodes ... edges", "After optimization ...", "Mean Absolute Trajectory Error: ... cm" against the views' true poses.
---baseline runs a classical baseline of baseline_scripts/baseline_3DMatch.py (--method SM / PMC: pointdsc_amd.baselines) in place of
-the model on the same pairs and prints the same stats rows.
+--baseline runs a classical baseline of baseline_scripts/baseline_3DMatch.py (--method SM / PMC / RANSAC: pointdsc_amd.baselines) in
+place of the model on the same pairs and prints the same stats rows.  --solver RANSAC is evaluation/test_3DMatch.py's: the model's
+pose and labels are replaced by correspondence RANSAC over the correspondences it labelled as inliers (pointdsc_amd.ransac).
 Registration Recall on 3DMatch-FCGF itself needs the released weights and the dataset (both absent here): pass
 --snapshot / real descriptors when they exist; the loop is the same.
 """
@@ -189,8 +191,11 @@ def main():
                     "print the median wall time")
     ap.add_argument("--posegraph", action="store_true", help="with --multiway: node chain, pose-graph optimisation on the device and the ATE "
                     "(test_multi_ate.py:159-227, :268); --use-icp adds the ICP refinement of the edges and the second optimisation")
-    ap.add_argument("--baseline", choices=harness.BaselineModel.METHODS, default=None,
+    ap.add_argument("--baseline", choices=harness.BaselineModel.METHODS + ("RANSAC",), default=None,
                     help="run this baseline of baseline_3DMatch.py in place of the model (pair loop only)")
+    ap.add_argument("--max-iteration", type=int, default=1000, help="with --baseline RANSAC: hypotheses per pair (baseline_3DMatch.py:131)")
+    ap.add_argument("--solver", choices=harness.SOLVERS, default="SVD", help="test_3DMatch.py --solver: RANSAC replaces every pose and "
+                    "label set by correspondence RANSAC (ransac_n 3, 5000 iterations) over the model's inliers, on the device")
     ap.add_argument("--validate", action="store_true", help="the validation loop of libs/trainer.py:158-222 on the device "
                     "(harness.validate: validation forward + the three losses) over --num-batches synthetic batches (bs 16, N 1000)")
     ap.add_argument("--num-batches", type=int, default=4, help="with --validate: batches of 16 pairs")
@@ -227,7 +232,9 @@ def main():
     else:
         cloud = np.load(ROOT / "tests" / "golden" / "demo_clouds_vox005.npz")["cloud_bin_0"]
     kw = dict(workloads.BASE_MODEL)                       # evaluation/test_3DMatch.py:215-224 with the snapshot's config.json
-    if a.baseline:
+    if a.baseline == "RANSAC":
+        model = harness.RansacModel(kw["inlier_threshold"], max_iteration=a.max_iteration)
+    elif a.baseline:
         model = harness.BaselineModel(a.baseline, kw["inlier_threshold"])
     else:
         model = PointDSC(**kw)
@@ -247,13 +254,13 @@ def main():
     pairs = harness.demo_pairs(cloud, a.num_pairs, corrupt=a.outlier_share, descriptor=a.descriptor, voxel=a.voxel)
     stats = harness.eval_scene(model, pairs, scene_ind=0,
                                inlier_threshold=kw["inlier_threshold"], use_mutual=a.mutual, batch_size=a.batch_size,
-                               use_icp=a.use_icp, icp_distance=a.icp_distance)
+                               use_icp=a.use_icp, icp_distance=a.icp_distance, solver=a.solver)
     summ = harness.summarize(stats)
     if a.json:
         print(json.dumps({"stats_columns": harness.STATS_NAMES, "stats": stats.tolist(), "summary": summ}))
         return
     print(f"{len(cloud)} points after {a.voxel} m voxel down-sampling; {a.num_pairs} pairs" + (" (ICP post-step)" if a.use_icp else "") +
-          (f" (baseline {a.baseline})" if a.baseline else ""))
+          (f" (baseline {a.baseline})" if a.baseline else "") + (" (solver RANSAC)" if a.solver == "RANSAC" else ""))
     print(" ".join(f"{n[:10]:>10s}" for n in harness.STATS_NAMES))
     for row in stats:
         print(" ".join(f"{v:10.4f}" for v in row))

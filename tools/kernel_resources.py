@@ -27,7 +27,11 @@ and of section 8 f-12 (the attention's backward):
 
 and of section 8 f-13 (the backward of the feature-similarity matrix, next to its forward and its sibling of the loss):
 
-    python tools/kernel_resources.py feature_compat_backward gram_rows_kernel sm_loss_features_kernel"""
+    python tools/kernel_resources.py feature_compat_backward gram_rows_kernel sm_loss_features_kernel
+
+and of section 8 f-21 (correspondence RANSAC):
+
+    python tools/kernel_resources.py ransac"""
 import re
 import subprocess
 import sys
