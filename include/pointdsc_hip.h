@@ -8,9 +8,9 @@
  * Every entry point cites the reference lines it replaces.
  *
  * Two tiers (r05):
- *   PRODUCT BOUNDARY -- what a caller of the reference's module needs: pdsc_forward_testing (+ _ragged, _streams),
- *     pdsc_forward_validation; the weight packers pdsc_wpack_floats / _offset, pdsc_wsplit_bytes / _offset / _build; the workspace
- *     queries pdsc_workspace_bytes / _offset; pdsc_encoder_range_probe; pdsc_version / pdsc_last_error; and, for the callers either
+ *   PRODUCT BOUNDARY -- what a caller of the reference's module needs: pdsc_forward (one call struct: testing forward, uniform or
+ *     ragged, on one or two streams; validation forward; range probe); the weight packers pdsc_wpack_floats / _offset,
+ *     pdsc_wsplit_bytes / _offset / _build; the workspace queries pdsc_workspace_bytes / _offset; pdsc_version / pdsc_last_error; and, for the callers either
  *     side of the path (SURVEY.md section 8 f-2 .. f-4), pdsc_match_* / pdsc_select_correspondences / pdsc_build_corr_pos,
  *     pdsc_sm_baseline*, pdsc_pmc_*, pdsc_cal_confidence, pdsc_eval_stats, pdsc_*_loss*, pdsc_pointwise_train_*, pdsc_icp_*, pdsc_information_*, pdsc_voxel_*, pdsc_cloud_*.
  *   STAGE LEVEL -- one entry point per reference stage (sections a-1 .. a-11 below), the plan / size queries that go with them,
@@ -45,7 +45,7 @@
 extern "C" {
 #endif
 
-#define PDSC_VERSION 9
+#define PDSC_VERSION 10
 #define PDSC_CHANNELS 128        /* num_channels of every released PointDSC model */
 #define PDSC_MAX_K 64            /* neighbours per seed handled by one wavefront   */
 #define PDSC_MAX_POWER_ITERS 32
@@ -83,7 +83,7 @@ typedef struct pdsc_config {
  * association order of an fp32-class computation changes.  W1f Wv is formed in fp64 from the packed fp32 matrices and rounded
  * once to fp32 (pdsc_wsplit_build).
  *   OFF (0): the 128-channel value path, layouts and bits of library version 8.
- *   ON  (1): valid with a split-precision attention and layer_gemm = PDSC_LAYER_GEMM_H3 only (config check).  pdsc_forward_*
+ *   ON  (1): valid with a split-precision attention and layer_gemm = PDSC_LAYER_GEMM_H3 only (config check).  pdsc_forward
  *            folds on the point-fragment hand-offs (leaf form, and key splits of 2..8) of calls with N <= PDSC_VALUE_FOLD_MAX_N
  *            (N = the longest pair of a ragged batch); a per-launch plan whose key split is 1 or more than 8, and larger N, keep
  *            the 128-channel path.                                                             [default of the Python module]
@@ -143,7 +143,7 @@ enum pdsc_compat_format { PDSC_COMPAT_F32 = 0, PDSC_COMPAT_U16 = 1 };
  *           denormal floor, which the gfx950 f16 MFMA honours), three v_mfma_f32_32x32x16_f16 per operand pair
  *           (hi*hi + hi*lo + lo*hi) into one fp32 accumulator: ~2^-21 relative error per product.  Operands must stay inside the
  *           fp16 range (|q|, |k|, |v| < 65504; the softmax weights are kept in (0, 32768] by construction): the Python module
- *           probes the first forward of a checkpoint and falls back to FP32 outside it (pdsc_encoder_range_probe).
+ *           probes the first forward of a checkpoint and falls back to FP32 outside it (pdsc_forward, PDSC_FORWARD_PROBE).
  *           Also used for the q|k|v projection (its results only feed the attention); the GEMMs whose results
  *           land on the residual stream (PointCN, fc_message) follow pdsc_config.layer_gemm.           [default]
  *           Rounds 1-4 split into bf16 pairs (2^-16 per product, fp32's range): on trained-like KITTI weights, whose
@@ -158,10 +158,7 @@ enum pdsc_compat_format { PDSC_COMPAT_F32 = 0, PDSC_COMPAT_U16 = 1 };
  * carries a device-side sentinel (workspace entry "range_flag", [bs] u32, pdsc_workspace_offset): a pair any of whose activations
  * reached 65504 on its way into an fp16 pair has a non-zero word there after the call AND its final_trans is returned as NaN. */
 enum pdsc_attention_precision { PDSC_ATT_FP16X3 = 0, PDSC_ATT_FP32 = 1, PDSC_ATT_FP16X3_ALL = 2 };
-/* Optional: where the testing forwards enqueued by THIS thread from now on also leave their range words -- host_words = [bs] u32 of
- * pinned, device-mapped host memory (hipHostMalloc; checked), written by the forward's last launch: a caller that waits for the
- * stream anyway reads them without a device-to-host copy of its own.  NULL switches it off.  Thread-local, like pdsc_last_error. */
-int pdsc_set_range_report(unsigned int* host_words);
+/* (A testing forward can also leave the range words in pinned host memory: pdsc_forward_call.range_report.) */
 
 /* ---- packed weights --------------------------------------------------------------------------
  * One flat fp32 buffer holding the model with BatchNorm (eval) folded into the preceding conv and
@@ -205,7 +202,7 @@ long long pdsc_wpack_offset(const pdsc_config* cfg, int section, int layer);
 /* leading dimension (floats) the compat matrix rows must have for N correspondences */
 long long pdsc_compat_ld(int N);
 
-/* bytes of scratch pdsc_forward_testing needs (compat matrix included) */
+/* bytes of scratch pdsc_forward needs (compat matrix included) */
 size_t pdsc_workspace_bytes(const pdsc_config* cfg, int bs, int N, int num_seeds);
 
 /* ---- a-1  spatial-consistency matrix -----------------------------------------------------------
@@ -260,7 +257,7 @@ int pdsc_layer0(const float* corr_pos, int in_dim, const float* W0, const float*
  * One call, pdsc_layer_run, takes one struct; a zero-initialised field means "absent".  The weights come in ONE of two forms:
  *   natural layout: [out][in] fp32 matrices, BN folded (sections PDSC_W_FC1..FC3 of layer i, PDSC_W_PCN / QKV of layer i+1);
  *   fragment streams: 8 KiB chunks in exactly the order the wavefront-resident kernels consume them, so every weight load of
- *     a wave is 1 KiB of consecutive memory -- what pdsc_forward_* uses by default.  Built by pdsc_wfrag_build_tail / _head:
+ *     a wave is 1 KiB of consecutive memory -- what pdsc_forward uses by default.  Built by pdsc_wfrag_build_tail / _head:
  *       tail stream: pdsc_wfrag_tail_bytes() bytes from (fc1 [C/2][C], fc2 [C/2][C/2], fc3 [C][C/2]) fp32 and their biases;
  *       head stream: pdsc_wfrag_head_bytes() bytes from (pcn [C][C], qkv [3C][C] fp32 -> fp16 hi / lo) and their biases
  *                    (the bias of an output tile is one more k-step of its GEMM: A = bias, B = 1);
@@ -338,7 +335,7 @@ int       pdsc_wsplit_build(const pdsc_config* cfg, const float* wpack, void* ws
 #define PDSC_WS_FOLD_W 106
 size_t pdsc_wfrag_fold_tail_bytes(void);
 size_t pdsc_wfrag_fold_head_bytes(void);
-int pdsc_layer_prefers_block(int bs, int N);   /* 1: with layer_gemm = F32, pdsc_forward_* takes the workgroup-per-tile kernel for this size */
+int pdsc_layer_prefers_block(int bs, int N);   /* 1: with layer_gemm = F32, pdsc_forward takes the workgroup-per-tile kernel for this size */
 int pdsc_layer_h3_uses_coop(int bs, int N);    /* 1: with layer_gemm = H3, a launch over bs x N points takes layer_h3_coop_kernel (four
                                                 * wavefronts per 32-point tile: at most 2560 tiles), 0: layer_h3_kernel */
 size_t pdsc_wfrag_tail_bytes(void);
@@ -407,7 +404,7 @@ int pdsc_layer_trace(long long* device_buffer);
  *   h2[m][0:32] = relu(W2 relu(W1 feat[m][0:128] + b1) + b2),  W1 [32][128], W2 [32][32] row-major fp32.
  * Exact fp32 MFMA; every output element goes through the same fma chain as
  *   pdsc_linear(feat, 128, W1, b1, ..., relu) followed by pdsc_linear(h1, 32, W2, b2, ..., relu)   -- bit-identical --
- * without the [M][32] hidden layer going through HBM.  pdsc_forward_* calls this since r04. */
+ * without the [M][32] hidden layer going through HBM.  pdsc_forward calls this since r04. */
 int pdsc_classifier_hidden(const float* feat, const float* W1, const float* b1, const float* W2, const float* b2, float* h2,
                            int M, void* stream);
 
@@ -506,64 +503,86 @@ int pdsc_post_refinement(const float* initial_trans, const float* src_keypts, co
                          int bs, int N, void* stream);
 
 /* ---- whole path --------------------------------------------------------------------------------
- * replaces PointDSC.forward(data) with 'testing' in data (models/PointDSC.py:128-197).
- * corr_pos [bs][N][in_dim], src/tgt [bs][N][3]  ->  final_trans [bs][16], final_labels [bs][N] (0/1).
- * num_seeds = int(N * ratio) computed by the caller in double precision like the reference (:174). */
-int pdsc_forward_testing(const pdsc_config* cfg, const float* wpack, const void* wsplit /* NULL iff PDSC_ATT_FP32 */,
-                         const float* corr_pos, const float* src_keypts, const float* tgt_keypts,
-                         int bs, int N, int num_seeds,
-                         float* final_trans, float* final_labels,
-                         void* workspace, size_t workspace_bytes, void* stream);
-
-/* ---- whole path, ragged batch ---------------------------------------------------------------------
- * The reference's real evaluation feeds every pair with its own number of correspondences (evaluation/test_3DMatch.py:126
- * `num_node='all'`, datasets/ThreeDMatch.py:271-276) and therefore one pair per call (models/PointDSC.py:210); its own
- * batching crops every pair to the shortest (datasets/dataloader.py:6-31).  Here a batch may mix sizes: the inputs are
- * padded to the longest pair, [bs][N][.] with N = max_b num_corr[b] (padding rows: any finite values, e.g. zeros), and
- *   num_corr           [bs] int32, DEVICE: correspondences of pair b (2 <= num_corr[b] <= N)
- *   num_seeds_per_pair [bs] int32, DEVICE: int(num_corr[b] * ratio) >= 1, computed by the caller in double precision (:174)
- *   num_seeds          = max_b num_seeds_per_pair[b],   n_min = min_b num_corr[b] (host copies; n_min must leave every pair
- *                        at least one 32-key tile per attention key split: ceil(n_min / 32) >= pdsc_attention_split_default_split(bs, N),
- *                        and n_min > min(cfg->k, N - 1): the reference clamps k per pair, k = min(k, num_corr - 1)
- *                        (models/PointDSC.py:250), one launch has one k -- a pair of at most k rows is its own call;
- *                        PDSC_ERR_ARG otherwise)
- * Pair b's results are those of pdsc_forward_testing on its own num_corr[b] rows (same stages on the same data; only the
- * launch plans, i.e. fp32 summation orders, are the batch's): final_trans [bs][16], final_labels [bs][N] with rows
- * >= num_corr[b] zero.  Workspace: pdsc_workspace_bytes(cfg, bs, N, num_seeds).  Split-precision attention modes only. */
-int pdsc_forward_testing_ragged(const pdsc_config* cfg, const float* wpack, const void* wsplit,
-                                const float* corr_pos, const float* src_keypts, const float* tgt_keypts,
-                                int bs, int N, int num_seeds, const int* num_corr, const int* num_seeds_per_pair, int n_min,
-                                float* final_trans, float* final_labels,
-                                void* workspace, size_t workspace_bytes, void* stream);
-
-/* ---- whole path on two streams (throughput loops with several forwards in flight, pointdsc_amd/pipeline.py) --------
- * Same result as pdsc_forward_testing (num_corr == NULL) / pdsc_forward_testing_ragged.  The encoder (compat build, 12 attention
- * + layer launches) is enqueued on `stream`; everything after it -- classifier, NMS, seed ranking, kNN, per-seed solver,
- * scoring, refinement: a sequential chain of ~15 small launches -- on `tail_stream`, which the caller creates with a HIGHER
- * priority: while forward i's tail runs, forward i+1's encoder (another stream) keeps the chip full, and the tail's few
- * workgroups are dispatched ahead of the attention launch's queued ones instead of behind them.  fork_event / join_event:
- * caller-owned hipEvent_t (no timing needed), recorded on stream / tail_stream; on return `stream` waits for join_event, so
- * work enqueued on `stream` afterwards is ordered after the results.  Nothing is allocated; capturable in a hipGraph.
- * Measured with two forwards in flight (profiles/r03_h_inflight_ab.txt, r03_i_inflight_ab.txt): -2.6 % per step at 32 pairs of
- * N = 5000, -6 % at 4 pairs, -13 % for one pair of N = 10000 against one stream; two plain streams without it: +-0. */
-int pdsc_forward_testing_streams(const pdsc_config* cfg, const float* wpack, const void* wsplit,
-                                 const float* corr_pos, const float* src_keypts, const float* tgt_keypts,
-                                 int bs, int N, int num_seeds, const int* num_corr /* NULL: uniform batch */,
-                                 const int* num_seeds_per_pair, int n_min,
-                                 float* final_trans, float* final_labels,
-                                 void* workspace, size_t workspace_bytes,
-                                 void* stream, void* tail_stream, void* fork_event, void* join_event);
-
-/* ---- validation forward -------------------------------------------------
- * replaces PointDSC.forward(data) WITHOUT the 'testing' key on a module in eval() mode (libs/trainer.py:158-222
- * calls it so): models/PointDSC.py:158-163 (feature similarity matrix M), :176 (seeds = top int(N*ratio) by
- * confidence, no NMS), :182 (per-seed hypotheses; the power iteration's allclose exit is taken over the whole batch),
- * no post refinement, :190-191 (the returned labels are the confidence logits).  Forward only (no autograd).
- *   final_trans [bs][16] = best seed hypothesis; logits [bs][N]; M [bs][N][ldM]. */
-int pdsc_forward_validation(const pdsc_config* cfg, const float* wpack, const void* wsplit,
-                            const float* corr_pos, const float* src_keypts, const float* tgt_keypts,
-                            int bs, int N, int num_seeds, float* final_trans, float* logits,
-                            float* M, long long ldM, void* workspace, size_t workspace_bytes, void* stream);
+ * One call, pdsc_forward, takes one struct; a zero-initialised field means "absent".  `mode` says which forward runs:
+ *
+ * PDSC_FORWARD_TESTING replaces PointDSC.forward(data) with 'testing' in data (models/PointDSC.py:128-197).
+ *   corr_pos [bs][N][in_dim], src/tgt [bs][N][3]  ->  final_trans [bs][16], final_labels [bs][N] (0/1).
+ *   num_seeds = int(N * ratio) computed by the caller in double precision like the reference (:174).
+ *
+ *   Ragged batch (num_corr, num_seeds_per_pair, n_min given).  The reference's real evaluation feeds every pair with its own number
+ *   of correspondences (evaluation/test_3DMatch.py:126 `num_node='all'`, datasets/ThreeDMatch.py:271-276) and therefore one pair
+ *   per call (models/PointDSC.py:210); its own batching crops every pair to the shortest (datasets/dataloader.py:6-31).  Here a
+ *   batch may mix sizes: the inputs are padded to the longest pair, [bs][N][.] with N = max_b num_corr[b] (padding rows: any
+ *   finite values, e.g. zeros), num_seeds = max_b num_seeds_per_pair[b].  Pair b's results are those of a uniform call on its own
+ *   num_corr[b] rows (same stages on the same data; only the launch plans, i.e. fp32 summation orders, are the batch's):
+ *   final_trans [bs][16], final_labels [bs][N] with rows >= num_corr[b] zero.  Workspace: pdsc_workspace_bytes(cfg, bs, N,
+ *   num_seeds).  Split-precision attention modes only.
+ *
+ *   Two streams (tail_stream, fork_event, join_event given; throughput loops with several forwards in flight,
+ *   pointdsc_amd/pipeline.py).  Same result as on one stream, uniform or ragged.  The encoder (compat build, 12 attention + layer
+ *   launches) is enqueued on `stream`; everything after it -- classifier, NMS, seed ranking, kNN, per-seed solver, scoring,
+ *   refinement: a sequential chain of ~15 small launches -- on `tail_stream`, which the caller creates with a HIGHER priority:
+ *   while forward i's tail runs, forward i+1's encoder (another stream) keeps the chip full, and the tail's few workgroups are
+ *   dispatched ahead of the attention launch's queued ones instead of behind them.  fork_event / join_event: caller-owned
+ *   hipEvent_t (no timing needed), recorded on stream / tail_stream; on return `stream` waits for join_event, so work enqueued on
+ *   `stream` afterwards is ordered after the results.  Nothing is allocated; capturable in a hipGraph.  Measured with two forwards
+ *   in flight (profiles/r03_h_inflight_ab.txt, r03_i_inflight_ab.txt): -2.6 % per step at 32 pairs of N = 5000, -6 % at 4 pairs,
+ *   -13 % for one pair of N = 10000 against one stream; two plain streams without it: +-0.
+ *
+ * PDSC_FORWARD_VALIDATION replaces PointDSC.forward(data) WITHOUT the 'testing' key on a module in
+ *   eval() mode (libs/trainer.py:158-222 calls it so): models/PointDSC.py:158-163 (feature similarity matrix M), :176 (seeds = top
+ *   int(N*ratio) by confidence, no NMS), :182 (per-seed hypotheses; the power iteration's allclose exit is taken over the whole
+ *   batch), no post refinement, :190-191 (the returned labels are the confidence logits).  Forward only (no autograd).
+ *   final_trans [bs][16] = best seed hypothesis; final_labels [bs][N] = the logits; M [bs][N][ldM].  Uniform batches, one stream.
+ *
+ * PDSC_FORWARD_PROBE: range probe for layer_gemm = PDSC_LAYER_GEMM_H3.  The H3 arithmetic carries every operand of the
+ *   fc_message / PointCN GEMMs as fp16 hi + lo, so every activation of the 12-layer chain -- hidden ones included -- must stay
+ *   below 65504.  This mode runs the ENCODER (compat, layer0, 12 x {PointCN, q|k|v, attention, fc1, fc2, fc3 + residual};
+ *   models/PointDSC.py:48-77) once with the fp32 GEMMs, one launch per conv, and leaves in absmax[kind] (enum pdsc_range_kind) the
+ *   largest |value| of each activation kind over all layers (a NaN anywhere reads back as NaN).  No pose, no labels: final_trans,
+ *   final_labels and M are not written.  The module calls it on the first forward after packing weights and falls back to
+ *   PDSC_LAYER_GEMM_F32 with a warning when a value is out of range.  Same inputs and workspace as the testing forward. */
+enum pdsc_forward_mode { PDSC_FORWARD_TESTING = 0, PDSC_FORWARD_VALIDATION = 1, PDSC_FORWARD_PROBE = 2 };
+enum pdsc_range_kind { PDSC_RANGE_LAYER0 = 0, PDSC_RANGE_POINTCN = 1, PDSC_RANGE_QKV = 2, PDSC_RANGE_MESSAGE = 3, PDSC_RANGE_FC1 = 4,
+                       PDSC_RANGE_FC2 = 5, PDSC_RANGE_FEATURE = 6, PDSC_RANGE_NUM_KINDS = 8 };
+typedef struct pdsc_forward_call {
+    int mode;                        /* enum pdsc_forward_mode */
+    const pdsc_config* cfg;
+    const float* wpack;              /* packed weights (pdsc_wpack_floats) */
+    const void* wsplit;              /* split-weight buffer (pdsc_wsplit_build); NULL iff PDSC_ATT_FP32 */
+    const float* corr_pos;           /* [bs][N][in_dim] */
+    const float* src_keypts;         /* [bs][N][3] */
+    const float* tgt_keypts;         /* [bs][N][3] */
+    int bs, N, num_seeds;            /* ragged batch: N and num_seeds are those of the longest pair */
+    float* final_trans;              /* [bs][16]; required except by the probe */
+    float* final_labels;             /* [bs][N]: 0/1 labels (testing) or the confidence logits (validation); required except by the probe */
+    float* M;                        /* [bs][N][ldM] feature similarity matrix: validation only, and required there */
+    long long ldM;                   /*   >= N */
+    void* workspace;                 /* pdsc_workspace_bytes(cfg, bs, N, num_seeds) bytes */
+    size_t workspace_bytes;
+    const int* num_corr;             /* ragged batch (testing only; both arrays or neither): [bs] int32, DEVICE: correspondences of pair b
+                                      * (2 <= num_corr[b] <= N) */
+    const int* num_seeds_per_pair;   /*   [bs] int32, DEVICE: int(num_corr[b] * ratio) >= 1, computed by the caller in double precision (:174) */
+    int n_min;                       /*   min_b num_corr[b] (host copy), 2 <= n_min <= N.  It must leave every pair at least one 32-key tile
+                                      *   per attention key split: ceil(n_min / 32) >= pdsc_attention_split_default_split(bs, N), and
+                                      *   n_min > min(cfg->k, N - 1): the reference clamps k per pair, k = min(k, num_corr - 1)
+                                      *   (models/PointDSC.py:250), one launch has one k -- a pair of at most k rows is its own call;
+                                      *   PDSC_ERR_ARG otherwise */
+    void* tail_stream;               /* two streams (testing only): hipStream_t of the tail, different from `stream`; needs both events */
+    void* fork_event;                /*   hipEvent_t recorded on `stream` behind the encoder; tail_stream waits for it */
+    void* join_event;                /*   hipEvent_t recorded on tail_stream behind the last launch; `stream` waits for it */
+    float* absmax;                   /* probe only, and required there: [PDSC_RANGE_NUM_KINDS] floats, DEVICE; zeroed by the call's first launch */
+    unsigned int* range_report;      /* optional (testing only): where the forward also leaves its range words -- [bs] u32 of pinned,
+                                      * device-mapped HOST memory (hipHostMalloc; checked: anything else is PDSC_ERR_ARG), written by the
+                                      * forward's last launch: a caller that waits for the stream anyway reads them without a
+                                      * device-to-host copy of its own */
+} pdsc_forward_call;
+/* Every field is checked before the first launch, event record or fill: a rejected call (< 0) has enqueued nothing, and
+ * pdsc_last_error() names the call and its mode, "pdsc_forward(validation): ...".
+ * BREAKING in PDSC_VERSION 10: the five whole-path entry points of version 9 (testing, ragged, on two streams, validation, encoder
+ * range probe) and the thread-local range-report setter are GONE.  pdsc_forward does what each did when the struct's fields of the
+ * same names hold the same values. */
+int pdsc_forward(const pdsc_forward_call* call, void* stream);
 
 /* M[b][i][j] = clamp(1 - (1 - <normed_i, normed_j>) / sigma^2, 0, 1), M[b][i][i] = 0   (models/PointDSC.py:158-163);
  * normed [bs*N][C], sigma: device pointer to the learned sigma, M [bs][N][ld >= N]. */
@@ -1003,21 +1022,8 @@ int pdsc_global_optimization(const double* nodes, const int* source, const int* 
                              unsigned char* live_out, double* record, long long* ticks, void* workspace, size_t workspace_bytes,
                              int num_graphs, int max_nodes, int max_edges, int total_nodes, int total_edges, void* stream);
 
-/* ---- range probe for layer_gemm = PDSC_LAYER_GEMM_H3 ----------------------------------------------------------------
- * The H3 arithmetic carries every operand of the fc_message / PointCN GEMMs as fp16 hi + lo, so every activation of the
- * 12-layer chain -- hidden ones included -- must stay below 65504.  This entry runs the ENCODER (compat, layer0, 12 x
- * {PointCN, q|k|v, attention, fc1, fc2, fc3 + residual}; models/PointDSC.py:48-77) once with the fp32 GEMMs, one launch per
- * conv, and leaves in absmax[kind] (DEVICE, PDSC_RANGE_NUM_KINDS floats) the largest |value| of each activation kind over
- * all layers (a NaN anywhere reads back as NaN).  The module calls it on the first forward after packing weights and falls
- * back to PDSC_LAYER_GEMM_F32 with a warning when a value is out of range.  Same workspace as pdsc_forward_testing. */
-enum pdsc_range_kind { PDSC_RANGE_LAYER0 = 0, PDSC_RANGE_POINTCN = 1, PDSC_RANGE_QKV = 2, PDSC_RANGE_MESSAGE = 3, PDSC_RANGE_FC1 = 4,
-                       PDSC_RANGE_FC2 = 5, PDSC_RANGE_FEATURE = 6, PDSC_RANGE_NUM_KINDS = 8 };
-int pdsc_encoder_range_probe(const pdsc_config* cfg, const float* wpack, const void* wsplit, const float* corr_pos,
-                             const float* src_keypts, const float* tgt_keypts, int bs, int N, int num_seeds, float* absmax,
-                             void* workspace, size_t workspace_bytes, void* stream);
-
 /* Named views into the workspace of the last layout computed for (cfg, bs, N, num_seeds): lets the
- * parity tests read intermediates after pdsc_forward_testing.  Returns byte offset or -1. */
+ * parity tests read intermediates after pdsc_forward.  Returns byte offset or -1. */
 long long pdsc_workspace_offset(const pdsc_config* cfg, int bs, int N, int num_seeds, const char* name);
 
 /* ---- opt-in kernel timing (bench.py's roofline leg) ----------------------------------------------

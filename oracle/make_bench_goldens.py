@@ -17,7 +17,7 @@ For each BASELINE.json configuration it
      reference's own GPU path included, can be expected to reproduce its pose to 1e-4; such pairs are flagged
      `stable = False` and compared on labels + a 1e-3 pose tolerance only,
   5. stores the reference outputs (poses + bit-packed labels), the stability flags and input checksums.
-The GPU tests compare ``pdsc_forward_testing`` on the WHOLE bench batch (the launch plans bench.py times) with these.
+The GPU tests compare ``pdsc_forward`` on the WHOLE bench batch (the launch plans bench.py times) with these.
 """
 from __future__ import annotations
 

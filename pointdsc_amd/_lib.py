@@ -48,10 +48,26 @@ class PdscLayerCall(C.Structure):
                             "w1", "b1", "w2", "b2", "w3", "b3", "wp", "bp", "wq", "bq", "wq_split", "wfrag_tail", "wfrag_head")] +
         [(n, _i) for n in ("gemm_format", "io_flags", "bs", "N", "kernel")])
 
+
+ERR_ARG = -1        # enum pdsc_status: PDSC_ERR_ARG
+# enum pdsc_forward_mode
+FORWARD_TESTING, FORWARD_VALIDATION, FORWARD_PROBE = 0, 1, 2
+
+
+class PdscForwardCall(C.Structure):
+    """struct pdsc_forward_call (include/pointdsc_hip.h): one whole-path call; zero / None = absent."""
+    _fields_ = (
+        [("mode", _i), ("cfg", _cfgp)] + [(n, _vp) for n in ("wpack", "wsplit", "corr_pos", "src_keypts", "tgt_keypts")] +
+        [("bs", _i), ("N", _i), ("num_seeds", _i)] + [(n, _vp) for n in ("final_trans", "final_labels", "M")] + [("ldM", _ll)] +
+        [("workspace", _vp), ("workspace_bytes", _sz), ("num_corr", _vp), ("num_seeds_per_pair", _vp), ("n_min", _i)] +
+        [(n, _vp) for n in ("tail_stream", "fork_event", "join_event", "absmax", "range_report")])
+
+
+ABI_VERSION = 10        # PDSC_VERSION of include/pointdsc_hip.h that this table binds
+
 # name -> (restype, argtypes); must list every function include/pointdsc_hip.h declares
 SIGNATURES = {
     "pdsc_version": (_i, []),
-    "pdsc_set_range_report": (_i, [_vp]),
     "pdsc_last_error": (C.c_char_p, []),
     "pdsc_experiments_enabled": (_i, []),
     "pdsc_wpack_floats": (_ll, [_cfgp]),
@@ -186,13 +202,9 @@ SIGNATURES = {
     "pdsc_posegraph_nodes": (_i, [_vp] * 6 + [_i, _i, _i, _vp]),
     "pdsc_global_optimization": (_i, [_vp] * 9 + [C.c_double, C.c_double, C.c_double, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i,
                                       _i, _vp]),
-    "pdsc_encoder_range_probe": (_i, [_cfgp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
-    "pdsc_forward_validation": (_i, [_cfgp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _ll, _vp, _sz, _vp]),
     "pdsc_feature_compat": (_i, [_vp, _vp, _vp, _ll, _i, _i, _vp]),
     "pdsc_conv_mask_all_pairs": (_i, [_vp, _i, _vp]),
-    "pdsc_forward_testing": (_i, [_cfgp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
-    "pdsc_forward_testing_ragged": (_i, [_cfgp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
-    "pdsc_forward_testing_streams": (_i, [_cfgp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
+    "pdsc_forward": (_i, [C.POINTER(PdscForwardCall), _vp]),
 }
 
 _lib = None
@@ -218,8 +230,8 @@ def load() -> C.CDLL:
             raise PointDSCLibraryError(f"{LIB_PATH} does not export {name}") from e
         fn.restype = res
         fn.argtypes = args
-    if lib.pdsc_version() != 9:
-        raise PointDSCLibraryError(f"unexpected library version {lib.pdsc_version()}")
+    if lib.pdsc_version() != ABI_VERSION:
+        raise PointDSCLibraryError(f"unexpected library version {lib.pdsc_version()} (this binding: {ABI_VERSION})")
     _lib = lib
     return lib
 

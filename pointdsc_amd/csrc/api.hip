@@ -1,6 +1,6 @@
 // Host side of libpointdsc_hip.so: error plumbing, packed-weight layout, workspace layout (entries by WsId) and the whole-path
-// orchestrator run_forward behind pdsc_forward_testing* / pdsc_forward_validation / pdsc_encoder_range_probe: one ForwardCall,
-// an explicit ForwardMode, one function per stage (reference PointDSC.forward, models/PointDSC.py:128-197).  Pure HIP runtime --
+// orchestrator pdsc_forward: one pdsc_forward_call with an explicit mode, checked whole before the first launch, then one
+// function per stage (reference PointDSC.forward, models/PointDSC.py:128-197).  Pure HIP runtime --
 // no torch types cross this boundary.  Every stage is enqueued on the caller's stream with no host synchronisation, so one
 // forward is hipGraph-capturable.
 #include <stdarg.h>
@@ -15,12 +15,6 @@
 namespace pdsc {
 
 static thread_local char g_err[512] = "";
-
-// where the NEXT forward of this thread also reports its range words: pinned, device-mapped host memory ([bs] u32), or NULL
-static unsigned int*& range_report_slot() {
-    static thread_local unsigned int* slot = nullptr;
-    return slot;
-}
 
 void set_error(const char* fmt, ...) {
     va_list ap;
@@ -282,20 +276,6 @@ using namespace pdsc;
 
 extern "C" int pdsc_version(void) { return PDSC_VERSION; }
 
-extern "C" int pdsc_set_range_report(unsigned int* host_words) {
-    if (host_words) {
-        // must be host memory the device can write (hipHostMalloc / a registered range): anything else would fault inside the kernel
-        hipPointerAttribute_t at{};
-        if (hipPointerGetAttributes(&at, host_words) != hipSuccess || at.type != hipMemoryTypeHost || at.devicePointer == nullptr) {
-            (void)hipGetLastError();
-            set_error("pdsc_set_range_report: %p is not pinned, device-mapped host memory", (void*)host_words);
-            return PDSC_ERR_ARG;
-        }
-        host_words = (unsigned int*)at.devicePointer;
-    }
-    range_report_slot() = host_words;
-    return PDSC_OK;
-}
 extern "C" int pdsc_experiments_enabled(void) {
 #ifdef PDSC_EXPERIMENTS
     return 1;
@@ -401,7 +381,7 @@ static int plan_encoder(const pdsc_config* cfg, int bs, int N, const int* nvalid
     const int min_tiles = (n_min + 31) / 32;         // 32-key tiles of the shortest pair (ragged batches)
     p.ns = p.split ? pdsc_attention_split_default_split(bs, N) : 0;
 #define PDSC_REQUIRE_SHORTEST_PAIR(cond)                                                                                             \
-    PDSC_REQUIRE(cond, "pdsc_forward_testing_ragged: the shortest pair (%d correspondences) has fewer 32-key tiles than the key split " \
+    PDSC_REQUIRE(cond, "pdsc_forward(testing): the shortest pair (%d correspondences) has fewer 32-key tiles than the key split " \
                  "planned for bs=%d, N=%d (%d): batch pairs of more similar size", n_min, bs, N, p.ns)
     // Every pair must keep at least one tile per key split.  Two checks, because they do not reject the same calls.  This one
     // alone catches the un-fused path (PDSC_FUSED_LAYERS = 0, or no layers): whatever the layer kernels, a configuration without
@@ -461,35 +441,11 @@ static int plan_encoder(const pdsc_config* cfg, int bs, int N, const int* nvalid
     return PDSC_OK;
 }
 
-// Testing = the reference's testing forward.  Validation (no 'testing' key, module in eval mode): feature similarity matrix M,
-// seeds = top-S by confidence (no NMS), batch-wide power-iteration exit, no refinement, labels = logits.  Probe
-// (pdsc_encoder_range_probe): the encoder alone, one launch per conv, |max| of each activation kind; no pose, no labels.
-enum class ForwardMode { Testing, Validation, Probe };
-
-// One whole-path call, as the extern "C" entry points fill it in (zero / NULL = absent).
-struct ForwardCall {
-    ForwardMode mode;
-    const pdsc_config* cfg;
-    const float* wpack;
-    const void* wsplit;
-    const float *corr_pos, *src, *tgt;
-    int bs, N, num_seeds;
-    float *final_trans, *final_labels, *Mout;      // Mout [bs][N][ldM]: Validation only; the probe writes none of the three
-    long long ldM;
-    void* workspace;
-    size_t workspace_bytes;
-    void* stream;
-    // ragged batch (ragged.h): device [bs] counts -- N and num_seeds are then those of the longest pair, n_min the shortest pair's
-    // count (host copy: the attention's key split must leave every pair at least one tile per split)
-    const int *nvalid, *svalid;
-    int n_min;
-    void *tail_stream, *ev_fork, *ev_join;      // pdsc_forward_testing_streams
-    unsigned int* probe;                        // Probe: [PDSC_RANGE_NUM_KINDS] |max| bit patterns (device)
-};
-
-// The call plus what is derived from it once: encoder plan, workspace layout, the buffers more than one stage uses, a few scalars.
+// The call (include/pointdsc_hip.h: struct pdsc_forward_call, enum pdsc_forward_mode) plus what is derived from it once: encoder
+// plan, workspace layout, the buffers more than one stage uses, a few scalars.
 struct ForwardCtx {
-    const ForwardCall& c;
+    const pdsc_forward_call& c;
+    hipStream_t main;    // the caller's stream
     EncoderPlan plan;
     WsLayout L;
     hipStream_t st;      // where the next launch goes: the caller's stream, after fork_tail the tail stream
@@ -499,42 +455,69 @@ struct ForwardCtx {
     float *compat, *featA, *featB, *featC, *qkv, *msg, *normed, *normed_pf, *conf, *keys, *seed_trans;
     int *seeds, *knn_idx, *counts;
     unsigned int *conv_mask, *range_flag;
+    unsigned int* range_report;      // device address of c.range_report (validate_call), or NULL
     void *att_scratch, *q_split, *kv_tiles;
     const float* W(int section, int layer) const { return c.wpack + wpack_offset(c.cfg, section, layer); }
     const void* WS(int section, int layer) const { return (const unsigned short*)c.wsplit + pdsc_wsplit_offset(c.cfg, section, layer); }
 };
 
-static int validate_call(const ForwardCall& c) {
+static const char* mode_name(int mode) {
+    return mode == PDSC_FORWARD_TESTING ? "testing" : mode == PDSC_FORWARD_VALIDATION ? "validation" : mode == PDSC_FORWARD_PROBE ? "probe" : "?";
+}
+// PDSC_REQUIRE whose text names the call and its mode; `c` is the pdsc_forward_call in scope
+#define PDSC_REQUIRE_CALL(cond, fmt, ...) PDSC_REQUIRE(cond, "pdsc_forward(%s): " fmt, mode_name(c.mode), ##__VA_ARGS__)
+
+// Every argument check of the call: pure host code but for one pointer query, nothing is enqueued before it has passed.
+static int validate_call(ForwardCtx& x) {
+    const pdsc_forward_call& c = x.c;
     if (!config_ok(c.cfg)) return PDSC_ERR_ARG;
-    PDSC_REQUIRE(!c.tail_stream || (c.ev_fork && c.ev_join && c.tail_stream != c.stream),
-                 "pdsc_forward_testing_streams: a tail stream (different from the main stream) needs the fork and join events");
+    PDSC_REQUIRE(c.mode == PDSC_FORWARD_TESTING || c.mode == PDSC_FORWARD_VALIDATION || c.mode == PDSC_FORWARD_PROBE,
+                 "pdsc_forward: unknown mode %d (enum pdsc_forward_mode)", c.mode);
+    const bool testing = c.mode == PDSC_FORWARD_TESTING;
+    PDSC_REQUIRE_CALL(testing || !c.tail_stream, "a tail stream belongs to the testing forward only");
+    PDSC_REQUIRE_CALL(testing || !c.range_report, "range_report belongs to the testing forward only");
+    PDSC_REQUIRE_CALL(!c.tail_stream || (c.fork_event && c.join_event && c.tail_stream != x.main),
+                      "a tail stream (different from the main stream) needs the fork and join events");
     const int N = c.N, n_min = c.n_min, k = c.cfg->k < N - 1 ? c.cfg->k : N - 1;
-    if (c.nvalid) {
-        PDSC_REQUIRE(c.mode == ForwardMode::Testing && c.svalid, "pdsc_forward_testing_ragged: testing forward only, both count arrays needed");
-        PDSC_REQUIRE(n_min >= 2 && n_min <= N, "pdsc_forward_testing_ragged: n_min=%d (N=%d)", n_min, N);
+    PDSC_REQUIRE_CALL((c.num_corr == nullptr) == (c.num_seeds_per_pair == nullptr), "both per-pair count arrays (device, [bs] int32) or neither");
+    if (c.num_corr) {
+        PDSC_REQUIRE_CALL(testing, "a ragged batch belongs to the testing forward only");
+        PDSC_REQUIRE_CALL(n_min >= 2 && n_min <= N, "n_min=%d (N=%d)", n_min, N);
         // one launch has one neighbour count k = min(cfg->k, N - 1); the reference clamps per pair, k_b = min(k, num_corr_b - 1)
         // (models/PointDSC.py:250): a pair with fewer than k + 1 correspondences must be its own call
-        PDSC_REQUIRE(n_min > k, "pdsc_forward_testing_ragged: the shortest pair (%d correspondences) has no "
-                     "more than k=%d: the reference clamps k per pair (k = min(k, num_corr - 1)); run such a pair in its own call", n_min, k);
+        PDSC_REQUIRE_CALL(n_min > k, "the shortest pair (%d correspondences) has no "
+                          "more than k=%d: the reference clamps k per pair (k = min(k, num_corr - 1)); run such a pair in its own call", n_min, k);
     }
-    const bool outputs = c.mode == ForwardMode::Probe || (c.final_trans && c.final_labels);
-    PDSC_REQUIRE(c.wpack && c.corr_pos && c.src && c.tgt && outputs && c.workspace, "pdsc_forward_testing: null pointer");
-    PDSC_REQUIRE(c.bs > 0 && N > 1, "pdsc_forward_testing: bs=%d N=%d", c.bs, N);
-    PDSC_REQUIRE(c.num_seeds >= 1 && c.num_seeds <= N,
-                 "pdsc_forward_testing: num_seeds=%d (int(N*ratio) must be >= 1; the reference fails on an empty seed set)", c.num_seeds);
+    PDSC_REQUIRE_CALL(c.mode != PDSC_FORWARD_VALIDATION || (c.M && c.ldM >= N), "M matrix [bs][N][ldM >= N] required");
+    PDSC_REQUIRE_CALL(c.mode != PDSC_FORWARD_PROBE || c.absmax, "absmax [PDSC_RANGE_NUM_KINDS] (device) required");
+    const bool outputs = c.mode == PDSC_FORWARD_PROBE || (c.final_trans && c.final_labels);
+    PDSC_REQUIRE_CALL(c.wpack && c.corr_pos && c.src_keypts && c.tgt_keypts && outputs && c.workspace, "null pointer");
+    PDSC_REQUIRE_CALL(c.bs > 0 && N > 1, "bs=%d N=%d", c.bs, N);
+    PDSC_REQUIRE_CALL(c.num_seeds >= 1 && c.num_seeds <= N,
+                      "num_seeds=%d (int(N*ratio) must be >= 1; the reference fails on an empty seed set)", c.num_seeds);
+    x.range_report = nullptr;
+    if (c.range_report) {
+        // must be host memory the device can write (hipHostMalloc / a registered range): anything else would fault inside the kernel
+        hipPointerAttribute_t at{};
+        if (hipPointerGetAttributes(&at, c.range_report) != hipSuccess || at.type != hipMemoryTypeHost || at.devicePointer == nullptr) {
+            (void)hipGetLastError();
+            PDSC_REQUIRE_CALL(false, "range_report %p is not pinned, device-mapped host memory", (void*)c.range_report);
+        }
+        x.range_report = (unsigned int*)at.devicePointer;
+    }
     return PDSC_OK;
 }
 
 // layout, workspace size check, shared buffers and derived scalars (x.c and x.plan are set)
 static int bind_workspace(ForwardCtx& x) {
-    const ForwardCall& c = x.c;
+    const pdsc_forward_call& c = x.c;
     const WsLayout& L = x.L = make_layout(c.cfg, c.bs, c.N, c.num_seeds);
     if (c.workspace_bytes < L.total) {
-        set_error("pdsc_forward_testing: workspace %zu < %zu bytes", c.workspace_bytes, L.total);
+        set_error("pdsc_forward(%s): workspace %zu < %zu bytes", mode_name(c.mode), c.workspace_bytes, L.total);
         return PDSC_ERR_WORKSPACE;
     }
     void* ws = c.workspace;
-    x.st = (hipStream_t)c.stream;
+    x.st = x.main;
     x.M = c.bs * c.N; x.S = c.num_seeds; x.k = c.cfg->k < c.N - 1 ? c.cfg->k : c.N - 1;
     x.ld = pdsc_compat_ld(c.N);
     x.compat = L.at<float>(ws, WS_COMPAT); x.featA = L.at<float>(ws, WS_FEATA); x.featB = L.at<float>(ws, WS_FEATB);
@@ -543,32 +526,32 @@ static int bind_workspace(ForwardCtx& x) {
     x.seed_trans = L.at<float>(ws, WS_SEED_TRANS); x.seeds = L.at<int>(ws, WS_SEEDS); x.knn_idx = L.at<int>(ws, WS_KNN_IDX);
     x.counts = L.at<int>(ws, WS_COUNTS); x.conv_mask = L.at<unsigned int>(ws, WS_CONV_MASK); x.att_scratch = L.at<void>(ws, WS_ATT_SCRATCH);
     const bool split = x.split = x.plan.split;
-    PDSC_REQUIRE(!split || c.wsplit, "pdsc_forward_testing: the split-precision modes need the split-weight buffer (pdsc_wsplit_build)");
+    PDSC_REQUIRE_CALL(!split || c.wsplit, "the split-precision modes need the split-weight buffer (pdsc_wsplit_build)");
     x.q_split = split ? L.at<void>(ws, WS_Q_SPLIT) : nullptr;
     x.kv_tiles = split ? L.at<void>(ws, WS_KV_TILES) : nullptr;
     // fp16 range sentinel: zeroed by the layer0 launch, set by the layer kernels' conversion sites (LayerArgs.range_flag), read by
     // the refinement launch
-    x.range_flag = split && c.mode != ForwardMode::Probe ? L.at<unsigned int>(ws, WS_RANGE_FLAG) : nullptr;
+    x.range_flag = split && c.mode != PDSC_FORWARD_PROBE ? L.at<unsigned int>(ws, WS_RANGE_FLAG) : nullptr;
     x.cfmt = split && c.cfg->compat_format == PDSC_COMPAT_U16 ? PDSC_COMPAT_U16 : PDSC_COMPAT_F32;
     // (testing forward, large batches: the seeds' kNN runs fused -- knn_fused_kernel -- and takes the normalised rows in
     // point-fragment order too; normed_pf != NULL says so)
-    const bool knn_fused = c.mode == ForwardMode::Testing && knn_seeds_uses_fused(c.bs, c.N, x.S, x.k);
+    const bool knn_fused = c.mode == PDSC_FORWARD_TESTING && knn_seeds_uses_fused(c.bs, c.N, x.S, x.k);
     x.normed_pf = knn_fused ? L.at<float>(ws, WS_NORMED_PF) : nullptr;
     return PDSC_OK;
 }
 
 // Probe: slot[kind] := max(slot[kind], max |v|); every other mode: nothing
 static int probe_absmax(const ForwardCtx& x, int kind, const float* v, size_t count) {
-    return x.c.probe ? launch_absmax(v, count, x.c.probe + kind, x.st) : PDSC_OK;
+    return x.c.absmax ? launch_absmax(v, count, (unsigned int*)x.c.absmax + kind, x.st) : PDSC_OK;
 }
 
 // Step 1 (models/PointDSC.py:150-155): compat, then layer0 of the SCNonlocal encoder
 static int run_compat_layer0(const ForwardCtx& x) {
-    const ForwardCall& c = x.c;
+    const pdsc_forward_call& c = x.c;
     if (x.cfmt == PDSC_COMPAT_U16)
-        PDSC_TRY(pdsc_spatial_compat_u16(c.src, c.tgt, x.W(PDSC_W_SIGMA_SPAT, 0), (unsigned short*)x.compat, x.ld, c.bs, c.N, x.st));
+        PDSC_TRY(pdsc_spatial_compat_u16(c.src_keypts, c.tgt_keypts, x.W(PDSC_W_SIGMA_SPAT, 0), (unsigned short*)x.compat, x.ld, c.bs, c.N, x.st));
     else
-        PDSC_TRY(pdsc_spatial_compat(c.src, c.tgt, x.W(PDSC_W_SIGMA_SPAT, 0), x.compat, nullptr, x.ld, c.bs, c.N, x.st));
+        PDSC_TRY(pdsc_spatial_compat(c.src_keypts, c.tgt_keypts, x.W(PDSC_W_SIGMA_SPAT, 0), x.compat, nullptr, x.ld, c.bs, c.N, x.st));
     PDSC_TRY(launch_layer0(c.corr_pos, c.cfg->in_dim, x.W(PDSC_W_LAYER0_W, 0), x.W(PDSC_W_LAYER0_B, 0), x.featA, x.M, x.range_flag, c.bs, x.st));
     return probe_absmax(x, PDSC_RANGE_LAYER0, x.featA, (size_t)x.M * PDSC_CHANNELS);
 }
@@ -576,7 +559,7 @@ static int run_compat_layer0(const ForwardCtx& x) {
 // the row-order split attention: merged rows in msg_out, or (msg_out == NULL) the key-split partials left in att_scratch
 static int attention_split(const ForwardCtx& x, float* msg_out, int nsplit) {
     return launch_attention_split_ex(x.q_split, x.kv_tiles, x.compat, x.cfmt, x.ld, msg_out, x.att_scratch, x.L.bytes[WS_ATT_SCRATCH], x.c.bs,
-                                     x.c.N, nsplit, PDSC_PARTIALS_ROWS, x.c.nvalid, x.st);
+                                     x.c.N, nsplit, PDSC_PARTIALS_ROWS, x.c.num_corr, x.st);
 }
 
 // One fused launch: the tail of layer i (i = -1: none, the input is featA) and the head of layer i+1 (last: none, the result is
@@ -628,34 +611,34 @@ static int run_fused_layer(const ForwardCtx& x, int i, bool last, const float* c
     // the forward's own fields: EVERY launch reports to the range sentinel (NULL in exact fp32 and in the probe: bind_workspace);
     // the point-fragment route takes no trace (layer_args.h)
     LayerArgs a = layer_args_from_call(c);
-    a.nvalid = split ? x.c.nvalid : nullptr;
+    a.nvalid = split ? x.c.num_corr : nullptr;
     a.range_flag = x.range_flag;
     if (tail) a.part_slots = slots;
     if (plan.pf)
         a.value_fold = plan.fold;
     else
         a.trace = pdsc_layer_trace_buffer();
-    PDSC_TRY(validate_layer_args(a, plan.kernel, "pdsc_forward_testing(layer)"));
+    PDSC_TRY(validate_layer_args(a, plan.kernel, "pdsc_forward(layer)"));
     return dispatch_layer(a, plan.kernel, x.st);
 }
 
 // head of layer 0, then per layer: attention + ONE launch for the merge of the key-split partials (when they are left
 // un-merged), the tail of layer i and the head of layer i+1
 static int run_encoder_fused(const ForwardCtx& x) {
-    const ForwardCall& c = x.c;
+    const pdsc_forward_call& c = x.c;
     const EncoderPlan& plan = x.plan;
     const size_t att_bytes = x.L.bytes[WS_ATT_SCRATCH];
     PDSC_TRY(run_fused_layer(x, -1, false, nullptr, x.featB));
     float *cur = x.featB, *nxt = x.featC;
     for (int i = 0; i < c.cfg->num_layers; ++i) {
         if (!x.split)
-            PDSC_TRY(launch_attention_fp32(x.qkv, x.compat, x.ld, x.msg, x.att_scratch, att_bytes, c.bs, c.N, 0, c.nvalid, x.st));      // (r06: ragged batches too)
+            PDSC_TRY(launch_attention_fp32(x.qkv, x.compat, x.ld, x.msg, x.att_scratch, att_bytes, c.bs, c.N, 0, c.num_corr, x.st));      // (r06: ragged batches too)
         else if (plan.leaves)
             PDSC_TRY(launch_attention_leaves(x.q_split, x.kv_tiles, x.compat, x.cfmt, x.ld, x.att_scratch, att_bytes, c.bs, c.N,
-                                             c.cfg->att_leaves, c.nvalid, c.n_min, x.st, plan.value_width));
+                                             c.cfg->att_leaves, c.num_corr, c.n_min, x.st, plan.value_width));
         else if (plan.pf)
             PDSC_TRY(launch_attention_split_ex(x.q_split, x.kv_tiles, x.compat, x.cfmt, x.ld, nullptr, x.att_scratch, att_bytes, c.bs, c.N,
-                                               plan.ns, PDSC_PARTIALS_PF, c.nvalid, x.st, plan.value_width));
+                                               plan.ns, PDSC_PARTIALS_PF, c.num_corr, x.st, plan.value_width));
         else
             PDSC_TRY(attention_split(x, plan.fuse_merge ? nullptr : x.msg, plan.ns));
         PDSC_TRY(run_fused_layer(x, i, i + 1 == c.cfg->num_layers, cur, nxt));
@@ -690,30 +673,30 @@ static int run_encoder_per_conv(const ForwardCtx& x) {
     return PDSC_OK;
 }
 
-// pdsc_forward_testing_streams: everything after the encoder -- a strictly sequential chain of ~15 small, latency-bound
+// Two streams (pdsc_forward_call.tail_stream): everything after the encoder -- a strictly sequential chain of ~15 small, latency-bound
 // launches -- goes to the caller's second (high-priority) stream: with several forwards in flight its workgroups are then
 // dispatched ahead of the queued workgroups of another forward's attention launch instead of behind them.
 static int fork_tail(ForwardCtx& x) {
     if (!x.c.tail_stream) return PDSC_OK;
-    if (hipEventRecord((hipEvent_t)x.c.ev_fork, (hipStream_t)x.c.stream) != hipSuccess ||
-        hipStreamWaitEvent((hipStream_t)x.c.tail_stream, (hipEvent_t)x.c.ev_fork, 0) != hipSuccess)
-        return check_launch("pdsc_forward_testing_streams(fork)");
+    if (hipEventRecord((hipEvent_t)x.c.fork_event, x.main) != hipSuccess ||
+        hipStreamWaitEvent((hipStream_t)x.c.tail_stream, (hipEvent_t)x.c.fork_event, 0) != hipSuccess)
+        return check_launch("pdsc_forward(fork)");
     x.st = (hipStream_t)x.c.tail_stream;
     return PDSC_OK;
 }
 // join: whatever the caller enqueues on the main stream next is ordered after the results
 static int join_tail(const ForwardCtx& x) {
     if (!x.c.tail_stream) return PDSC_OK;
-    if (hipEventRecord((hipEvent_t)x.c.ev_join, (hipStream_t)x.c.tail_stream) != hipSuccess ||
-        hipStreamWaitEvent((hipStream_t)x.c.stream, (hipEvent_t)x.c.ev_join, 0) != hipSuccess)
-        return check_launch("pdsc_forward_testing_streams(join)");
+    if (hipEventRecord((hipEvent_t)x.c.join_event, (hipStream_t)x.c.tail_stream) != hipSuccess ||
+        hipStreamWaitEvent(x.main, (hipEvent_t)x.c.join_event, 0) != hipSuccess)
+        return check_launch("pdsc_forward(join)");
     return PDSC_OK;
 }
 
 // Step 2.1 (:156,:171,:174): confidence head, normalise, then the seeds: by NMS (Testing), or the top S by confidence next to the
 // feature similarity matrix (Validation, :158-163 and :176)
 static int run_seed_selection(const ForwardCtx& x) {
-    const ForwardCall& c = x.c;
+    const pdsc_forward_call& c = x.c;
     const int C = PDSC_CHANNELS, M = x.M;
     float *h1 = x.L.at<float>(c.workspace, WS_H1), *h2 = x.L.at<float>(c.workspace, WS_H2);
     if (env_int("PDSC_CLS_FUSED", 1))       // (A/B knob, experiments builds: 0 = the two pdsc_linear launches of r01-r03; same bits)
@@ -726,37 +709,37 @@ static int run_seed_selection(const ForwardCtx& x) {
         PDSC_TRY(launch_normalize_conf_pf(x.featA, h2, x.W(PDSC_W_CLS3_W, 0), x.W(PDSC_W_CLS3_B, 0), x.normed, x.normed_pf, x.conf, c.bs, c.N, x.st));
     else
         PDSC_TRY(pdsc_normalize_confidence(x.featA, h2, x.W(PDSC_W_CLS3_W, 0), x.W(PDSC_W_CLS3_B, 0), x.normed, x.conf, M, x.st));
-    if (c.mode == ForwardMode::Testing) {
-        PDSC_TRY(launch_nms_keys_grid(c.src, x.conf, c.cfg->nms_radius, x.keys, x.L.at<void>(c.workspace, WS_NMS_WS),
-                                      pdsc_nms_workspace_bytes(c.bs, c.N), c.bs, c.N, c.nvalid, x.st));
-        return launch_rank_select(x.keys, x.seeds, c.bs, c.N, x.S, c.nvalid, c.svalid, x.st, x.conv_mask);      // (+ the solver's mask := all-ones)
+    if (c.mode == PDSC_FORWARD_TESTING) {
+        PDSC_TRY(launch_nms_keys_grid(c.src_keypts, x.conf, c.cfg->nms_radius, x.keys, x.L.at<void>(c.workspace, WS_NMS_WS),
+                                      pdsc_nms_workspace_bytes(c.bs, c.N), c.bs, c.N, c.num_corr, x.st));
+        return launch_rank_select(x.keys, x.seeds, c.bs, c.N, x.S, c.num_corr, c.num_seeds_per_pair, x.st, x.conv_mask);      // (+ the solver's mask := all-ones)
     }
-    PDSC_TRY(pdsc_feature_compat(x.normed, x.W(PDSC_W_SIGMA, 0), c.Mout, c.ldM, c.bs, c.N, x.st));
+    PDSC_TRY(pdsc_feature_compat(x.normed, x.W(PDSC_W_SIGMA, 0), c.M, c.ldM, c.bs, c.N, x.st));
     return pdsc_rank_select(x.conf, x.seeds, c.bs, c.N, x.S, x.st);
 }
 
 // Step 3 & 4 (:182 -> :234-336): per-seed hypotheses and their scores
 static int run_hypotheses(const ForwardCtx& x) {
-    const ForwardCall& c = x.c;
-    const bool testing = c.mode == ForwardMode::Testing;
+    const pdsc_forward_call& c = x.c;
+    const bool testing = c.mode == PDSC_FORWARD_TESTING;
     const int iters = c.cfg->num_iterations;
     void* ws = c.workspace;
     float *knn_dist = x.L.at<float>(ws, WS_KNN_DIST), *eig = x.L.at<float>(ws, WS_EIG_ITERS), *seed_w = x.L.at<float>(ws, WS_SEED_W);
-    PDSC_TRY(launch_knn_seeds_form(x.normed, x.normed_pf, x.seeds, knn_dist, x.knn_idx, c.bs, c.N, x.S, x.k, c.nvalid, x.normed_pf ? 2 : 1, x.st));
+    PDSC_TRY(launch_knn_seeds_form(x.normed, x.normed_pf, x.seeds, knn_dist, x.knn_idx, c.bs, c.N, x.S, x.k, c.num_corr, x.normed_pf ? 2 : 1, x.st));
     if (!testing && c.bs > 1) {
         // validation forward: the early exit is taken over the seeds of ALL pairs of the batch (one torch.allclose over
         // [bs*S, k]) -- the per-pair masks are AND-ed before the iterate is chosen, so the two steps stay apart
-        PDSC_TRY(pdsc_seed_power_iteration(x.normed, c.src, c.tgt, x.knn_idx, x.W(PDSC_W_SIGMA, 0), x.W(PDSC_W_SIGMA_SPAT, 0), eig, x.conv_mask,
+        PDSC_TRY(pdsc_seed_power_iteration(x.normed, c.src_keypts, c.tgt_keypts, x.knn_idx, x.W(PDSC_W_SIGMA, 0), x.W(PDSC_W_SIGMA_SPAT, 0), eig, x.conv_mask,
                                            nullptr, c.bs, c.N, x.S, x.k, iters, x.st));
         PDSC_TRY(pdsc_conv_mask_all_pairs(x.conv_mask, c.bs, x.st));
-        PDSC_TRY(pdsc_seed_transforms(c.src, c.tgt, x.knn_idx, eig, x.conv_mask, x.seed_trans, seed_w, c.bs, c.N, x.S, x.k, iters, x.st));
+        PDSC_TRY(pdsc_seed_transforms(c.src_keypts, c.tgt_keypts, x.knn_idx, eig, x.conv_mask, x.seed_trans, seed_w, c.bs, c.N, x.S, x.k, iters, x.st));
     } else
-        PDSC_TRY(launch_seed_solve_forward(x.normed, c.src, c.tgt, x.knn_idx, x.W(PDSC_W_SIGMA, 0), x.W(PDSC_W_SIGMA_SPAT, 0), eig, x.conv_mask,
+        PDSC_TRY(launch_seed_solve_forward(x.normed, c.src_keypts, c.tgt_keypts, x.knn_idx, x.W(PDSC_W_SIGMA, 0), x.W(PDSC_W_SIGMA_SPAT, 0), eig, x.conv_mask,
                                            /*seed_M=*/nullptr, x.seed_trans, seed_w, c.bs, c.N, x.S, x.k, iters, /*mask_ready=*/testing, x.st));
 #ifdef PDSC_EXPERIMENTS
     score_debug_slot() = env_int("PDSC_SCORE_DEBUG", 0) ? x.L.at<float>(ws, WS_SCORE_DBG) : nullptr;
 #endif
-    PDSC_TRY(launch_score_hypotheses(x.seed_trans, c.src, c.tgt, c.cfg->inlier_threshold, x.counts, c.bs, c.N, x.S, c.nvalid, x.st));
+    PDSC_TRY(launch_score_hypotheses(x.seed_trans, c.src_keypts, c.tgt_keypts, c.cfg->inlier_threshold, x.counts, c.bs, c.N, x.S, c.num_corr, x.st));
 #ifdef PDSC_EXPERIMENTS
     score_debug_slot() = nullptr;
 #endif
@@ -766,32 +749,36 @@ static int run_hypotheses(const ForwardCtx& x) {
 // best hypothesis + its labels, then post refinement (:186 -> :403-438) in the same launch; final_labels stay those of the
 // pre-refinement best hypothesis
 static int finish_testing(const ForwardCtx& x) {
-    const ForwardCall& c = x.c;
+    const pdsc_forward_call& c = x.c;
     const WsLayout& L = x.L;
     void* ws = c.workspace;
-    return launch_select_and_refine(x.counts, x.seed_trans, c.src, c.tgt, c.cfg->inlier_threshold, c.cfg->refine_threshold, c.cfg->refine_iters,
+    return launch_select_and_refine(x.counts, x.seed_trans, c.src_keypts, c.tgt_keypts, c.cfg->inlier_threshold, c.cfg->refine_threshold, c.cfg->refine_iters,
                                     L.at<int>(ws, WS_BEST), L.at<float>(ws, WS_INITIAL_TRANS), c.final_labels, c.final_trans,
-                                    L.at<int>(ws, WS_SOLVES), c.bs, c.N, x.S, c.nvalid, x.st, L.at<int>(ws, WS_REFINE_TRACE), x.range_flag,
-                                    range_report_slot());
+                                    L.at<int>(ws, WS_SOLVES), c.bs, c.N, x.S, c.num_corr, x.st, L.at<int>(ws, WS_REFINE_TRACE), x.range_flag,
+                                    x.range_report);
 }
 // best hypothesis is the result (:186 is skipped); the labels of the call are the logits (:190-191).  pdsc_select_best does not know
 // the range sentinel: a launch of its own behind it turns the pose of every flagged pair into NaN, as the refinement launch of the
 // testing forward does
 static int finish_validation(const ForwardCtx& x) {
-    const ForwardCall& c = x.c;
-    PDSC_TRY(pdsc_select_best(x.counts, x.seed_trans, c.src, c.tgt, c.cfg->inlier_threshold, x.L.at<int>(c.workspace, WS_BEST), c.final_trans,
+    const pdsc_forward_call& c = x.c;
+    PDSC_TRY(pdsc_select_best(x.counts, x.seed_trans, c.src_keypts, c.tgt_keypts, c.cfg->inlier_threshold, x.L.at<int>(c.workspace, WS_BEST), c.final_trans,
                               x.keys /* scratch */, c.bs, c.N, x.S, x.st));
     if (x.range_flag) PDSC_TRY(launch_poison_flagged(c.final_trans, x.range_flag, c.bs, x.st));
     return launch_copy_u32((unsigned int*)c.final_labels, (const unsigned int*)x.conf, (size_t)x.M, x.st);
 }
 
-// The whole path: which mode runs which stage.  Every stage only enqueues (no host synchronisation, no allocation, no state).
-static int run_forward(const ForwardCall& call) {
-    const bool probe = call.mode == ForwardMode::Probe, testing = call.mode == ForwardMode::Testing;
-    ForwardCtx x{call};
-    PDSC_TRY(validate_call(call));
-    PDSC_TRY(plan_encoder(call.cfg, call.bs, call.N, call.nvalid, call.n_min, &x.plan));
+// The whole path: which mode runs which stage.  Nothing is enqueued before the call has passed every check (validate_call,
+// plan_encoder and bind_workspace launch nothing); every stage after them only enqueues (no host synchronisation, no allocation,
+// no state).
+extern "C" int pdsc_forward(const pdsc_forward_call* call, void* stream) {
+    PDSC_REQUIRE(call, "pdsc_forward: null call");
+    const bool probe = call->mode == PDSC_FORWARD_PROBE, testing = call->mode == PDSC_FORWARD_TESTING;
+    ForwardCtx x{*call, (hipStream_t)stream};
+    PDSC_TRY(validate_call(x));
+    PDSC_TRY(plan_encoder(call->cfg, call->bs, call->N, call->num_corr, call->n_min, &x.plan));
     PDSC_TRY(bind_workspace(x));
+    if (probe) PDSC_TRY(launch_fill_u32((unsigned int*)call->absmax, 0u, PDSC_RANGE_NUM_KINDS, x.st));
     PDSC_TRY(run_compat_layer0(x));
     PDSC_TRY(x.plan.fused && !probe ? run_encoder_fused(x) : run_encoder_per_conv(x));
     if (probe) return PDSC_OK;
@@ -800,59 +787,4 @@ static int run_forward(const ForwardCall& call) {
     PDSC_TRY(run_hypotheses(x));
     PDSC_TRY(testing ? finish_testing(x) : finish_validation(x));
     return join_tail(x);
-}
-
-extern "C" int pdsc_forward_testing(const pdsc_config* cfg, const float* wpack, const void* wsplit, const float* corr_pos,
-                                    const float* src, const float* tgt, int bs, int N, int num_seeds,
-                                    float* final_trans, float* final_labels, void* workspace, size_t workspace_bytes,
-                                    void* stream) {
-    return run_forward({.mode = ForwardMode::Testing, .cfg = cfg, .wpack = wpack, .wsplit = wsplit, .corr_pos = corr_pos, .src = src,
-                        .tgt = tgt, .bs = bs, .N = N, .num_seeds = num_seeds, .final_trans = final_trans, .final_labels = final_labels,
-                        .workspace = workspace, .workspace_bytes = workspace_bytes, .stream = stream});
-}
-
-extern "C" int pdsc_forward_testing_ragged(const pdsc_config* cfg, const float* wpack, const void* wsplit, const float* corr_pos,
-                                           const float* src, const float* tgt, int bs, int N, int num_seeds, const int* num_corr,
-                                           const int* num_seeds_per_pair, int n_min, float* final_trans, float* final_labels,
-                                           void* workspace, size_t workspace_bytes, void* stream) {
-    PDSC_REQUIRE(num_corr && num_seeds_per_pair, "pdsc_forward_testing_ragged: the per-pair count arrays (device, [bs] int32) are required");
-    return run_forward({.mode = ForwardMode::Testing, .cfg = cfg, .wpack = wpack, .wsplit = wsplit, .corr_pos = corr_pos, .src = src,
-                        .tgt = tgt, .bs = bs, .N = N, .num_seeds = num_seeds, .final_trans = final_trans, .final_labels = final_labels,
-                        .workspace = workspace, .workspace_bytes = workspace_bytes, .stream = stream, .nvalid = num_corr,
-                        .svalid = num_seeds_per_pair, .n_min = n_min});
-}
-
-extern "C" int pdsc_forward_testing_streams(const pdsc_config* cfg, const float* wpack, const void* wsplit, const float* corr_pos,
-                                            const float* src, const float* tgt, int bs, int N, int num_seeds, const int* num_corr,
-                                            const int* num_seeds_per_pair, int n_min, float* final_trans, float* final_labels,
-                                            void* workspace, size_t workspace_bytes, void* stream, void* tail_stream, void* fork_event,
-                                            void* join_event) {
-    PDSC_REQUIRE((num_corr == nullptr) == (num_seeds_per_pair == nullptr), "pdsc_forward_testing_streams: both count arrays or neither");
-    PDSC_REQUIRE(tail_stream && fork_event && join_event, "pdsc_forward_testing_streams: tail stream and both events are required");
-    return run_forward({.mode = ForwardMode::Testing, .cfg = cfg, .wpack = wpack, .wsplit = wsplit, .corr_pos = corr_pos, .src = src,
-                        .tgt = tgt, .bs = bs, .N = N, .num_seeds = num_seeds, .final_trans = final_trans, .final_labels = final_labels,
-                        .workspace = workspace, .workspace_bytes = workspace_bytes, .stream = stream, .nvalid = num_corr,
-                        .svalid = num_seeds_per_pair, .n_min = n_min, .tail_stream = tail_stream, .ev_fork = fork_event, .ev_join = join_event});
-}
-
-// Range probe for layer_gemm = PDSC_LAYER_GEMM_H3 (fp16 hi/lo operands: every activation of the chain must stay below 65504): the
-// encoder once with the fp32 GEMMs, one launch per conv, and the largest |value| of every activation kind over all layers.
-extern "C" int pdsc_encoder_range_probe(const pdsc_config* cfg, const float* wpack, const void* wsplit, const float* corr_pos,
-                                        const float* src, const float* tgt, int bs, int N, int num_seeds, float* absmax,
-                                        void* workspace, size_t workspace_bytes, void* stream) {
-    PDSC_REQUIRE(absmax, "pdsc_encoder_range_probe: absmax [PDSC_RANGE_NUM_KINDS] (device) required");
-    PDSC_TRY(launch_fill_u32((unsigned int*)absmax, 0u, PDSC_RANGE_NUM_KINDS, (hipStream_t)stream));
-    return run_forward({.mode = ForwardMode::Probe, .cfg = cfg, .wpack = wpack, .wsplit = wsplit, .corr_pos = corr_pos, .src = src, .tgt = tgt,
-                        .bs = bs, .N = N, .num_seeds = num_seeds, .workspace = workspace, .workspace_bytes = workspace_bytes, .stream = stream,
-                        .probe = (unsigned int*)absmax});
-}
-
-extern "C" int pdsc_forward_validation(const pdsc_config* cfg, const float* wpack, const void* wsplit, const float* corr_pos,
-                                       const float* src, const float* tgt, int bs, int N, int num_seeds,
-                                       float* final_trans, float* logits, float* Mout, long long ldM, void* workspace,
-                                       size_t workspace_bytes, void* stream) {
-    PDSC_REQUIRE(Mout && ldM >= N, "pdsc_forward_validation: M matrix [bs][N][ldM >= N] required");
-    return run_forward({.mode = ForwardMode::Validation, .cfg = cfg, .wpack = wpack, .wsplit = wsplit, .corr_pos = corr_pos, .src = src,
-                        .tgt = tgt, .bs = bs, .N = N, .num_seeds = num_seeds, .final_trans = final_trans, .final_labels = logits, .Mout = Mout,
-                        .ldM = ldM, .workspace = workspace, .workspace_bytes = workspace_bytes, .stream = stream});
 }

@@ -153,7 +153,7 @@ __global__ __launch_bounds__(NW * 64, 2) void sc_attention_split_kernel(AttSplit
         qb = rank % a.nq;
     }
     int sp = grp % a.nsplit, b = grp / a.nsplit;
-    // ragged batches (pdsc_forward_testing_ragged): this pair's own correspondence count -- its queries, its key tiles and the
+    // ragged batches (pdsc_forward_call.num_corr): this pair's own correspondence count -- its queries, its key tiles and the
     // mask of its last tile; buffer strides stay those of the longest pair.  (Not in the persistent form: one N per launch.)
     const int N = (!PS && a.nvalid) ? a.nvalid[b] : NS;
     if (!PS && qb * (NW * 32) >= N) return;      // query block entirely past this pair's rows (workgroup-uniform)

@@ -1,4 +1,4 @@
-// Ragged batches (pdsc_forward_testing_ragged): every pair of a batch has its own correspondence count n_b <= N and its own
+// Ragged batches (pdsc_forward_call.num_corr): every pair of a batch has its own correspondence count n_b <= N and its own
 // seed count s_b <= S, while every buffer keeps the strides of the longest pair (rows n_b .. N-1 of a pair are padding).
 // The stages whose result depends on the count -- attention (keys / queries), NMS, seed ranking, kNN columns, hypothesis
 // scoring, best-hypothesis labels, refinement -- take the device arrays `nvalid` / `svalid` ([bs] int32, NULL = uniform

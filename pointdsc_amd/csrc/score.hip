@@ -163,7 +163,7 @@ __global__ __launch_bounds__(512) void select_refine_kernel(const int* __restric
                                                             const unsigned int* __restrict__ range_flag, unsigned int* __restrict__ range_report) {
     __shared__ float Tb[16];
     const int b = blockIdx.x;
-    // (pdsc_set_range_report) the pair's range word also goes to pinned host memory: the caller that waits for the stream anyway reads
+    // (pdsc_forward_call.range_report) the pair's range word also goes to pinned host memory: the caller that waits for the stream anyway reads
     // it there without a copy of its own
     if (range_report && threadIdx.x == 0) range_report[b] = range_flag ? range_flag[b] : 0u;
     select_best_body<512>(counts, seed_trans, src, tgt, thr, best_out, initial_trans, labels, NS, S, nvalid, b, Tb);
@@ -227,9 +227,9 @@ int launch_post_refinement(const float* initial_trans, const float* src, const f
 }
 
 int launch_poison_flagged(float* final_trans, const unsigned int* range_flag, int bs, hipStream_t st) {
-    PDSC_REQUIRE(final_trans && range_flag && bs > 0, "pdsc_forward_validation(range sentinel): null pointer or bs=%d", bs);
+    PDSC_REQUIRE(final_trans && range_flag && bs > 0, "pdsc_forward(validation, range sentinel): null pointer or bs=%d", bs);
     hipLaunchKernelGGL(poison_flagged_kernel, dim3(ceil_div(bs * 16, 256)), dim3(256), 0, st, final_trans, range_flag, bs);
-    return check_launch("pdsc_forward_validation(range sentinel)");
+    return check_launch("pdsc_forward(validation, range sentinel)");
 }
 
 }  // namespace pdsc

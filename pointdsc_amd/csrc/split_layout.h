@@ -8,7 +8,7 @@
 // in fp32; the dropped a_lo*b_lo term is 2^-22 relative), i.e. three v_mfma_f32_32x32x16_f16 per operand pair = 3/16 of the cost of
 // the exact fp32 MFMA, ONE accumulator.  (r01-r04 carried bf16 hi/lo -- 8 + 8 bits, 2^-17 per operand: on trained KITTI-scale
 // weights that left the logits 6e-3 off, profiles/r05_f_kitti_stage_trained.txt; fp16 costs the same MFMAs and conversions and
-// needs |x| < 65504, which pdsc_encoder_range_probe checks for every activation that becomes such an operand.)
+// needs |x| < 65504, which the range probe (PDSC_FORWARD_PROBE) checks for every activation that becomes such an operand.)
 //
 //   Q stream : [bs*N][256] fp16   row = (hi[0..127] | lo[0..127]), natural channel order
 //   KV stream: [bs][ntiles][SPL_TILE_STRIDE]  one 32 KiB block (SPL_TILE_BYTES) per tile of 32 keys, laid out as the exact LDS image

@@ -9,7 +9,7 @@ Mirrors reference ``models/PointDSC.py``:
 so the reference's callers (evaluation/test_3DMatch.py:53, demo_registration.py:117) only swap the import.
 
 The sub-modules below are weight containers only; the arithmetic runs in libpointdsc_hip.so through
-``pdsc_forward_testing`` (include/pointdsc_hip.h).  There is no CPU or eager-PyTorch fallback: inputs
+``pdsc_forward`` (include/pointdsc_hip.h).  There is no CPU or eager-PyTorch fallback: inputs
 must be CUDA(ROCm) tensors and the library must be built, otherwise forward raises.
 
 Extension over the reference: testing mode accepts bs >= 1 (the reference asserts bs == 1,
@@ -170,7 +170,7 @@ class PointDSC(nn.Module):
         self._wpack_key = None
         self._workspace: Optional[torch.Tensor] = None
         self._h3_range_checked = False
-        self.last_range_probe = None            # {activation kind: largest |value|} of the last pdsc_encoder_range_probe
+        self.last_range_probe = None            # {activation kind: largest |value|} of the last range probe (PDSC_FORWARD_PROBE)
         self._tail: Dict[int, tuple] = {}       # workspace slot -> (high-priority tail stream, fork event, join event): pipeline.InFlight(tail_streams=True)
         self._workspaces: Dict[int, torch.Tensor] = {}      # one per in-flight slot (pointdsc_amd.pipeline.InFlight); slot 0 = the plain call
         self._ws_slot = 0
@@ -455,6 +455,16 @@ class PointDSC(nn.Module):
                 out.append(g)
         return out + small
 
+    @staticmethod
+    def _forward_call(cfg, wpack, wsplit, inputs, bs, n, num_seeds, ws) -> _lib.PdscForwardCall:
+        """struct pdsc_forward_call with what every mode needs; the caller sets the mode and its optional fields.  The struct holds
+        addresses only: the tensors stay the caller's to keep alive."""
+        corr_pos, src_keypts, tgt_keypts = inputs
+        return _lib.PdscForwardCall(
+            cfg=C.pointer(cfg), wpack=wpack.data_ptr(), wsplit=wsplit.data_ptr() if wsplit is not None else None,
+            corr_pos=corr_pos.data_ptr(), src_keypts=src_keypts.data_ptr(), tgt_keypts=tgt_keypts.data_ptr(),
+            bs=bs, N=n, num_seeds=num_seeds, workspace=ws.data_ptr(), workspace_bytes=ws.numel())
+
     def _run(self, corr_pos, src_keypts, tgt_keypts, testing, counts=None, _in_fallback=False):
         lib = _lib.load()
         dev = corr_pos.device
@@ -491,14 +501,13 @@ class PointDSC(nn.Module):
             ws = self._get_workspace(nbytes, dev)
             final_trans = torch.empty(bs, 4, 4, device=dev, dtype=torch.float32)
             final_labels = torch.empty(bs, n, device=dev, dtype=torch.float32)
-            wsp = C.c_void_p(wsplit.data_ptr()) if wsplit is not None else None
-            common = (C.byref(cfg), C.c_void_p(wpack.data_ptr()), wsp, C.c_void_p(corr_pos.data_ptr()),
-                      C.c_void_p(src_keypts.data_ptr()), C.c_void_p(tgt_keypts.data_ptr()), bs, n, num_seeds)
-            outs = (C.c_void_p(final_trans.data_ptr()), C.c_void_p(final_labels.data_ptr()))
-            stream = torch.cuda.current_stream().cuda_stream
+            call = self._forward_call(cfg, wpack, wsplit, (corr_pos, src_keypts, tgt_keypts), bs, n, num_seeds, ws)
+            call.mode = _lib.FORWARD_TESTING if testing else _lib.FORWARD_VALIDATION
+            call.final_trans, call.final_labels = final_trans.data_ptr(), final_labels.data_ptr()
             M = None
-            tail = self._tail.get(self._ws_slot) if testing else None
-            cnt = None
+            if not testing:
+                M = torch.empty(bs, n, n, device=dev, dtype=torch.float32)
+                call.M, call.ldM = M.data_ptr(), n
             if counts is not None:
                 seeds_per = [int(c * self.ratio) for c in counts]
                 if min(seeds_per) < 1:
@@ -507,35 +516,28 @@ class PointDSC(nn.Module):
                 if not hasattr(self, "_last_counts"):
                     self._last_counts = {}
                 self._last_counts[self._ws_slot] = cnt      # (keeps the device arrays alive until the slot's next call: the launches are asynchronous)
-            ragged = (C.c_void_p(cnt[0].data_ptr()), C.c_void_p(cnt[1].data_ptr()), min(counts)) if cnt is not None else (None, None, 0)
+                call.num_corr, call.num_seeds_per_pair, call.n_min = cnt[0].data_ptr(), cnt[1].data_ptr(), min(counts)
+            tail = self._tail.get(self._ws_slot) if testing else None
+            if tail is not None:
+                # encoder on the current stream, the latency-bound tail on the slot's high-priority stream
+                call.tail_stream, call.fork_event, call.join_event = tail[0].cuda_stream, tail[1].cuda_event, tail[2].cuda_event
             # "sync" range guard of a testing forward: the last launch writes the pairs' range words straight into pinned host memory
-            # (pdsc_set_range_report) -- no device-to-host copy of our own, only the wait
+            # (pdsc_forward_call.range_report) -- no device-to-host copy of our own, only the wait
             report = None
             if (testing and wsplit is not None and not _in_fallback and (self._guard_override or self.range_guard) == "sync"
                     and self._report_ok and not torch.cuda.is_current_stream_capturing()):
                 report = self._report_buffer(bs)
-                if lib.pdsc_set_range_report(C.c_void_p(report.data_ptr())) != 0:
-                    self._report_ok, report = False, None          # (not device-mapped on this platform: the copy path below)
-            try:
-                if tail is not None:
-                    # encoder on the current stream, the latency-bound tail on the slot's high-priority stream (pdsc_forward_testing_streams)
-                    rc = lib.pdsc_forward_testing_streams(*common, *ragged, *outs, C.c_void_p(ws.data_ptr()), nbytes, stream,
-                                                          tail[0].cuda_stream, tail[1].cuda_event, tail[2].cuda_event)
-                    what = "pdsc_forward_testing_streams"
-                elif cnt is not None:
-                    rc = lib.pdsc_forward_testing_ragged(*common, *ragged, *outs, C.c_void_p(ws.data_ptr()), nbytes, stream)
-                    what = "pdsc_forward_testing_ragged"
-                elif testing:
-                    rc = lib.pdsc_forward_testing(*common, *outs, C.c_void_p(ws.data_ptr()), nbytes, stream)
-                    what = "pdsc_forward_testing"
-                else:
-                    M = torch.empty(bs, n, n, device=dev, dtype=torch.float32)
-                    rc = lib.pdsc_forward_validation(*common, *outs, C.c_void_p(M.data_ptr()), n, C.c_void_p(ws.data_ptr()), nbytes, stream)
-                    what = "pdsc_forward_validation"
-            finally:
-                if report is not None:
-                    lib.pdsc_set_range_report(None)          # (thread-local in the library: never left pointing at this buffer)
-        _lib.check(rc, what)
+                call.range_report = report.data_ptr()
+            stream = torch.cuda.current_stream().cuda_stream
+            rc = lib.pdsc_forward(C.byref(call), stream)
+            if rc == _lib.ERR_ARG and report is not None:
+                # rejected by the checks in front of the first launch, so nothing is enqueued yet: once more without the buffer.  If
+                # that passes, pinned memory is not device-mapped on this platform: the copy path of _guard_after_forward from now on
+                call.range_report = None
+                rc = lib.pdsc_forward(C.byref(call), stream)
+                if rc == 0:
+                    self._report_ok, report = False, None
+        _lib.check(rc, "pdsc_forward")
         res = {"final_trans": final_trans, "final_labels": final_labels, "M": M}
         if wsplit is not None and not _in_fallback:
             redo = self._guard_after_forward(ws, cfg, bs, n, num_seeds, dev, report)
@@ -628,7 +630,7 @@ class PointDSC(nn.Module):
     def _h3_range_probe(self, corr_pos, src_keypts, tgt_keypts, counts=None) -> None:
         """layer_gemm = "h3" carries every operand of the fc_message / PointCN GEMMs as fp16 hi + lo, and (r05) so do the split-precision
         attention and q|k|v projection: EVERY activation of the chain, hidden ones included, must stay below 65504.  Once per weight packing, before the first forward: the encoder with the fp32
-        GEMMs, one launch per conv, and the largest |value| of every activation kind over all layers (pdsc_encoder_range_probe;
+        GEMMs, one launch per conv, and the largest |value| of every activation kind over all layers (pdsc_forward, PDSC_FORWARD_PROBE;
         one device -> host copy of 8 floats).  Out of range (or NaN): warn and keep layer_gemm = "f32" for this module.
         A heuristic, not a proof: it sees the first input only -- a later input with much larger activations is not re-checked
         (set model.layer_gemm = "f32" yourself for checkpoints whose activations approach 1e4)."""
@@ -652,11 +654,10 @@ class PointDSC(nn.Module):
                 return                               # (the forward itself reports the unsupported size)
             ws = self._get_workspace(nbytes, dev)
             absmax = torch.zeros(8, device=dev, dtype=torch.float32)
-            rc = lib.pdsc_encoder_range_probe(C.byref(cfg), C.c_void_p(wpack.data_ptr()), C.c_void_p(wsplit.data_ptr()),
-                                              C.c_void_p(corr_pos.data_ptr()), C.c_void_p(src_keypts.data_ptr()),
-                                              C.c_void_p(tgt_keypts.data_ptr()), bs, n, num_seeds, C.c_void_p(absmax.data_ptr()),
-                                              C.c_void_p(ws.data_ptr()), nbytes, torch.cuda.current_stream().cuda_stream)
-        _lib.check(rc, "pdsc_encoder_range_probe")
+            call = self._forward_call(cfg, wpack, wsplit, (corr_pos, src_keypts, tgt_keypts), bs, n, num_seeds, ws)
+            call.mode, call.absmax = _lib.FORWARD_PROBE, absmax.data_ptr()
+            rc = lib.pdsc_forward(C.byref(call), torch.cuda.current_stream().cuda_stream)
+        _lib.check(rc, "pdsc_forward")
         vals = absmax[: len(self.RANGE_KINDS)].tolist()
         self.last_range_probe = dict(zip(self.RANGE_KINDS, vals))
         bad = [(k, v) for k, v in zip(self.RANGE_KINDS, vals) if not v < 3.0e4]

@@ -4,7 +4,7 @@ refinement: a chain of ~15 small launches that occupy a few CUs) overlaps the co
 
 Measured on one MI355X (profiles/r03_b_overlap_probe.txt): 32 pairs of N=5000 per step 14.96 -> 14.57 ms, 4 pairs (the
 per-GPU share of the 8-GPU configuration) 2.06 -> 1.89 ms, one pair of N=1000 0.558 -> 0.354 ms per step.  Results are bit
-for bit those of the plain call: every forward is still one ``pdsc_forward_testing`` over its own workspace; only WHEN its
+for bit those of the plain call: every forward is still one ``pdsc_forward`` call over its own workspace; only WHEN its
 kernels run changes.  Weights (packed / split buffers) are shared and read-only.
 
     runner = InFlight(model, depth=2)
@@ -15,7 +15,7 @@ kernels run changes.  Weights (packed / split buffers) are shared and read-only.
                                            # t.record_stream(current) for result tensors that outlive the runner's next use
                                            # of the slot) before using res on another stream
 
-``tail_streams=True`` (default) enqueues each forward on TWO streams (``pdsc_forward_testing_streams``): the encoder on the
+``tail_streams=True`` (default) enqueues each forward on TWO streams (``pdsc_forward_call.tail_stream``): the encoder on the
 slot's stream, everything after it on a high-priority companion stream, so that the tail's few workgroups are dispatched ahead
 of the queued workgroups of the other slot's attention launch.  Measured, interleaved in one process, final build
 (profiles/r03_h_inflight_ab.txt, r03_i_inflight_ab.txt; ms per step: one stream / two plain streams / two streams + tail streams
@@ -26,7 +26,7 @@ final attention kernel (they did, 1.4-5 %, while its workgroups still reserved 1
 N=1000 lose 10 % with tail streams and take the hipGraph path below instead.  (Also tried and removed: holding forward i+1 back
 until forward i's encoder is done so that the two overlap tail-on-head -- as slow as one stream, r03_g.)
 
-``graphs=True`` additionally captures each slot's forward in a hipGraph (``pdsc_forward_testing`` only enqueues kernels: no
+``graphs=True`` additionally captures each slot's forward in a hipGraph (``pdsc_forward`` only enqueues kernels: no
 sync, no allocation) and replays it: the ~45 launches of a forward cost the host one call.  That only matters when a forward is
 launch-bound -- one pair of N=1000: 0.243 ms per forward with three eager forwards in flight, 0.149 ms with four captured ones
 (profiles/r03_e_graph_probe.txt); at 32 pairs of N=5000 it changes nothing.  Inputs are copied into per-slot static tensors,
@@ -81,7 +81,7 @@ class InFlight:
         self._slots = list(range(model._next_ws_slot, model._next_ws_slot + depth)) if depth > 1 else [0]
         if depth > 1:
             model._next_ws_slot += depth
-        # Each slot's forward is enqueued on two streams (pdsc_forward_testing_streams): the encoder on the slot's stream, the
+        # Each slot's forward is enqueued on two streams (pdsc_forward_call.tail_stream): the encoder on the slot's stream, the
         # latency-bound tail (classifier ... refinement: ~15 small launches) on a HIGH-priority companion stream, so that its few
         # workgroups are dispatched ahead of the queued workgroups of the other slot's attention launch.
         self.tail_streams = bool(tail_streams) and depth > 1 and not graphs     # (captured forwards are launch-bound problems: one stream)

@@ -309,7 +309,7 @@ def test_header_declares_fpfh_and_library_exports_it():
     for rule in ("FLANN_RADIUS_RULE", "COVARIANCE_ORDER_RULE", "NORMAL_SIGN_RULE"):
         assert rule in header, rule
     lib = _lib.load()
-    assert lib.pdsc_version() == 9
+    assert lib.pdsc_version() == int(re.search(r"#define\s+PDSC_VERSION\s+(\d+)", header).group(1)) == _lib.ABI_VERSION
     n, bs = 5333, 2
     assert lib.pdsc_fpfh_workspace_bytes(bs, n, 30, 100) >= bs * n * (30 * 4 + 100 * 12 + 33 * 8 + 16)
     assert lib.pdsc_hybrid_neighbours_workspace_bytes(bs, n) >= bs * n * 16

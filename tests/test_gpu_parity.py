@@ -2387,7 +2387,7 @@ def test_full_size_batch_properties():
 
 # ------------------------------------------------------------------------------------------------------
 # ragged batches (real evaluation pairs differ in N; reference evaluation/test_3DMatch.py:126,
-# datasets/dataloader.py:6-31) -- pdsc_forward_testing_ragged
+# datasets/dataloader.py:6-31) -- pdsc_forward with per-pair counts
 # ------------------------------------------------------------------------------------------------------
 def _ragged_pairs(sizes, seed0, **kw):
     return [synthetic.make_pair(n, seed=seed0 + i, **kw) for i, n in enumerate(sizes)]
@@ -2401,7 +2401,7 @@ def _as_lists(pairs):
 @pytest.mark.parametrize("sizes", [(3000, 4100, 5000, 5333), (5000, 4999, 4097, 4096, 4095, 3333, 2600, 5001),
                                    (1000, 777, 640, 999), (257, 300, 1000, 2053, 5000)])
 def test_ragged_batch_equals_the_single_pair_calls(sizes):
-    """A batch of pairs with different N through pdsc_forward_testing_ragged (lists of per-pair tensors) against the same pairs
+    """A batch of pairs with different N through the ragged pdsc_forward (lists of per-pair tensors) against the same pairs
     one call each: inlier masks bit-exact, R/t within 1e-4 for every pair and within 2e-5 for all but at most one pair of a
     batch (same stages on the same rows; only the launch plans -- fp32 summation orders -- are the batch's, and ~5 % of random
     pairs sit on a hypothesis near-tie that a summation order moves by a few 1e-5).  The last case is
@@ -2601,9 +2601,10 @@ def test_ragged_batch_with_pairs_of_at_most_k_rows():
     nb = int(lib.pdsc_workspace_bytes(C.byref(cfg), bs, n, S))
     ws = torch.empty(nb, device=DEV, dtype=torch.uint8)
     T, L = z(bs, 4, 4), z(bs, n)
-    P = lambda t: C.c_void_p(t.data_ptr())
-    rc = lib.pdsc_forward_testing_ragged(C.byref(cfg), P(model.packed_weights()), P(model.split_weights()), P(z(bs, n, 6)), P(z(bs, n, 3)),
-                                         P(z(bs, n, 3)), bs, n, S, P(cnt), P(sds), 30, P(T), P(L), P(ws), nb, torch.cuda.current_stream().cuda_stream)
+    call = model._forward_call(cfg, model.packed_weights(), model.split_weights(), (z(bs, n, 6), z(bs, n, 3), z(bs, n, 3)), bs, n, S, ws)
+    call.mode, call.final_trans, call.final_labels = _lib.FORWARD_TESTING, T.data_ptr(), L.data_ptr()
+    call.num_corr, call.num_seeds_per_pair, call.n_min = cnt.data_ptr(), sds.data_ptr(), 30
+    rc = lib.pdsc_forward(C.byref(call), torch.cuda.current_stream().cuda_stream)
     assert rc != 0 and "clamps k per pair" in _lib.last_error()
 
 
@@ -2830,7 +2831,7 @@ def test_h3_falls_back_to_fp32_gemms_outside_the_fp16_range():
     """layer_gemm = "h3" carries the operands of the fc_message / PointCN GEMMs as fp16 hi + lo (|x| < 65504).  A checkpoint whose
     folded weights or activations -- HIDDEN ones included -- leave that range must not produce inf / NaN silently: the module
     checks the packed weights and, before the first forward after packing, every activation kind of every layer
-    (pdsc_encoder_range_probe), warns and continues with the fp32 GEMMs."""
+    (pdsc_forward, PDSC_FORWARD_PROBE), warns and continues with the fp32 GEMMs."""
     kw = dict(KW, num_layers=2)
     pair = synthetic.make_pair(400, inlier_ratio=0.4, seed=3)
     # only a HIDDEN activation out of range, every folded weight far below the weight check's 3e4: v x 1e4 makes the message ~1e3-1e4,

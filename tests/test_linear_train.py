@@ -57,7 +57,7 @@ def test_public_names_and_signatures():
         args = re.search(rf"\b{name}\s*\((.*?)\)\s*;", header, flags=re.S).group(1)
         assert len(_lib.SIGNATURES[name][1]) == len(args.split(",")), name
         assert hasattr(lib, name)
-    assert lib.pdsc_version() == 9
+    assert lib.pdsc_version() == int(re.search(r"#define\s+PDSC_VERSION\s+(\d+)", header).group(1)) == _lib.ABI_VERSION
     q = lib.pdsc_linear_train_workspace_bytes
     assert q(0, 64, 128) == 0 and q(258, 17, 128) == 0 and q(258, 0, 128) == 0 and q(258, 64, 96) == 0 and q(258, 128, 128) == 0
     for cin in (1, 3, 6, 16, 64):

@@ -148,7 +148,7 @@ def test_header_declares_multiway_entries_and_library_exports_them():
         assert name in _lib.SIGNATURES, name
         assert re.search(rf"\bT {name}\b", out), name
     lib = _lib.load()
-    assert lib.pdsc_version() == 9
+    assert lib.pdsc_version() == int(re.search(r"#define\s+PDSC_VERSION\s+(\d+)", header).group(1)) == _lib.ABI_VERSION
     assert lib.pdsc_information_workspace_bytes(2, 5000, 4000) >= 2 * 4000 * 16
     assert lib.pdsc_information_workspace_bytes(0, 10, 10) == 0
     # argument validation happens before any HIP call

@@ -3,7 +3,7 @@
 
     python tools/graph_probe.py [--config n1000_b1]
 
-pdsc_forward_testing only enqueues kernels (no sync, no allocation), so a forward is capturable as is: the probe captures
+pdsc_forward only enqueues kernels (no sync, no allocation), so a forward is capturable as is: the probe captures
 `model(data)` with torch.cuda.CUDAGraph (static inputs / outputs), checks the replay reproduces the eager result bit for
 bit, and times eager calls against graph replays, each as a long back-to-back run on one stream.
 """

@@ -4,7 +4,7 @@
     python tools/parity_census.py [--only NAME] [--batches 1,2,4,8,16,32] [--compat-format u16|f32] [--layer-gemm h3|f32] [--json]
 
 Fixtures: tests/golden/census_<name>.npz (oracle/make_census_goldens.py: for every pair the reference's pose and label mask as
-shipped (fp32) and with the default dtype switched to fp64).  Every pair is run through pdsc_forward_testing with the module's
+shipped (fp32) and with the default dtype switched to fp64).  Every pair is run through pdsc_forward with the module's
 shipped defaults (or the overrides), in consecutive batches of each requested size -- the batch size selects the attention's
 key-split plan and the layer kernel, i.e. the summation orders -- and held to BASELINE.json's contract:
     labels bit-exact and max|dT| < 1e-4 against the reference's fp32 output,

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Where does a GPU forward leave the oracle?  Runs one pair of a bench workload through pdsc_forward_testing (inside a
+"""Where does a GPU forward leave the oracle?  Runs one pair of a bench workload through pdsc_forward (inside a
 batch of --bs pairs, position 0) and through the CPU oracle with stages, and prints the first stage that differs.
 
     python tools/stage_diff.py --config n1000_b1 --pair 0 [--bs 1] [--precision fp16x3|fp32]
