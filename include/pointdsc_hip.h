@@ -432,7 +432,9 @@ int pdsc_rank_select(const float* keys, int* seeds, int bs, int N, int num_seeds
  * replaces knn(..., ignore_self=True, normalized=True) + the seed gather
  * (models/common.py:48-69, models/PointDSC.py:250-252); only the seed rows are computed.
  *   dist[s][j] = 2 - 2 * <normed[seed_s], normed[j]>;  knn_idx[s][0:k] = ranks 1..k of ascending
- *   (dist, index) order (rank 0 dropped exactly like `[:, :, 1:]`).
+ *   (dist, index) order (rank 0 dropped exactly like `[:, :, 1:]`).  A NaN distance (a NaN in a feature row) ranks after every
+ *   number whatever its sign, as torch.sort orders it: as long as a seed keeps k + 1 finite distances both forms return the
+ *   same finite neighbours; with fewer the remaining slots are unspecified.
  * dist_scratch: [bs][S][ldd] floats, ldd = pdsc_compat_ld(N).  knn_idx: [bs][S][k] int32.
  * NOTE: pdsc_knn_seeds = pdsc_knn_seeds_form(form 0): for large batches (bs * ceil(S / 32) >= 384) the library takes the fused
  * form, which never writes dist_scratch -- its contents are then UNDEFINED.  A caller that wants the S x N distances back calls

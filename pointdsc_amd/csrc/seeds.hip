@@ -418,7 +418,10 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_select_kernel(const float* __
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 if (j + e < N) {
-                    const unsigned int kb = float_order_bits(part[u][e]);
+                    // a NaN distance (a NaN feature) ranks last whatever its sign, as torch.sort has it and as the fused form's
+                    // `v <= tau` does: float_order_bits alone puts a NaN with the sign bit set BEFORE every number (f-23)
+                    const float dv = part[u][e];
+                    const unsigned int kb = dv != dv ? 0xFFFFFFFFu : float_order_bits(dv);
                     keys[j + e] = kb;
                     const unsigned long long v = ((unsigned long long)kb << idx_bits) | (unsigned)(j + e);
                     mymin = v < mymin ? v : mymin;
