@@ -38,6 +38,17 @@ struct AttSplitArgs {
 };
 
 
+// Running row maximum over four more logits: mx = max(mx, a, b, c, d) as a chain of two three-operand maxima (v_max3_f32 each)
+// instead of the tree fmaxf(fmaxf(mx, fmaxf(a, b)), fmaxf(c, d)), which the backend keeps as written -- with one quieting
+// v_max_f32 x, x per leaf on top: 28 instructions for the 16 logits of a tile against 8.  max is exact and does not depend on the
+// order of its operands, and both forms drop a quiet NaN operand (the logits come out of v_fma_f32 / v_mul_f32, which return no
+// signalling one): the same value bit for bit.  Every path of the split kernel that needs
+// a row maximum (the three compat modes of phase B, the first tile, a leaf boundary, the ragged last tile) goes through this one.
+__device__ __forceinline__ float row_max4(float mx, float a, float b, float c, float d) {
+    mx = __builtin_fmaxf(__builtin_fmaxf(mx, a), b);
+    return __builtin_fmaxf(__builtin_fmaxf(mx, c), d);
+}
+
 typedef __attribute__((address_space(1))) const void* gptr_t;
 typedef __attribute__((address_space(3))) void* lptr_t;
 

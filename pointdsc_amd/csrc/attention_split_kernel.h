@@ -398,9 +398,9 @@ __global__ __launch_bounds__(NW * 64, 2) void sc_attention_split_kernel(AttSplit
         return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
     };
     auto row_max = [&](const float (&tl)[16]) {
-        float m = tl[0];
+        float m = -INFINITY;
 #pragma unroll
-        for (int r = 1; r < 16; ++r) m = fmaxf(m, tl[r]);
+        for (int g = 0; g < 4; ++g) m = row_max4(m, tl[4 * g], tl[4 * g + 1], tl[4 * g + 2], tl[4 * g + 3]);
         return half_max(m);
     };
 
@@ -610,21 +610,21 @@ __global__ __launch_bounds__(NW * 64, 2) void sc_attention_split_kernel(AttSplit
                         c16_group(cw, g, cc);
 #pragma unroll
                         for (int e = 0; e < 4; ++e) tl[4 * g + e] = fmaf(cc[e], sacc[4 * g + e], -m_sub);
-                        mx_next = fmaxf(fmaxf(mx_next, fmaxf(tl[4 * g], tl[4 * g + 1])), fmaxf(tl[4 * g + 2], tl[4 * g + 3]));
+                        mx_next = row_max4(mx_next, tl[4 * g], tl[4 * g + 1], tl[4 * g + 2], tl[4 * g + 3]);
                     }
                 } else if (CREG) {
                     if (u & 1) {
                         const int g = u >> 1;
 #pragma unroll
                         for (int e = 0; e < 4; ++e) tl[4 * g + e] = fmaf(ccur[g][e], sacc[4 * g + e], -m_sub);
-                        mx_next = fmaxf(fmaxf(mx_next, fmaxf(tl[4 * g], tl[4 * g + 1])), fmaxf(tl[4 * g + 2], tl[4 * g + 3]));
+                        mx_next = row_max4(mx_next, tl[4 * g], tl[4 * g + 1], tl[4 * g + 2], tl[4 * g + 3]);
                     }
                 } else if (u & 1) {              // compat chunk 2g+h = keys 8g+4h..+3 = accumulator registers 4g..4g+3
                     const int g = u >> 1;
                     const f32x4 cc = *reinterpret_cast<const f32x4*>(Cn + (((2 * g + h) ^ csw) << 4));
 #pragma unroll
                     for (int e = 0; e < 4; ++e) tl[4 * g + e] = fmaf(cc[e], sacc[4 * g + e], -m_sub);
-                    mx_next = fmaxf(fmaxf(mx_next, fmaxf(tl[4 * g], tl[4 * g + 1])), fmaxf(tl[4 * g + 2], tl[4 * g + 3]));
+                    mx_next = row_max4(mx_next, tl[4 * g], tl[4 * g + 1], tl[4 * g + 2], tl[4 * g + 3]);
                 }
                 vh = nvh; vl = nvl;
                 __builtin_amdgcn_sched_barrier(0);
