@@ -12,7 +12,7 @@
  *     ragged, on one or two streams; validation forward; range probe); the weight packers pdsc_wpack_floats / _offset,
  *     pdsc_wsplit_bytes / _offset / _build; the workspace queries pdsc_workspace_bytes / _offset; pdsc_version / pdsc_last_error; and, for the callers either
  *     side of the path (SURVEY.md section 8 f-2 .. f-4), pdsc_match_* / pdsc_select_correspondences / pdsc_build_corr_pos,
- *     pdsc_sm_baseline*, pdsc_pmc_*, pdsc_cal_confidence, pdsc_eval_stats, pdsc_*_loss*, pdsc_pointwise_train_*, pdsc_icp_*, pdsc_information_*, pdsc_voxel_*, pdsc_cloud_*.
+ *     pdsc_sm_baseline*, pdsc_pmc_*, pdsc_cal_confidence, pdsc_eval_stats, pdsc_*_loss*, pdsc_pointwise_train_*, pdsc_optim_*, pdsc_icp_*, pdsc_information_*, pdsc_voxel_*, pdsc_cloud_*.
  *   STAGE LEVEL -- one entry point per reference stage (sections a-1 .. a-11 below), the plan / size queries that go with them,
  *     pdsc_selftest_* and the diagnostic hooks.  The forward does not go through them (it calls the same launchers directly); they
  *     exist so that every stage can be parity-checked on its own (tests/test_gpu_parity.py), for the tools, and for a maintainer
@@ -1245,6 +1245,71 @@ int pdsc_head_train_forward(const float* X, const float* W0, const float* b0, co
 int pdsc_head_train_backward(const float* X, const float* W0, const float* b0, const float* W1, const float* b1, const float* W2,
                              const float* dlogits, float* dX, float* dW0, float* db0, float* dW1, float* db1, float* dW2, float* db2,
                              void* ws, size_t ws_bytes, int M, void* stream);
+
+/* ---- the trainer's update on the device: finite-gradient guard, Adam or SGD, skip decision (DESIGN.md section 8 f-25;
+ *      reference train_3DMatch.py:48-66 and the guard of libs/trainer.py:123-130) -------------------------------------------------
+ * THE RULE.  All tensor arithmetic is fp32 round-to-nearest with NO fused multiply-add: every product and every sum below is its
+ * own rounding (the library is built with -ffp-contract=off); `/` and sqrt are the correctly rounded ones.  A numpy float32
+ * program that says the same reproduces the kernels bit for bit (tests/optimizer_oracle.py).
+ *   Adam (torch.optim.Adam with L2 weight_decay added to the gradient -- not AdamW --, no amsgrad, no maximize), for a tensor
+ *   that has taken t - 1 successful steps:
+ *     b1pow = b1pow beta1;  b2pow = b2pow beta2                          (fp64 running products, 1.0 when fresh)
+ *     step32 = fp32(lr / (1 - b1pow));  sq32 = fp32(sqrt(1 - b2pow))     (fp64, then one rounding)
+ *     B1 = fp32(beta1), OB1 = fp32(1 - beta1), B2 = fp32(beta2), OB2 = fp32(1 - beta2), E = fp32(eps), WD = fp32(weight_decay)
+ *     g1 = g + WD p   (g1 = g when weight_decay == 0)
+ *     m' = B1 m + OB1 g1;   v' = B2 v + (OB2 g1) g1;   d = sqrt(v') / sq32 + E;   p' = p - step32 (m' / d)
+ *   SGD (torch.optim.SGD, dampening 0, no nesterov):
+ *     g1 as above;  buf' = g1 on the tensor's first successful step, else fp32(momentum) buf + g1;  p' = p - fp32(lr) buf'
+ *     momentum == 0: no buffer is touched, p' = p - fp32(lr) g1.
+ *   Guard: when any element of any PRESENT gradient of any group of the step is NaN or +-Inf, the whole step changes nothing
+ *   (parameters, moments, step counts and running products keep their bits) and the skipped counter goes up by one.  Parameters
+ *   are not looked at.  A tensor whose grad is NULL is left out of the step: its values, step count and products stand still --
+ *   step counts are per tensor.
+ * ONE STEP is, in stream order: pdsc_optim_check of every group, pdsc_optim_update of every group, pdsc_optim_finish of every
+ * group with `last` = 1 on the last one only.  check sets guard[0] when it sees a non-finite element (identical plain stores);
+ * update returns at once when guard[0] is set and reads the per-tensor step state WITHOUT writing it (a tensor spans several
+ * workgroups: all of them compute the new products from the old state); finish commits the step state of the present tensors
+ * (unless guard[0] is set) and, with `last`, adds guard[0] to guard[1] (skipped steps), adds 1 to guard[2] (calls) and clears
+ * guard[0].  Nothing clears the flag while a launch of the same step may still read or set it.  With use_guard == 0 no check is
+ * needed and the flag is ignored.
+ * `tensors` is a HOST table; every launch copies up to pdsc_optim_tensors_per_launch() of its rows into its kernel arguments
+ * (synchronously: the caller may reuse the table at once), so a step is 3 ceil(count / that) launches whatever the tensors' sizes,
+ * and parameters and gradients may live anywhere.  param and grad need 4-byte alignment only (16-byte accesses are used where
+ * both allow them, the same bits either way).
+ * `state` (device, 16-byte aligned, pdsc_optim_state_bytes(kind, numel[], count) bytes, opaque, zero-filled = fresh) holds the
+ * step state {b1pow, b2pow (fp64), step (int64), unused} of every tensor, 32 bytes each, then per tensor m | v (Adam) or buf
+ * (SGD), each padded to a multiple of 4 floats.  `guard` is 4 device uint32 {flag, skipped, calls, unused}, zero-filled by the
+ * caller once.
+ * All three are enqueue-only: no host synchronisation, no allocation, no memset; repeat calls are bit-identical.  PDSC_ERR_ARG
+ * before any HIP call, with the text in pdsc_last_error(): null call / table / state / guard / param, a pointer that is not
+ * 4-byte aligned (state: 16), count < 1, numel < 1 or >= 2^31, state_bytes too small, unknown kind, lr / beta1 / beta2 / eps /
+ * weight_decay / momentum non-finite or outside what torch accepts (lr, eps, weight_decay, momentum >= 0; 0 <= beta < 1).
+ * pdsc_optim_state_bytes returns 0 for bad arguments. */
+enum pdsc_optim_kind { PDSC_OPTIM_ADAM = 0, PDSC_OPTIM_SGD = 1 };
+
+typedef struct pdsc_optim_tensor {
+    float* param;            /* device, numel floats */
+    const float* grad;       /* device, numel floats; NULL: absent at this step */
+    long long numel;
+} pdsc_optim_tensor;
+
+typedef struct pdsc_optim_call {
+    int kind;                            /* enum pdsc_optim_kind */
+    int count;                           /* rows of `tensors`: all tensors of one parameter group, in a fixed order */
+    const pdsc_optim_tensor* tensors;    /* HOST */
+    void* state;
+    size_t state_bytes;
+    unsigned int* guard;
+    int use_guard;                       /* 0 / 1 */
+    int reserved;                        /* 0 */
+    double lr, beta1, beta2, eps, weight_decay, momentum;      /* Adam reads lr, betas, eps, weight_decay; SGD lr, momentum, weight_decay */
+} pdsc_optim_call;
+
+size_t pdsc_optim_state_bytes(int kind, const long long* numel, int count);
+int pdsc_optim_tensors_per_launch(void);
+int pdsc_optim_check(const pdsc_optim_call* call, void* stream);
+int pdsc_optim_update(const pdsc_optim_call* call, void* stream);
+int pdsc_optim_finish(const pdsc_optim_call* call, int last, void* stream);
 
 #ifdef __cplusplus
 }

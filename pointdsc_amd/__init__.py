@@ -16,6 +16,8 @@ Only what the path needs lives here:
                matrix (``feature_similarity``), the differentiable per-seed solver (``seed_solve``), the fused train-mode point-wise
                layer (``conv_bn_relu``), the train path's plain linears (``linear_rows``, ``qkv_projection``,
                ``classification_head``), the train()-mode forward (``train_forward``) and ``TrainablePointDSC``
+  optim.py     the trainer's update on the device: ``DeviceAdam`` / ``DeviceSGD`` (finite-gradient guard, update and skip decision
+               in a handful of multi-tensor launches, nothing read back)
   multiway.py  the multiway driver's edge step (information matrix + overlap gate, voxel down-sampling, multi-scale ICP) and its
                pose-graph optimisation (node chain, LM with line process, edge pruning) on the device
   sharding.py  one-process-per-GPU sharding of pair batches + the single RCCL pose gather
@@ -30,6 +32,7 @@ from .losses import ClassificationLoss, SpectralMatchingLoss, TransformationLoss
 from .model import PointDSC  # noqa: F401
 from .training import (NonLocalBlock, TrainablePointDSC, classification_head, conv_bn_relu, feature_similarity,  # noqa: F401
                        linear_rows, qkv_projection, sc_attention, seed_solve, train_forward)
+from .optim import DeviceAdam, DeviceSGD  # noqa: F401
 from .multiway import (align, global_optimization, information_matrix, local_refinement, loop_closure_edge,  # noqa: F401
                        multi_scale_icp, pose_graph_nodes, voxel_down_sample)
 
@@ -38,4 +41,5 @@ __all__ = ["PointDSC", "icp_refine", "registration_icp", "information_matrix", "
            "fpfh_descriptors", "voxel_down_sample_with_normals", "extract_fpfh_features", "pose_graph_nodes", "global_optimization",
            "ClassificationLoss", "SpectralMatchingLoss", "TransformationLoss", "NonLocalBlock", "sc_attention",
            "TrainablePointDSC", "train_forward", "feature_similarity", "seed_solve", "conv_bn_relu",
-           "linear_rows", "qkv_projection", "classification_head", "build_correspondences_batch", "CorrPool", "ransac_correspondence"]
+           "linear_rows", "qkv_projection", "classification_head", "build_correspondences_batch", "CorrPool", "ransac_correspondence",
+           "DeviceAdam", "DeviceSGD"]

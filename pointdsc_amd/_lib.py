@@ -63,7 +63,23 @@ class PdscForwardCall(C.Structure):
         [(n, _vp) for n in ("tail_stream", "fork_event", "join_event", "absmax", "range_report")])
 
 
-ABI_VERSION = 10        # PDSC_VERSION of include/pointdsc_hip.h that this table binds
+OPTIM_ADAM, OPTIM_SGD = 0, 1        # enum pdsc_optim_kind
+
+
+class PdscOptimTensor(C.Structure):
+    """struct pdsc_optim_tensor (include/pointdsc_hip.h): one row of a step's host table; grad None = absent.  Three 8-byte words,
+    so an int64 array [count, 3] is the same table."""
+    _fields_ = [("param", _vp), ("grad", _vp), ("numel", _ll)]
+
+
+class PdscOptimCall(C.Structure):
+    """struct pdsc_optim_call (include/pointdsc_hip.h): one parameter group's part of an optimiser step."""
+    _fields_ = ([("kind", _i), ("count", _i), ("tensors", _vp), ("state", _vp), ("state_bytes", _sz), ("guard", _vp),
+                 ("use_guard", _i), ("reserved", _i)] +
+                [(n, C.c_double) for n in ("lr", "beta1", "beta2", "eps", "weight_decay", "momentum")])
+
+
+ABI_VERSION = 10       # PDSC_VERSION of include/pointdsc_hip.h that this table binds
 
 # name -> (restype, argtypes); must list every function include/pointdsc_hip.h declares
 SIGNATURES = {
@@ -205,6 +221,11 @@ SIGNATURES = {
     "pdsc_feature_compat": (_i, [_vp, _vp, _vp, _ll, _i, _i, _vp]),
     "pdsc_conv_mask_all_pairs": (_i, [_vp, _i, _vp]),
     "pdsc_forward": (_i, [C.POINTER(PdscForwardCall), _vp]),
+    "pdsc_optim_state_bytes": (_sz, [_i, _vp, _i]),
+    "pdsc_optim_tensors_per_launch": (_i, []),
+    "pdsc_optim_check": (_i, [C.POINTER(PdscOptimCall), _vp]),
+    "pdsc_optim_update": (_i, [C.POINTER(PdscOptimCall), _vp]),
+    "pdsc_optim_finish": (_i, [C.POINTER(PdscOptimCall), _i, _vp]),
 }
 
 _lib = None

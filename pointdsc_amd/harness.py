@@ -527,7 +527,8 @@ def train_epoch(model, batches: Iterable[Dict[str, torch.Tensor]], optimizer, we
     """``Trainer.train_epoch`` (libs/trainer.py:79-136) on the device: for every batch (the dict ``validate`` takes) zero_grad, the
     train()-mode forward of `model` (a ``training.TrainablePointDSC`` in train() mode), the three losses of pointdsc_amd.losses,
     ``weights[0] class_loss + weights[1] sm_loss``, backward, and the reference's rule that the optimiser step is skipped when any
-    gradient is non-finite (one boolean per step is read for it, as the reference reads one).  `balanced` is the reference's
+    gradient is non-finite (one boolean per step is read for it, as the reference reads one; with a ``pointdsc_amd.DeviceAdam`` /
+    ``DeviceSGD`` whose guard is on, the optimiser makes that decision on the device and the loop reads nothing back).  `balanced` is the reference's
     config.balanced (default False).  ``weights[2]`` is the reference's weight_transformation (libs/trainer.py:105-107; default 0.0,
     and the caller keeps it 0 until transformation_loss_start_epoch): above 0 the model must have been built with
     ``differentiable_trans=True``, so that its final_trans carries a gradient, and ``weights[2] * trans_loss`` joins the objective;
@@ -535,6 +536,7 @@ def train_epoch(model, batches: Iterable[Dict[str, torch.Tensor]], optimizer, we
     -> the nine meters of the reference (running means kept on the device in fp64, NaN values skipped, as in ``validate``), and
     "loss_first" / "loss_last" (the weighted sum at the first and the last step), "steps", "skipped" -- ONE read-back at the end."""
     from .losses import ClassificationLoss, SpectralMatchingLoss, TransformationLoss, transformation_loss_raw
+    from .optim import DeviceAdam, DeviceSGD
     w_cls, w_sm, w_tr = (float(w) for w in weights)
     if w_tr > 0.0 and not getattr(model, "differentiable_trans", False):
         raise NotImplementedError("a transformation-loss weight above 0 needs a final_trans with a gradient: build the model as "
@@ -547,6 +549,10 @@ def train_epoch(model, batches: Iterable[Dict[str, torch.Tensor]], optimizer, we
     sums = torch.zeros(len(VALIDATE_NAMES), device=dev, dtype=torch.float64)
     counts = torch.zeros(len(VALIDATE_NAMES), device=dev, dtype=torch.float64)
     totals, steps, skipped = [], 0, 0
+    # a DeviceAdam / DeviceSGD with its guard on decides the skip on the device: no boolean is read inside the loop, and the number
+    # of skipped steps (its device counter, now minus at entry) joins the one read-back at the end
+    on_device = isinstance(optimizer, (DeviceAdam, DeviceSGD)) and optimizer.guard
+    skipped_at_entry = optimizer.skipped_steps() if on_device else None
     for batch in batches:
         d = {k: v.to(dev) for k, v in batch.items() if torch.is_tensor(v)}
         gt = d["gt_labels"]
@@ -561,11 +567,14 @@ def train_epoch(model, batches: Iterable[Dict[str, torch.Tensor]], optimizer, we
             tr = tr_fn(res["final_trans"], d["gt_trans"], d["src_keypts"], d["tgt_keypts"], logits, device_stats=True)
             loss = loss + w_tr * tr[0]
         loss.backward()
-        grads = [p.grad for p in params if p.grad is not None]
-        if bool(torch.stack([torch.isfinite(g).all() for g in grads]).all()):
+        if on_device:
             optimizer.step()
         else:
-            skipped += 1
+            grads = [p.grad for p in params if p.grad is not None]
+            if bool(torch.stack([torch.isfinite(g).all() for g in grads]).all()):
+                optimizer.step()
+            else:
+                skipped += 1
         steps += 1
         with torch.no_grad():
             if tr is None:
@@ -578,7 +587,12 @@ def train_epoch(model, batches: Iterable[Dict[str, torch.Tensor]], optimizer, we
             totals.append(loss.detach().double())
     if not steps:
         raise ValueError("train_epoch: no batch")
-    out = torch.cat([sums / counts, torch.stack([totals[0], totals[-1]])]).cpu().tolist()          # the one read-back
+    tail = [totals[0], totals[-1]]
+    if on_device:
+        tail.append((optimizer.skipped_steps() - skipped_at_entry).double())
+    out = torch.cat([sums / counts, torch.stack(tail)]).cpu().tolist()          # the one read-back
+    if on_device:
+        skipped = int(out.pop())
     res = dict(zip(VALIDATE_NAMES, out))
     res.update(loss_first=out[-2], loss_last=out[-1], steps=steps, skipped=skipped)
     return res

@@ -881,3 +881,33 @@ def head_train_backward(x, w0, b0, w1, b1, w2, dlogits, want=(True,) * 7):
     _lib.check(lib.pdsc_head_train_backward(_p(x), _p(w0), _p(b0), _p(w1), _p(b1), _p(w2), _p(dlogits), *(_p(o) for o in outs), _p(ws),
                                             ws.numel() * 8, m, _stream()), "pdsc_head_train_backward")
     return tuple(outs)
+
+
+# ---- the trainer's update (pdsc_optim_*; pointdsc_amd.optim builds the call structs) -----------------------------------------------
+def optim_tensors_per_launch() -> int:
+    """Rows of a step's table that one launch carries in its kernel arguments (pdsc_optim_tensors_per_launch)."""
+    return int(_lib.load().pdsc_optim_tensors_per_launch())
+
+
+def optim_state_bytes(kind: int, numels) -> int:
+    """Bytes of the opaque state buffer of one parameter group (pdsc_optim_state_bytes); zero-filled = fresh."""
+    arr = (C.c_longlong * len(numels))(*numels)
+    n = int(_lib.load().pdsc_optim_state_bytes(kind, C.cast(arr, C.c_void_p), len(numels)))
+    if n == 0:
+        raise ValueError(f"optim_state_bytes: kind {kind}, {len(numels)} tensors: unsupported")
+    return n
+
+
+def optim_check(call) -> None:
+    """Scan the present gradients of one group for NaN / Inf into the guard flag (pdsc_optim_check); enqueue only."""
+    _lib.check(_lib.load().pdsc_optim_check(C.byref(call), _stream()), "pdsc_optim_check")
+
+
+def optim_update(call) -> None:
+    """Apply the rule to one group unless the guard flag is set (pdsc_optim_update); enqueue only."""
+    _lib.check(_lib.load().pdsc_optim_update(C.byref(call), _stream()), "pdsc_optim_update")
+
+
+def optim_finish(call, last: bool) -> None:
+    """Commit one group's per-tensor step state; `last`: settle the guard block (pdsc_optim_finish); enqueue only."""
+    _lib.check(_lib.load().pdsc_optim_finish(C.byref(call), int(bool(last)), _stream()), "pdsc_optim_finish")

@@ -149,7 +149,15 @@ def train(a):
         model.load_state_dict(workloads.state_dict("n5000_b32", model.state_dict()))
     model = model.cuda()
     batches = [synthetic.make_batch(16, 1000, seed=100 + 16 * i, inlier_ratio=0.3) for i in range(a.num_batches)]
-    optimizer = torch.optim.Adam(model.parameters(), lr=a.lr, weight_decay=1e-6)          # config.py:48-53
+    # config.py:48-53 and train_3DMatch.py:48-66: ADAM (the default) or SGD with momentum 0.9, weight decay 1e-6
+    if a.device_optimizer:          # guard, update and skip decision on the device: train_epoch reads nothing back in its loop
+        from pointdsc_amd import DeviceAdam, DeviceSGD
+        optimizer = (DeviceAdam(model.parameters(), lr=a.lr, weight_decay=1e-6) if a.optimizer == "adam" else
+                     DeviceSGD(model.parameters(), lr=a.lr, momentum=0.9, weight_decay=1e-6))
+    elif a.optimizer == "adam":
+        optimizer = torch.optim.Adam(model.parameters(), lr=a.lr, weight_decay=1e-6)
+    else:
+        optimizer = torch.optim.SGD(model.parameters(), lr=a.lr, momentum=0.9, weight_decay=1e-6)
     before = harness.validate(model.eval(), batches)
     steps = [batches[i % len(batches)] for i in range(a.train_steps)]
     meters = harness.train_epoch(model.train(), steps, optimizer, weights=(1.0, 1.0, a.weight_transformation))
@@ -157,7 +165,8 @@ def train(a):
     if a.json:
         print(json.dumps({"before": before, "train": meters, "after": after}))
         return
-    print(f"{a.train_steps} Adam steps (lr {a.lr}) over {a.num_batches} synthetic batches of 16 pairs x 1000 correspondences; "
+    name = ("Device" if a.device_optimizer else "") + {"adam": "Adam", "sgd": "SGD"}[a.optimizer]
+    print(f"{a.train_steps} {name} steps (lr {a.lr}) over {a.num_batches} synthetic batches of 16 pairs x 1000 correspondences; "
           f"{meters['skipped']} skipped; weighted loss {meters['loss_first']:.6f} -> {meters['loss_last']:.6f}")
     print(f"{'meter':18s} {'validation before':>18s} {'training mean':>18s} {'validation after':>18s}")
     for k in harness.VALIDATE_NAMES:
@@ -206,6 +215,9 @@ def main():
     ap.add_argument("--lr", type=float, default=1e-4, help="with --train (config.py:52)")
     ap.add_argument("--weight-transformation", type=float, default=0.0, help="with --train: config.py:43, the weight of the transformation "
                     "loss in the objective; above 0 the model is built with differentiable_trans=True")
+    ap.add_argument("--optimizer", choices=("adam", "sgd"), default="adam", help="with --train (train_3DMatch.py:48-66)")
+    ap.add_argument("--device-optimizer", action="store_true", help="with --train: pointdsc_amd.DeviceAdam / DeviceSGD instead of "
+                    "torch.optim's: finite-gradient guard, update and skip decision on the device (DESIGN.md section 8 f-25)")
     ap.add_argument("--fused-layers", action="store_true", help="with --train: the blocks' conv + batch-norm + ReLU groups as device kernels "
                     "(TrainablePointDSC(fused_layers=True), pointdsc_amd.conv_bn_relu)")
     ap.add_argument("--fused-linears", action="store_true", help="with --train: layer0, the q|k|v projections, fc_message.6 with its residual "

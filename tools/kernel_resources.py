@@ -31,7 +31,11 @@ and of section 8 f-13 (the backward of the feature-similarity matrix, next to it
 
 and of section 8 f-21 (correspondence RANSAC):
 
-    python tools/kernel_resources.py ransac"""
+    python tools/kernel_resources.py ransac
+
+and of section 8 f-25 (the optimiser's check, update and finish):
+
+    python tools/kernel_resources.py optim_"""
 import re
 import subprocess
 import sys

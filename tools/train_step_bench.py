@@ -17,6 +17,11 @@ These are CALL times, host work included.
     --fused-linears      (f-16) the whole step of TrainablePointDSC(fused_layers=True, fused_linears=True) next to
                          TrainablePointDSC(fused_layers=True) -- the step as it was before the flag existed -- likewise; with
                          --profile-steps the profiled model has both flags set
+    --device-optimizer   (f-25) the whole step of TrainablePointDSC(fused_layers=True, fused_linears=True) with pointdsc_amd.DeviceAdam
+                         (guard, update and skip decision on the device, nothing read back) next to the same model with
+                         torch.optim.Adam and the trainer's guard line exactly as harness.train_epoch has it (one boolean read per
+                         step), and next to torch.optim.Adam with no guard; with --profile-steps the profiled step is DeviceAdam's,
+                         or with --torch-guard the guarded torch.optim.Adam step it replaces
     --profile-steps K    run K device steps and exit: the program of the one `rocprofv3 --kernel-trace --stats` run
     --breakdown FILE     group the per-kernel table tools/rocpd_kernel_stats.py made of that run into the step's parts (GROUPS)"""
 import argparse
@@ -34,6 +39,7 @@ GROUPS = [      # first match wins
     ("attention backward", r"att_bwd_"),
     ("M forward + backward", r"gram_rows_kernel<2|feature_compat_backward"),
     ("losses", r"pdsc::(cls_|sm_loss_|trans_partial|trans_finish)"),
+    ("optimiser (guard check, update, finish)", r"pdsc::optim_"),
     ("parameter-gradient merge (train_tile.h, both below)", r"pdsc::tt_merge_"),
     ("plain linears (layer0, q|k|v, fc_message.6, head)", r"pdsc::lth?_"),
     ("fused point-wise layers (conv + BN + ReLU)", r"pdsc::pwt_"),
@@ -71,6 +77,8 @@ def main():
     ap.add_argument("--breakdown", default=None)
     ap.add_argument("--fused-layers", action="store_true")
     ap.add_argument("--fused-linears", action="store_true")
+    ap.add_argument("--device-optimizer", action="store_true")
+    ap.add_argument("--torch-guard", action="store_true", help="with --device-optimizer --profile-steps: profile the torch side")
     a = ap.parse_args()
     if a.breakdown:
         return breakdown(a.breakdown)
@@ -79,7 +87,7 @@ def main():
     import torch.nn.functional as F
     import train_oracle as TO
     from loss_bench import timed, torch_sm_matrix
-    from pointdsc_amd import ClassificationLoss, PointDSC, SpectralMatchingLoss, synthetic, training
+    from pointdsc_amd import ClassificationLoss, DeviceAdam, PointDSC, SpectralMatchingLoss, synthetic, training
     assert torch.cuda.is_available(), "train_step_bench needs the GPU: a CPU run gives no time"
     dev, bs, n = "cuda:0", a.bs, a.n
 
@@ -100,21 +108,31 @@ def main():
     gt = batch["gt_labels"]
     cls_fn, sm_fn = ClassificationLoss(False), SpectralMatchingLoss(False)
 
-    def make_step(fused, fused_linears=False):
+    def make_step(fused, fused_linears=False, optimizer="torch", guard=False):
         model = training.TrainablePointDSC(num_layers=a.layers, fused_layers=fused, fused_linears=fused_linears)
         model.load_state_dict({k: v.clone() for k, v in state.items()}, strict=True)
         model = model.to(dev).train()
-        opt = torch.optim.Adam(model.parameters(), lr=1e-4, weight_decay=1e-6)
+        cls = DeviceAdam if optimizer == "device" else torch.optim.Adam
+        opt = cls(model.parameters(), lr=1e-4, weight_decay=1e-6)
+        params = [p for p in model.parameters() if p.requires_grad]
 
         def step():
             opt.zero_grad()
             res = model(data)
             loss = cls_fn(res["final_labels"], gt, device_stats=True)["loss"] + sm_fn(res["M"], gt)
             loss.backward()
-            opt.step()
+            if guard:          # harness.train_epoch's lines for an optimiser without a guard of its own
+                grads = [p.grad for p in params if p.grad is not None]
+                if bool(torch.stack([torch.isfinite(g).all() for g in grads]).all()):
+                    opt.step()
+            else:
+                opt.step()
             return loss
         return step
-    device_step = make_step(a.fused_layers or a.fused_linears, a.fused_linears)
+    if a.device_optimizer:
+        device_step = make_step(True, True, "torch", True) if a.torch_guard else make_step(True, True, "device")
+    else:
+        device_step = make_step(a.fused_layers or a.fused_linears, a.fused_linears)
 
     if a.profile_steps:
         for _ in range(a.profile_steps):
@@ -123,6 +141,22 @@ def main():
         return
 
     print(f"bs={bs} N={n} layers={a.layers}: microseconds per call, median of {a.rounds} windows of {a.window} s (min .. max)")
+    if a.device_optimizer:
+        guarded_step, plain_step = make_step(True, True, "torch", True), make_step(True, True, "torch", False)
+        t_dev, t_guard, t_plain = [], [], []
+        for _ in range(a.rounds):                         # alternate the three steps
+            t_dev.append(timed(device_step, a.warmup, a.window)[0])
+            t_guard.append(timed(guarded_step, a.warmup, a.window)[0])
+            t_plain.append(timed(plain_step, a.warmup, a.window)[0])
+        md, mg = statistics.median(t_dev), statistics.median(t_guard)
+        print(f"  training step (forward, 2 losses, backward, guard, Adam), fused_layers=True, fused_linears=True:")
+        print(f"    DeviceAdam (guard on the device)            {spread(t_dev)}")
+        print(f"    torch.optim.Adam + the trainer's guard line {spread(t_guard)}   guarded torch / DeviceAdam {mg / md:6.3f}")
+        print(f"    torch.optim.Adam, no guard                  {spread(t_plain)}")
+        room = (max(t_dev) - min(t_dev)) + (max(t_guard) - min(t_guard))
+        print(f"    DeviceAdam median - guarded torch median = {md - mg:+.1f} us; the two sides' min..max spreads add up to {room:.1f} us: "
+              f"{'not above' if md - mg <= room else 'ABOVE'} the parent's behaviour by more than the spread")
+        return
     if a.fused_linears:
         layers_step = make_step(True)
         t_both, t_layers = [], []
